@@ -462,6 +462,27 @@ def long_grid_block(ctx, zs, ms, ks, mthr, pairs, reps=12):
     return out
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, res, pairs, max_bytes=DUMP_MAX_BYTES):
+    """Write the spectra a caller of the timed path receives, {(a,b): (P_1h, P_2h)}, as float64
+    `<out_dir>/P_<a>_<b>_{1h,2h}.npy`.  Above `max_bytes` in all, every array is reduced to the same
+    fixed, seeded sample of its (z,k) points (ascending flat indices), so two builds compare point for point."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {f"P_{a}_{b}_{t}": np.ascontiguousarray(res[(a, b)][i], dtype=np.float64)
+            for (a, b) in pairs for i, t in enumerate(("1h", "2h"))}
+    budget = max_bytes - 128 * len(arrs)          # less one .npy header per file
+    if sum(x.nbytes for x in arrs.values()) > budget:
+        size = next(iter(arrs.values())).size
+        keep = budget // (8 * len(arrs))
+        idx = np.sort(np.random.default_rng(20240901).choice(size, keep, replace=False))
+        arrs = {k: x.reshape(-1)[idx] for k, x in arrs.items()}
+    for k, x in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), x)
+    return sorted(arrs)
+
+
 # ------------------------------------------------------------------------------------------------
 # byte and instruction models of the three large kernels
 # ------------------------------------------------------------------------------------------------
@@ -520,7 +541,12 @@ def main():
                     help="also record per-stage HIP events (eager launches only; a few us of stream time each)")
     ap.add_argument("--cpu-sample-nz", type=int, default=8)
     ap.add_argument("--dry-run", action="store_true", help="launcher only: print the rank commands and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the spectra of the last timed step as DIR/P_<a>_<b>_{1h,2h}.npy "
+                         "(float64, (nz, nk); a fixed seeded sample of the points above 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.dry_run):
         sys.exit(spawn_ranks(args, sys.argv[1:]))
@@ -685,6 +711,11 @@ def main():
     ctx.sync()
     dt = time.perf_counter() - t0
     read_brackets()
+    # what the last timed step computed, before any later pass overwrites it (untimed)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        spec.wait_gathered()
+        dumped = {"dir": os.path.abspath(args.dump_outputs), "files": dump_outputs(args.dump_outputs, spec.results(), PAIRS)}
     dt_all = comm.allgather_host([dt]).reshape(-1) if world > 1 else np.array([dt])
     dt_max = float(dt_all.max())
     # The collective of a step, separately: in the timed loop the gather runs on the communication
@@ -1057,6 +1088,8 @@ def main():
                     "the constant left-fill prefix substituted from a hint), so this figure exceeds the HBM peak: it is a "
                     "speed-up equivalent, NOT a bandwidth, and no roofline fraction is formed from it"},
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if gather_ms is not None:
         out["gather_ms_per_step"] = gather_ms["max_over_ranks_ms"]
         out["gather"] = gather_ms

@@ -375,6 +375,32 @@ def test_bench_launcher_deadline(monkeypatch, capfd):
     assert rc != 0 and "deadline" in err and "rank 0 started" in out
 
 
+def test_bench_dump_outputs_writes_the_spectra_and_samples_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: one float64 file per (pair, term) with the spectrum as the caller gets it; above the
+    size cap every file holds the same fixed, seeded sample of points, identical from call to call."""
+    import importlib.util
+    from conftest import REPO
+    spec = importlib.util.spec_from_file_location("bench_under_test3", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(1)
+    res = {p: (rng.standard_normal((5, 64)), rng.standard_normal((5, 64))) for p in bench.PAIRS}
+    names = bench.dump_outputs(str(tmp_path / "full"), res, bench.PAIRS)
+    assert len(names) == 2 * len(bench.PAIRS) and "P_g_electron_2h" in names
+    for (a, b) in bench.PAIRS:
+        for i, t in enumerate(("1h", "2h")):
+            got = np.load(tmp_path / "full" / f"P_{a}_{b}_{t}.npy")
+            assert got.dtype == np.float64 and np.array_equal(got, res[(a, b)][i])
+    cap = 12 * (8 * 100 + 128)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), res, bench.PAIRS, max_bytes=cap)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == sorted(os.listdir(tmp_path / "s2")) and len(files) == 12
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= cap
+    a1, a2 = np.load(tmp_path / "s1" / "P_nfw_nfw_1h.npy"), np.load(tmp_path / "s2" / "P_nfw_nfw_1h.npy")
+    assert a1.shape == (100,) and np.array_equal(a1, a2) and np.isin(a1, res[("nfw", "nfw")][0]).all()
+
+
 def _rehearsal_rank(rank, world, tag, directory, q):
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
