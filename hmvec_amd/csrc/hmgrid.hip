@@ -349,65 +349,153 @@ static int get_fused_plan(hmg_ctx* c, int nxs, FusedPlan** out) {
     return 0;
 }
 
-template <int MAXB, int MAXP, int SPECM = 0>
+// Raise the kernel's dynamic-LDS limit when the launch needs more than the default 48 KiB, launch, check.
+template <class... P, class... Args>
+static int launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args) {
+    if (lds > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- one row in LDS (profile_fused_kernel and the kernels built around it) ------------------------------------------
+// The row shapes that are compiled in: MAXB / MAXP butterflies / unpack pairs per thread, SPECM the length M whose plan is
+// compiled in (strides, twiddle steps, index multipliers are immediates; 0: the run-time plan), TABLE whether
+// profile_table_kernel exists in that shape.
+template <int B, int P, int S, bool T = false>
+struct RowShape {
+    static constexpr int MAXB = B, MAXP = P, SPECM = S;
+    static constexpr bool TABLE = T;
+};
+enum Shape { SHAPE_2500, SHAPE_500, SHAPE_1000, SHAPE_1500, SHAPE_2000, SHAPE_3000, SHAPE_RT12, SHAPE_RT23, SHAPE_RT24, SHAPE_RT48 };
+template <class F>
+static int with_shape(Shape s, F&& f) {
+    switch (s) {
+        case SHAPE_2500: return f(RowShape<2, 3, 2500, true>{});
+        case SHAPE_500: return f(RowShape<1, 1, 500>{});
+        case SHAPE_1000: return f(RowShape<1, 1, 1000>{});
+        case SHAPE_1500: return f(RowShape<1, 2, 1500>{});
+        case SHAPE_2000: return f(RowShape<2, 2, 2000>{});
+        case SHAPE_3000: return f(RowShape<3, 3, 3000>{});
+        case SHAPE_RT12: return f(RowShape<1, 2, 0>{});
+        case SHAPE_RT23: return f(RowShape<2, 3, 0>{});
+        case SHAPE_RT24: return f(RowShape<2, 4, 0, true>{});
+        case SHAPE_RT48: return f(RowShape<4, 8, 0, true>{});
+    }
+    return fail("invalid argument", "internal: unknown row shape", __FILE__, __LINE__);
+}
+
+// The shape for a plan.  Compile-time plans: nxs = 5000 (the headline length) and 1000, 2000, 3000, 4000, 6000 (the last
+// one only when its rows' support does not let the long-grid route take it).  Table builds: the nxs = 5000 plan and two
+// run-time-plan shapes cover every one-row length.
+static Shape row_shape(const hmg_ctx* c, const FusedPlan& FP, bool table) {
+    const FftPlanDev& pl = FP.plan;
+    const bool ct = FUSED_NT == 512 && !c->fused_generic;       // (fused_generic: testing, force the run-time plan)
+    if (ct && pl.M == 2500 && pl.npass == 5 && pl.radix[0] == 4 && pl.radix[1] == 5 && pl.radix[2] == 5 &&
+        pl.radix[3] == 5 && pl.radix[4] == 5)
+        return SHAPE_2500;
+    if (table) return FP.maxb <= 2 && FP.maxp <= 4 ? SHAPE_RT24 : SHAPE_RT48;
+    if (ct) switch (pl.M) {
+            case 500: return SHAPE_500;
+            case 1000: return SHAPE_1000;
+            case 1500: return SHAPE_1500;
+            case 2000: return SHAPE_2000;
+            case 3000: return SHAPE_3000;
+        }
+    if (FP.maxb <= 1 && FP.maxp <= 2) return SHAPE_RT12;
+    if (FP.maxb <= 2 && FP.maxp <= 3) return SHAPE_RT23;
+    if (FP.maxb <= 2 && FP.maxp <= 4) return SHAPE_RT24;
+    return SHAPE_RT48;
+}
+
+// What may ride in the launch of a profile transform's rows (in), and what did (out).
+struct FftRiders {
+    const ChainArgs* C = nullptr;       // a per-z chain: nchain workgroups in front of the rows, chain_lds bytes of LDS
+    int nchain = 0;
+    size_t chain_lds = 0;
+    const NfwArgs* N = nullptr;         // analytic NFW rows behind them (tensor group): nfw_blocks workgroups
+    size_t nfw_blocks = 0;
+    const double* rho_tab = nullptr;    // the profile from a table (hmg_profile_fft_table); the family parameters are not read
+    int rho_shared = 0;
+    bool chain_done = false;            // the chain rode with the rows (else the caller issues it on its own)
+    bool nfw_done = false;              // the NFW rows rode with them
+};
+
+// The route of one profile transform, from the context's switches and the part alone: nothing is measured here (the
+// support bound that decides whether the long-grid route takes the launch is measured in profile_fft_pruned).
+struct FftRoute {
+    bool xs_aligned = false;    // the row kernels read x in 16-B pairs
+    bool try_long = false;      // the pruned / narrow-band long-grid route is tried first
+    FusedPlan* FP = nullptr;    // then one row in LDS with this plan and shape; nullptr: rocFFT
+    Shape shape = SHAPE_RT48;
+    bool grouped = false;       // a chain shares the rows' launch
+    bool tensor = false;        // ... and the tensor group can take it: the chain's sigma^2 -> n, b link and NFW rows too
+};
+static int fft_route(hmg_ctx* c, const hmg_profile_fft_part& p, bool chain, bool table, FftRoute* r) {
+    *r = FftRoute{};
+    r->xs_aligned = p.d_xs && ((uintptr_t)p.d_xs % 16) == 0;
+    if (!c->use_fused_fft || !r->xs_aligned) return 0;
+    if (get_fused_plan(c, p.nxs, &r->FP)) return 1;
+    // Rows longer than M = 2500 that would still fit LDS as one row (run-time plan, one or two workgroups per CU) are
+    // faster on the long-grid route when it applies - Config-3 grid, profile stage, nxs = 6000 / 8000 / 12000: 0.465 /
+    // 0.551 / 0.976 ms as one row against 0.342 / 0.400 / 0.438 ms (tools/probes/mid_length_routes.py)
+    r->try_long = c->use_pruned_fft && (!r->FP || r->FP->plan.M > c->fused_prefer_m);
+    if (!r->FP) return 0;
+    r->shape = row_shape(c, *r->FP, table);
+    // the group kernels read the rows' output-side scalars from the record of the rows stage; a caller without
+    // one (no hint arrays: ks not ascending) gets the stand-alone row kernel and its chain as a launch of its own
+    r->grouped = chain && !table && FUSED_NT == 512 && p.d_rowsc && p.d_nconst;
+    // The tensor kernel exists for compile-time plans only: the run-time-plan row kernel needs 80 registers (6 wavefronts
+    // per SIMD), and NFW rows sharing that allocation lose more than the kernel boundary costs (MI355X, Config-3 grid,
+    // nxs = 3000 forced onto the run-time plan: 0.560 against 0.530 ms per step).  Nor does it take a length the long-grid
+    // route might take.
+    const bool ct = with_shape(r->shape, [](auto s) { return (int)(decltype(s)::SPECM != 0); });
+    r->tensor = r->grouped && c->use_tensor_group && ct && !r->try_long;
+    return 0;
+}
+
+// The launchers of the rows in shape S: the table kernel, the row kernel, and - grouped - profile_group_kernel with the
+// chain in front of the rows or tensor_group_kernel with the NFW rows behind them as well.
+template <class S>
+static int launch_table(hmg_ctx* c, const FusedArgs& A, int rows) {
+    const size_t lds = (size_t)A.plan.M * 16 + 32 * sizeof(double);
+    if constexpr (S::TABLE)
+        return launch_lds(profile_table_kernel<FUSED_NT, S::MAXB, S::MAXP, S::SPECM>, dim3(rows), dim3(FUSED_NT), lds, c->stream, A);
+    else
+        return fail("invalid argument", "internal: no table kernel of this row shape", __FILE__, __LINE__);
+}
+
+template <class S>
 static int launch_fused(hmg_ctx* c, const FusedArgs& A, int rows) {
     const size_t lds = (size_t)A.plan.M * 16 + 32 * sizeof(double);
-    if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)profile_fused_kernel<FUSED_NT, MAXB, MAXP, SPECM>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // (Tried and dropped: fewer workgroups that loop over rows, to take the ~4 us of workgroup launch and
     // first-load latency per row off the path.  The loop-carried state spills under the 64-VGPR cap:
     // 0.21 -> 0.56-0.61 ms, with 1023, 2047 or one workgroup per row alike.)
-    hipLaunchKernelGGL((profile_fused_kernel<FUSED_NT, MAXB, MAXP, SPECM>), dim3(rows), dim3(FUSED_NT), lds,
-                       c->stream, A);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_lds(profile_fused_kernel<FUSED_NT, S::MAXB, S::MAXP, S::SPECM>, dim3(rows), dim3(FUSED_NT), lds, c->stream, A);
 }
 
-template <int MAXB, int MAXP, int SPECM = 0>
-static int launch_table(hmg_ctx* c, const FusedArgs& A, int rows) {
-    const size_t lds = (size_t)A.plan.M * 16 + 32 * sizeof(double);
-    if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)profile_table_kernel<FUSED_NT, MAXB, MAXP, SPECM>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((profile_table_kernel<FUSED_NT, MAXB, MAXP, SPECM>), dim3(rows), dim3(FUSED_NT), lds, c->stream, A);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// profile_group_kernel = the fused row kernel with `nchain` per-z chain workgroups in front of the rows;
-// with N: tensor_group_kernel, the analytic NFW rows behind them in the same grid
-template <int MAXB, int MAXP, int SPECM = 0>
-static int launch_fused_group(hmg_ctx* c, const FusedArgs& A, int rows, const ChainArgs& C, int nchain, size_t chain_lds,
-                              const NfwArgs* N = nullptr, size_t nfw_blocks = 0) {
+template <class S>
+static int launch_group(hmg_ctx* c, const FusedArgs& A, int rows, const FftRiders& R) {
+    constexpr int B = S::MAXB, P = S::MAXP, M = S::SPECM;
+    const ChainArgs& C = *R.C;
     size_t lds = (size_t)A.plan.M * 16 + 32 * sizeof(double);
-    if (chain_lds > lds) lds = chain_lds;
-    if (N || C.has_mf) {      // (only the tensor kernel carries the chain's sigma^2 -> n, b link)
-        if constexpr (SPECM != 0) {
+    if (R.chain_lds > lds) lds = R.chain_lds;
+    if (R.N || C.has_mf) {      // (only the tensor kernel carries the chain's sigma^2 -> n, b link)
+        if constexpr (M != 0) {
             const NfwArgs none{};
-            if (!N) { N = &none; nfw_blocks = 0; }
-            REQUIRE((size_t)rows + nchain + nfw_blocks <= 2147483647u, "bad grid");
-            if (lds > 48 * 1024)
-                HIP_TRY(hipFuncSetAttribute((const void*)tensor_group_kernel<MAXB, MAXP, SPECM>,
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((tensor_group_kernel<MAXB, MAXP, SPECM>), dim3((unsigned)(rows + nchain + nfw_blocks)),
-                               dim3(FUSED_NT), lds, c->stream, C, A, nchain, rows, N->T, N->acoef, N->ktile, N->nm, N->nk, N->cs,
-                               N->rss, N->zs, N->ks, N->uk);
-            HIP_TRY(hipGetLastError());
-            return 0;
+            const NfwArgs& N = R.N ? *R.N : none;
+            const size_t nfw_blocks = R.N ? R.nfw_blocks : 0;
+            REQUIRE((size_t)rows + R.nchain + nfw_blocks <= 2147483647u, "bad grid");
+            return launch_lds(tensor_group_kernel<B, P, M>, dim3((unsigned)(rows + R.nchain + nfw_blocks)), dim3(FUSED_NT),
+                              lds, c->stream, C, A, R.nchain, rows, N.T, N.acoef, N.ktile, N.nm, N.nk, N.cs, N.rss, N.zs,
+                              N.ks, N.uk);
         } else {
             REQUIRE(false, "internal: the tensor group is compiled for compile-time plans only");
         }
     }
-    if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)profile_group_kernel<MAXB, MAXP, SPECM>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((profile_group_kernel<MAXB, MAXP, SPECM>), dim3(rows + nchain), dim3(FUSED_NT), lds, c->stream, C,
-                       A, nchain);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_lds(profile_group_kernel<B, P, M>, dim3(rows + R.nchain), dim3(FUSED_NT), lds, c->stream, C, A, R.nchain);
 }
-
 
 // ---- pruned long-grid route (profile_pruned_kernel) -------------------------------------------------------
 // Lengths of the sub-transforms that are compiled in.  A launch takes the smallest one that divides M = nxs/2
@@ -597,141 +685,67 @@ static int profile_fft_pruned(hmg_ctx* c, const FusedArgs& A0, int rows, bool ca
     return bracket_close(c, stop);
 }
 
-// One hmg_profile_fft; with a chain (nchain > 0) and a length the in-LDS transform takes, chain and rows share
-// the launch, otherwise *chain_done stays 0 and the caller issues the chain on its own.
-// rho_tab != nullptr: the profile comes from a table (hmg_profile_fft_table); *taken = 0 when no in-LDS route takes the
-// launch (the caller then runs its rocFFT chain); the family parameters of p are not read.
-// The length M of a one-row transform whose plan is compiled in (strides, twiddle steps, index multipliers are immediates):
-// nxs = 5000 (the headline length) and 1000, 2000, 3000, 4000, 6000; 0: the run-time plan.
-static int fused_ct_plan(const hmg_ctx* c, const FftPlanDev& pl) {
-    if (FUSED_NT != 512 || c->fused_generic) return 0;       // (fused_generic: testing, force the run-time plan)
-    if (pl.M == 2500 && pl.npass == 5 && pl.radix[0] == 4 && pl.radix[1] == 5 && pl.radix[2] == 5 && pl.radix[3] == 5 &&
-        pl.radix[4] == 5)
-        return 2500;
-    if (pl.M == 500 || pl.M == 1000 || pl.M == 1500 || pl.M == 2000 || pl.M == 3000) return pl.M;
-    return 0;
+// The row kernels' arguments for part p: with the tables of a one-row plan FP, or none (the long-grid routes add their own).
+static FusedArgs fused_args(int nm, int nk, const hmg_profile_fft_part& p, const FusedPlan* FP, const FftRiders& R) {
+    FusedArgs A{};
+    if (FP) { A.plan = FP->plan; A.twM = FP->twM; A.twN = FP->twN; }
+    A.nxs = p.nxs; A.nm = nm; A.nk = nk; A.do_norm = p.do_mass_norm;
+    A.xs = p.d_xs; A.kts = p.d_kts;
+    A.amp = p.d_amp; A.xc = p.d_xc; A.alpha = p.d_alpha; A.expo = p.d_expo;
+    A.amp_c = p.amp_const; A.xc_c = p.xc_const; A.alpha_c = p.alpha_const; A.expo_c = p.expo_const; A.gamma = p.gamma;
+    A.step = p.fft_step; A.cmax = p.d_cmax; A.rss = p.d_rss; A.zs = p.d_zs; A.ks = p.d_ks; A.post = p.d_post; A.out = p.d_out;
+    A.nconst = p.d_nconst; A.cconst = p.d_cconst;
+    A.logx = p.d_logxs;
+    A.rho_tab = R.rho_tab; A.rho_shared = R.rho_shared;
+    // the row scalars a rows part left for exactly this transform (they carry the left-fill count: hints required)
+    A.rowsc = (p.d_rowsc && p.d_nconst) ? p.d_rowsc : nullptr;
+    return A;
 }
 
-// N != nullptr: analytic NFW rows that may ride in the same launch when chain and rows share one (*nfw_done = 1 then).
-static int profile_fft_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_profile_fft_part& p, const ChainArgs* C,
-                            int nchain, size_t chain_lds, int* chain_done, const double* rho_tab = nullptr,
-                            int rho_shared = 0, int* taken = nullptr, const NfwArgs* N = nullptr, size_t nfw_blocks = 0,
-                            int* nfw_done = nullptr) {
+// One hmg_profile_fft (or, with R.rho_tab, hmg_profile_fft_table), on the route fft_route decides; the riders of R that
+// the route takes ride in the rows' launch and are marked done.
+static int profile_fft_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_profile_fft_part& p, FftRiders& R) {
     const int nxs = p.nxs;
     const double step = p.fft_step;
-    const double *xs = p.d_xs, *kts = p.d_kts, *amp = p.d_amp, *xcs = p.d_xc, *alpha = p.d_alpha, *expo = p.d_expo;
-    const double amp_c = p.amp_const, xc_c = p.xc_const, alpha_c = p.alpha_const, expo_c = p.expo_const, gamma = p.gamma;
-    const double *cmax = p.d_cmax, *rss = p.d_rss, *zs = p.d_zs, *ks = p.d_ks, *post = p.d_post, *logxs = p.d_logxs;
-    const int do_mass_norm = p.do_mass_norm;
-    double* out = p.d_out;
-    int* nconst = p.d_nconst;
-    double* cconst = p.d_cconst;
-    if (chain_done) *chain_done = 0;
-    if (nfw_done) *nfw_done = 0;
-    REQUIRE(c && xs && kts && cmax && rss && zs && ks && out, "NULL argument");
-    REQUIRE((nconst == nullptr) == (cconst == nullptr), "pass both hint arrays or neither");
+    const double *xs = p.d_xs, *kts = p.d_kts, *cmax = p.d_cmax, *rss = p.d_rss, *zs = p.d_zs, *ks = p.d_ks;
+    R.chain_done = R.nfw_done = false;
+    REQUIRE(c && xs && kts && cmax && rss && zs && ks && p.d_out, "NULL argument");
+    REQUIRE((p.d_nconst == nullptr) == (p.d_cconst == nullptr), "pass both hint arrays or neither");
     REQUIRE(nz > 0 && nm > 0 && nk > 0, "empty grid");
     REQUIRE(nxs >= 4, "nxs too small");
     const int nh = nxs / 2;  // rfft output length is nh+1
     const int rows = nz * nm;
     REQUIRE(step > 0.0, "step must be positive");
-    const bool xs_aligned = ((uintptr_t)xs % 16) == 0;   // the row kernels read x in 16-B pairs
-    if (c->use_fused_fft && xs_aligned) {
-        FusedPlan* FP = nullptr;
-        if (get_fused_plan(c, nxs, &FP)) return 1;
-        // Rows longer than M = 2500 that would still fit LDS as one row (run-time plan, one or two workgroups per CU) are
-        // faster on the long-grid route when it applies - Config-3 grid, profile stage, nxs = 6000 / 8000 / 12000: 0.465 /
-        // 0.551 / 0.976 ms as one row against 0.342 / 0.400 / 0.438 ms (tools/probes/mid_length_routes.py)
-        const bool prefer_long = FP && FP->plan.M > c->fused_prefer_m;
-        if ((!FP || prefer_long) && c->use_pruned_fft) {
-            // a grid too long for one LDS row: the pruned decomposition, if the support of the rows is short enough
-            FusedArgs A{};
-            A.nxs = nxs; A.nm = nm; A.nk = nk; A.do_norm = do_mass_norm;
-            A.xs = xs; A.twM = nullptr; A.twN = nullptr; A.kts = kts;
-            A.amp = amp; A.xc = xcs; A.alpha = alpha; A.expo = expo;
-            A.amp_c = amp_c; A.xc_c = xc_c; A.alpha_c = alpha_c; A.expo_c = expo_c; A.gamma = gamma;
-            A.step = step; A.cmax = cmax; A.rss = rss; A.zs = zs; A.ks = ks; A.post = post; A.out = out;
-            A.nconst = nconst; A.cconst = cconst;
-            A.logx = logxs;
-            A.rho_tab = rho_tab; A.rho_shared = rho_shared;
-            int took = 0;
-            if (profile_fft_pruned(c, A, rows, FP != nullptr, &took)) return 1;
-            if (took) {
-                if (taken) *taken = 1;
-                return 0;
-            }
-        }
-        if (FP) {
-            FusedArgs A;
-            A.plan = FP->plan; A.nxs = nxs; A.nm = nm; A.nk = nk; A.do_norm = do_mass_norm;
-            A.xs = xs; A.twM = FP->twM; A.twN = FP->twN; A.kts = kts;
-            A.amp = amp; A.xc = xcs; A.alpha = alpha; A.expo = expo;
-            A.amp_c = amp_c; A.xc_c = xc_c; A.alpha_c = alpha_c; A.expo_c = expo_c; A.gamma = gamma;
-            A.step = step; A.cmax = cmax; A.rss = rss; A.zs = zs; A.ks = ks; A.post = post; A.out = out;
-            A.nconst = nconst; A.cconst = cconst;
-            A.logx = logxs;
-            A.rho_tab = rho_tab; A.rho_shared = rho_shared;
-            // the row scalars a rows part left for exactly this transform (they carry the left-fill count: hints required)
-            A.rowsc = (p.d_rowsc && nconst) ? p.d_rowsc : nullptr;
-            int stop = -1;
-            if (bracket_open(c, HMG_KERNEL_PROFILE_FFT, &stop)) return 1;
-            if (rho_tab) {      // table builds: the nxs = 5000 plan and two run-time-plan shapes cover every one-row length
-                int rc;
-                if (FUSED_NT == 512 && FP->plan.M == 2500 && !c->fused_generic) rc = launch_table<2, 3, 2500>(c, A, rows);
-                else if (FP->maxb <= 2 && FP->maxp <= 4) rc = launch_table<2, 4>(c, A, rows);
-                else rc = launch_table<4, 8>(c, A, rows);
-                if (rc) return 1;
-                if (taken) *taken = 1;
-                return bracket_close(c, stop);
-            }
-            if (!logxs && rows >= 8192) {   // no prepared table: its own launch pays from ~8000 rows (MI355X: -1 % at 16384 rows, +2 % at 4096)
-                if (ensure_scratch(c, 2, (size_t)nxs * 8)) return 1;
-                hipLaunchKernelGGL(logx_kernel, grid1d((size_t)nxs, 256), dim3(256), 0, c->stream, nxs, xs,
-                                   (double*)c->scratch[2]);
-                HIP_TRY(hipGetLastError());
-                A.logx = (const double*)c->scratch[2];
-            }
-            int rc;
-            const int mb = FP->maxb, mp = FP->maxp;
-            const FftPlanDev& pl = FP->plan;
-            const bool spec2500 = fused_ct_plan(c, pl) == 2500;
-            // the group kernels read the rows' output-side scalars from the record of the rows stage; a caller without
-            // one (no hint arrays: ks not ascending) gets the stand-alone row kernel and its chain as a launch of its own
-            const bool grouped = C && nchain > 0 && FUSED_NT == 512 && A.rowsc != nullptr;
-            // lengths with a compile-time plan (fused_passes_ct): nxs = 1000, 2000, 3000, 4000, 6000 (the last one only
-            // when its rows' support does not let the long-grid route take it)
-            const int ctM = spec2500 ? 0 : fused_ct_plan(c, pl);
-            if (grouped) {
-                if (spec2500) rc = launch_fused_group<2, 3, 2500>(c, A, rows, *C, nchain, chain_lds, N, nfw_blocks);
-                else if (ctM == 500) rc = launch_fused_group<1, 1, 500>(c, A, rows, *C, nchain, chain_lds, N, nfw_blocks);
-                else if (ctM == 1000) rc = launch_fused_group<1, 1, 1000>(c, A, rows, *C, nchain, chain_lds, N, nfw_blocks);
-                else if (ctM == 1500) rc = launch_fused_group<1, 2, 1500>(c, A, rows, *C, nchain, chain_lds, N, nfw_blocks);
-                else if (ctM == 2000) rc = launch_fused_group<2, 2, 2000>(c, A, rows, *C, nchain, chain_lds, N, nfw_blocks);
-                else if (ctM == 3000) rc = launch_fused_group<3, 3, 3000>(c, A, rows, *C, nchain, chain_lds, N, nfw_blocks);
-                else if (mb <= 1 && mp <= 2) rc = launch_fused_group<1, 2>(c, A, rows, *C, nchain, chain_lds, N, nfw_blocks);
-                else if (mb <= 2 && mp <= 3) rc = launch_fused_group<2, 3>(c, A, rows, *C, nchain, chain_lds, N, nfw_blocks);
-                else if (mb <= 2 && mp <= 4) rc = launch_fused_group<2, 4>(c, A, rows, *C, nchain, chain_lds, N, nfw_blocks);
-                else rc = launch_fused_group<4, 8>(c, A, rows, *C, nchain, chain_lds, N, nfw_blocks);
-                if (!rc && chain_done) *chain_done = 1;
-                if (!rc && N && nfw_done) *nfw_done = 1;
-            }
-            else if (spec2500) rc = launch_fused<2, 3, 2500>(c, A, rows);                 // nxs = 5000, compile-time plan
-            else if (ctM == 500) rc = launch_fused<1, 1, 500>(c, A, rows);
-            else if (ctM == 1000) rc = launch_fused<1, 1, 1000>(c, A, rows);
-            else if (ctM == 1500) rc = launch_fused<1, 2, 1500>(c, A, rows);
-            else if (ctM == 2000) rc = launch_fused<2, 2, 2000>(c, A, rows);
-            else if (ctM == 3000) rc = launch_fused<3, 3, 3000>(c, A, rows);
-            else if (mb <= 1 && mp <= 2) rc = launch_fused<1, 2>(c, A, rows);
-            else if (mb <= 2 && mp <= 3) rc = launch_fused<2, 3>(c, A, rows);
-            else if (mb <= 2 && mp <= 4) rc = launch_fused<2, 4>(c, A, rows);
-            else rc = launch_fused<4, 8>(c, A, rows);
-            if (rc) return 1;
-            return bracket_close(c, stop);
-        }
+    const bool table = R.rho_tab != nullptr;
+    FftRoute r;
+    if (fft_route(c, p, R.C && R.nchain > 0, table, &r)) return 1;
+    if (r.try_long) {
+        // a grid too long for one LDS row: the pruned decomposition, if the support of the rows is short enough
+        int took = 0;
+        if (profile_fft_pruned(c, fused_args(nm, nk, p, nullptr, R), rows, r.FP != nullptr, &took)) return 1;
+        if (took) return 0;
     }
-    if (rho_tab) {              // no in-LDS route for this length: the caller's table -> rocFFT chain
-        if (taken) *taken = 0;
-        return 0;
+    if (r.FP) {
+        FusedArgs A = fused_args(nm, nk, p, r.FP, R);
+        int stop = -1;
+        if (bracket_open(c, HMG_KERNEL_PROFILE_FFT, &stop)) return 1;
+        if (!table && !A.logx && rows >= 8192) {   // no prepared table: its own launch pays from ~8000 rows (MI355X: -1 % at 16384 rows, +2 % at 4096)
+            if (ensure_scratch(c, 2, (size_t)nxs * 8)) return 1;
+            hipLaunchKernelGGL(logx_kernel, grid1d((size_t)nxs, 256), dim3(256), 0, c->stream, nxs, xs,
+                               (double*)c->scratch[2]);
+            HIP_TRY(hipGetLastError());
+            A.logx = (const double*)c->scratch[2];
+        }
+        // (one dispatch over the row shapes; the three launchers are instantiated in this order, which fixes the order of
+        // the kernels in the code object)
+        int rc;
+        if (table) rc = with_shape(r.shape, [&](auto s) { return launch_table<decltype(s)>(c, A, rows); });
+        else if (r.grouped) rc = with_shape(r.shape, [&](auto s) { return launch_group<decltype(s)>(c, A, rows, R); });
+        else rc = with_shape(r.shape, [&](auto s) { return launch_fused<decltype(s)>(c, A, rows); });
+        if (rc) return 1;
+        R.chain_done = r.grouped;
+        R.nfw_done = r.grouped && R.N;
+        return bracket_close(c, stop);
     }
     // ---- rocFFT path.  Chunk the batch so integrand + spectrum of a chunk stay inside the 256 MiB Infinity Cache:
     // the R2C input written by K4 and the spectrum read by K5 then never round-trip through HBM.
@@ -748,12 +762,17 @@ static int profile_fft_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_profil
     double* mnorm = (double*)c->scratch[2];
     const bool stage = (size_t)nh * sizeof(double) <= 64 * 1024;
     const size_t lds = stage ? (size_t)nh * sizeof(double) : 0;
-    int stop = -1;
-    if (bracket_open(c, HMG_KERNEL_PROFILE_FFT, &stop)) return 1;
+    int stop = -1;      // (the event bracket of the profile transform: the family's route only)
+    if (!table && bracket_open(c, HMG_KERNEL_PROFILE_FFT, &stop)) return 1;
     for (int r0 = 0; r0 < rows; r0 += chunk) {
         const int nr = rows - r0 < chunk ? rows - r0 : chunk;
-        hipLaunchKernelGGL(integrand_kernel, dim3(nr), dim3(256), 0, c->stream, nxs, r0, xs, amp, xcs,
-                           alpha, expo, amp_c, xc_c, alpha_c, expo_c, gamma, cmax, do_mass_norm, (int)xs_aligned, fin, mnorm);
+        if (table)
+            hipLaunchKernelGGL(table_integrand_kernel, dim3(nr), dim3(256), 0, c->stream, nxs, r0, xs, R.rho_tab,
+                               R.rho_shared, cmax, p.do_mass_norm, fin, mnorm);
+        else
+            hipLaunchKernelGGL(integrand_kernel, dim3(nr), dim3(256), 0, c->stream, nxs, r0, xs, p.d_amp, p.d_xc,
+                               p.d_alpha, p.d_expo, p.amp_const, p.xc_const, p.alpha_const, p.expo_const, p.gamma, cmax,
+                               p.do_mass_norm, (int)r.xs_aligned, fin, mnorm);
         HIP_TRY(hipGetLastError());
         FftPlan* P = nullptr;
         if (get_plan(c, nxs, nr, &P)) return 1;
@@ -763,10 +782,10 @@ static int profile_fft_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_profil
         FFT_TRY(rocfft_execute(P->plan, ib, ob, P->info));
         if (stage)
             hipLaunchKernelGGL(interp_kernel<true>, dim3(nr), dim3(256), lds, c->stream, nm, nk, nh, r0, step,
-                               (const double2*)fout, kts, mnorm, rss, zs, ks, post, out, nconst, cconst);
+                               (const double2*)fout, kts, mnorm, rss, zs, ks, p.d_post, p.d_out, p.d_nconst, p.d_cconst);
         else
             hipLaunchKernelGGL(interp_kernel<false>, dim3(nr), dim3(256), 0, c->stream, nm, nk, nh, r0, step,
-                               (const double2*)fout, kts, mnorm, rss, zs, ks, post, out, nconst, cconst);
+                               (const double2*)fout, kts, mnorm, rss, zs, ks, p.d_post, p.d_out, p.d_nconst, p.d_cconst);
         HIP_TRY(hipGetLastError());
     }
     return bracket_close(c, stop);
@@ -780,7 +799,8 @@ int hmg_profile_fft(hmg_ctx* c, int nz, int nm, int nk, int nxs, double step, co
                     const double* logxs) {
     const hmg_profile_fft_part p{nxs, step, xs, kts, amp, xcs, alpha, expo, amp_c, xc_c, alpha_c, expo_c, gamma,
                                  cmax, rss, zs, ks, do_mass_norm, post, out, nconst, cconst, logxs};
-    return profile_fft_impl(c, nz, nm, nk, p, nullptr, 0, 0, nullptr);
+    FftRiders R;
+    return profile_fft_impl(c, nz, nm, nk, p, R);
 }
 
 int hmg_profile_support_epoch(hmg_ctx* c, long long epoch) {
@@ -842,12 +862,9 @@ static int launch_power(hmg_ctx* c, const PowerArgs& A, int nz, int ms_split) {
     const int per_block = 64 * V;
     dim3 grid((A.nk + per_block - 1) / per_block, nz);
     const size_t lds = (size_t)ms_split * 3 * V * 64 * sizeof(double);
-    if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)power_kernel<NT, V>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int stop = -1;
     if (bracket_open(c, HMG_KERNEL_POWER, &stop)) return 1;
-    hipLaunchKernelGGL((power_kernel<NT, V>), grid, dim3(64 * ms_split), lds, c->stream, A);
-    HIP_TRY(hipGetLastError());
+    if (launch_lds(power_kernel<NT, V>, grid, dim3(64 * ms_split), lds, c->stream, A)) return 1;
     return bracket_close(c, stop);
 }
 
@@ -920,13 +937,9 @@ static int launch_power_batch(hmg_ctx* c, const BatchArgs& A, int nz) {
     dim3 grid((A.nk + per_block - 1) / per_block, nz);
     constexpr int NACC = NTR + NTR * (NTR + 1) / 2;
     const size_t lds = (size_t)8 * NACC * V * 64 * sizeof(double);
-    if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)power_batch_kernel<NT, NTR, V, W16, CODE>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int stop = -1;
     if (bracket_open(c, HMG_KERNEL_POWER, &stop)) return 1;
-    hipLaunchKernelGGL((power_batch_kernel<NT, NTR, V, W16, CODE>), grid, dim3(W16 ? 1024 : 512), lds, c->stream, A);
-    HIP_TRY(hipGetLastError());
+    if (launch_lds(power_batch_kernel<NT, NTR, V, W16, CODE>, grid, dim3(W16 ? 1024 : 512), lds, c->stream, A)) return 1;
     return bracket_close(c, stop);
 }
 
@@ -1265,15 +1278,16 @@ int hmg_group_rows(hmg_ctx* c, int nz, int nm, int nk, int nq, const hmg_massfn_
 
 // The launches of a profile group once its chain is set up: the rows of the transform with the chain (and, in a tensor group,
 // the NFW rows N) in their launch when the transform's route shares one, the chain as a launch of its own otherwise, the
-// generic coefficient rows behind them.  *nfw_done = 1 if the NFW rows rode along.
+// generic coefficient rows behind them.  *nfw_done: the NFW rows rode along.
 static int profile_group_launches(hmg_ctx* c, int nz, int nm, int nk, const hmg_profile_fft_part* fft, const ChainArgs& C, int one,
                                   const hmg_power_batch_desc* prep, const PbPlan& P, const NfwArgs* N = nullptr,
-                                  size_t nfw_blocks = 0, int* nfw_done = nullptr) {
-    int chain_done = 0;
-    if (fft && profile_fft_impl(c, nz, nm, nk, *fft, &C, one ? nz : 0, chain_lds_doubles(nm, C.has_mf != 0, 512) * 8, &chain_done,
-                                nullptr, 0, nullptr, N, nfw_blocks, nfw_done))
-        return 1;
-    if (one && !chain_done) {      // no rows to share a launch with (or a length the in-LDS transform does not take)
+                                  size_t nfw_blocks = 0, bool* nfw_done = nullptr) {
+    FftRiders R;
+    R.C = &C; R.nchain = one ? nz : 0; R.chain_lds = chain_lds_doubles(nm, C.has_mf != 0, 512) * 8;
+    R.N = N; R.nfw_blocks = nfw_blocks;
+    if (fft && profile_fft_impl(c, nz, nm, nk, *fft, R)) return 1;
+    if (nfw_done) *nfw_done = R.nfw_done;
+    if (one && !R.chain_done) {      // no rows to share a launch with (or a length the in-LDS transform does not take)
         REQUIRE(!C.has_mf, "internal: the transform did not take the route the tensor group was set up for");
         const RowsArgs none{};
         if (launch_rows_group(c, nz, nm, C, nz, nullptr, none, nullptr, 0)) return 1;
@@ -1310,20 +1324,11 @@ int hmg_group_tensors(hmg_ctx* c, int nz, int nm, int nk, int nq, const hmg_mass
     ChainArgs C;
     int one = 0;
     if (chain_setup(nm, hod, prep ? &P : nullptr, &C, &one)) return 1;
-    // Will the transform share its launch with a chain?  (One row in LDS with the row scalars of the rows stage and a chain
-    // to ride with: the decision of profile_fft_impl for such a length.)  If not - long grids, the rocFFT route, no hint
-    // arrays, nothing for a chain to do - the two groups run one after the other, as the two calls would.
-    bool merge = c->use_tensor_group && c->use_fused_fft && fft->d_xs && ((uintptr_t)fft->d_xs % 16) == 0 && fft->d_rowsc &&
-                 fft->d_nconst && FUSED_NT == 512 && (one || mf);
-    if (merge) {
-        FusedPlan* FP = nullptr;
-        if (get_fused_plan(c, fft->nxs, &FP)) return 1;
-        // ... and with a compile-time plan: the run-time-plan row kernel needs 80 registers (6 wavefronts per SIMD), and
-        // NFW rows sharing that allocation lose more than the kernel boundary costs (MI355X, Config-3 grid, nxs = 3000
-        // forced onto the run-time plan: 0.560 against 0.530 ms per step)
-        merge = FP && !(FP->plan.M > c->fused_prefer_m && c->use_pruned_fft) && fused_ct_plan(c, FP->plan) != 0;
-    }
-    if (!merge) {
+    // Can the tensor group take the transform (fft_route)?  If not - long grids, the rocFFT route, no hint arrays, nothing
+    // for a chain to do - the two groups run one after the other, as the two calls would.
+    FftRoute r;
+    if (fft_route(c, *fft, one || mf, false, &r)) return 1;
+    if (!r.tensor) {
         if ((mf || nfw) && hmg_group_rows(c, nz, nm, nk, nq, mf, nullptr, nullptr, nfw)) return 1;
         return profile_group_launches(c, nz, nm, nk, fft, C, one, prep, P);
     }
@@ -1340,7 +1345,7 @@ int hmg_group_tensors(hmg_ctx* c, int nz, int nm, int nk, int nq, const hmg_mass
         nfw_blocks = (size_t)nz * nm * ((nk + ktile - 1) / ktile);
         N = NfwArgs{c->d_sici, nfw->d_nfw_series, ktile, nm, nk, nfw->d_cs, nfw->d_rs, nfw->d_zs, nfw->d_ks, nfw->d_uk};
     }
-    int nfw_done = 0;
+    bool nfw_done = false;
     if (profile_group_launches(c, nz, nm, nk, fft, C, one, prep, P, nfw ? &N : nullptr, nfw_blocks, &nfw_done)) return 1;
     REQUIRE(!nfw || nfw_done, "internal: the transform did not take the route the tensor group was set up for");
     return 0;
@@ -1453,49 +1458,12 @@ int hmg_profile_fft_table(hmg_ctx* c, int nz, int nm, int nk, int nxs, double st
     REQUIRE(step > 0.0, "step must be positive");
     const int rows = nz * nm;
     REQUIRE(rho_rows == 1 || rho_rows == rows, "rho must have 1 or nz*nm rows");
-    {   // the in-LDS routes of hmg_profile_fft with the table in the place of the family's integrand
-        hmg_profile_fft_part p{};
-        p.nxs = nxs; p.fft_step = step; p.d_xs = xs; p.d_kts = kts; p.d_cmax = cmax; p.d_rss = rss; p.d_zs = zs; p.d_ks = ks;
-        p.do_mass_norm = do_mass_norm; p.d_out = out;
-        p.amp_const = p.xc_const = p.alpha_const = p.expo_const = 1.0;
-        int taken = 0;
-        if (profile_fft_impl(c, nz, nm, nk, p, nullptr, 0, 0, nullptr, rho, rho_rows == 1, &taken)) return 1;
-        if (taken) return 0;
-    }
-    const int nh = nxs / 2;
-    const size_t per_row = (size_t)nxs * 8 + (size_t)(nh + 1) * 16;
-    size_t budget = c->fft_chunk_bytes ? c->fft_chunk_bytes : ((size_t)160 << 20);
-    int chunk = (int)(budget / per_row);
-    if (chunk < 1) chunk = 1;
-    if (chunk > rows) chunk = rows;
-    if (ensure_scratch(c, 0, (size_t)chunk * nxs * 8)) return 1;
-    if (ensure_scratch(c, 1, (size_t)chunk * (nh + 1) * 16)) return 1;
-    if (ensure_scratch(c, 2, (size_t)chunk * 8)) return 1;
-    double* fin = (double*)c->scratch[0];
-    double2* fout = (double2*)c->scratch[1];
-    double* mnorm = (double*)c->scratch[2];
-    const bool stage = (size_t)nh * sizeof(double) <= 64 * 1024;
-    const size_t lds = stage ? (size_t)nh * sizeof(double) : 0;
-    for (int r0 = 0; r0 < rows; r0 += chunk) {
-        const int nr = rows - r0 < chunk ? rows - r0 : chunk;
-        hipLaunchKernelGGL(table_integrand_kernel, dim3(nr), dim3(256), 0, c->stream, nxs, r0, xs, rho,
-                           (int)(rho_rows == 1), cmax, do_mass_norm, fin, mnorm);
-        HIP_TRY(hipGetLastError());
-        FftPlan* P = nullptr;
-        if (get_plan(c, nxs, nr, &P)) return 1;
-        void* ib[1] = {fin};
-        void* ob[1] = {fout};
-        FFT_TRY(rocfft_execution_info_set_stream(P->info, c->stream));
-        FFT_TRY(rocfft_execute(P->plan, ib, ob, P->info));
-        if (stage)
-            hipLaunchKernelGGL(interp_kernel<true>, dim3(nr), dim3(256), lds, c->stream, nm, nk, nh, r0, step,
-                               (const double2*)fout, kts, mnorm, rss, zs, ks, (const double*)nullptr, out,
-                               (int*)nullptr, (double*)nullptr);
-        else
-            hipLaunchKernelGGL(interp_kernel<false>, dim3(nr), dim3(256), 0, c->stream, nm, nk, nh, r0, step,
-                               (const double2*)fout, kts, mnorm, rss, zs, ks, (const double*)nullptr, out,
-                               (int*)nullptr, (double*)nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    // the routes of hmg_profile_fft with the table in the place of the family's integrand
+    hmg_profile_fft_part p{};
+    p.nxs = nxs; p.fft_step = step; p.d_xs = xs; p.d_kts = kts; p.d_cmax = cmax; p.d_rss = rss; p.d_zs = zs; p.d_ks = ks;
+    p.do_mass_norm = do_mass_norm; p.d_out = out;
+    p.amp_const = p.xc_const = p.alpha_const = p.expo_const = 1.0;
+    FftRiders R;
+    R.rho_tab = rho; R.rho_shared = rho_rows == 1;
+    return profile_fft_impl(c, nz, nm, nk, p, R);
 }
