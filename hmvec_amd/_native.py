@@ -12,7 +12,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HMG_LIB_PATH") or os.path.join(_HERE, "libhmgrid.so")   # override: tuning experiments only
-ABI_VERSION = 9
+ABI_VERSION = 10
 COMM_ID_BYTES = 128
 
 c_double_p = C.c_void_p  # device or host pointers travel as plain addresses
@@ -183,6 +183,9 @@ SIGNATURES = {
     "hmg_trapz_rows": [_P, _I, _I, _P, _P, _P],
     "hmg_sine_transform": [_P, _I, _I, _P, _P, _P],
     "hmg_profile_fft_table": [_P, _I, _I, _I, _I, _D, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P],
+    "hmg_lensing_sigma_nfw": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "hmg_lensing_sigma_nfw_off": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "hmg_lensing_kappa_2h": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P],
     "hmg_comm_unique_id": [C.c_char * COMM_ID_BYTES],
     "hmg_comm_init": [_P, C.c_char * COMM_ID_BYTES, _I, _I],
     "hmg_comm_allgather": [_P, _P, _P, _Z],
@@ -205,7 +208,8 @@ def kernel_source_sha16():
     import hashlib
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
-    names = ["hmgrid.hip", "longgrid.hip", "longgrid.hpp", "rowdev.hpp", "sici.hpp", "ldsfft.hpp", "fastmath.hpp", "Makefile"]
+    names = ["hmgrid.hip", "longgrid.hip", "longgrid.hpp", "rowdev.hpp", "sici.hpp", "ldsfft.hpp", "fastmath.hpp", "Makefile",
+             "lensing.hip", "j0.hpp"]
     names += sorted(os.path.join("kernels", n) for n in os.listdir(os.path.join(csrc, "kernels")) if n.endswith(".hpp"))
     for name in names:          # (runtime.hip / comm.hip / hmctx.hpp hold no device code: not part of the kernel identity)
         with open(os.path.join(csrc, name), "rb") as f:

@@ -1,0 +1,112 @@
+// Cluster-lensing profiles: the C-ABI entry points hmg_lensing_* (include/hmgrid.h) and their kernels
+// (kernels/lensing.hpp).  A translation unit of its own: the headline path's units (hmgrid.hip, longgrid.hip) do not
+// see these instantiations.  Definitions and accuracy: DESIGN.md section 10.
+#include <cmath>
+
+#include "hmctx.hpp"
+#include "kernels/lensing.hpp"
+
+using namespace hmg;
+
+namespace {
+
+// Gauss-Legendre nodes and weights on [0, 1] (Newton on P_n from the Chebyshev-like first guess)
+void gauss_legendre01(int n, double* x, double* w) {
+    for (int i = 0; i < n; ++i) {
+        double t = std::cos(M_PI * (i + 0.75) / (n + 0.5)), dp = 0.0;
+        for (int it = 0; it < 100; ++it) {
+            double p0 = 1.0, p1 = t;
+            for (int k = 2; k <= n; ++k) {
+                const double p2 = ((2.0 * k - 1.0) * t * p1 - (k - 1.0) * p0) / k;
+                p0 = p1;
+                p1 = p2;
+            }
+            dp = n * (t * p1 - p0) / (t * t - 1.0);
+            const double dt = p1 / dp;
+            t -= dt;
+            if (std::fabs(dt) < 1e-16) break;
+        }
+        // recompute P_n' at the converged node for the weight
+        double p0 = 1.0, p1 = t;
+        for (int k = 2; k <= n; ++k) {
+            const double p2 = ((2.0 * k - 1.0) * t * p1 - (k - 1.0) * p0) / k;
+            p0 = p1;
+            p1 = p2;
+        }
+        dp = n * (t * p1 - p0) / (t * t - 1.0);
+        x[n - 1 - i] = 0.5 * (t + 1.0);                      // ascending
+        w[n - 1 - i] = 1.0 / ((1.0 - t * t) * dp * dp);      // 2 / ((1-t^2) P'^2), halved for [0, 1]
+    }
+}
+
+LensQuad build_lens_quad() {
+    LensQuad q;
+    gauss_legendre01(LENS_QUAD_N / 2, q.w_outer, q.wt_outer);
+    double x[LENS_QUAD_N], w[LENS_QUAD_N];
+    gauss_legendre01(LENS_QUAD_N, x, w);
+    for (int j = 0; j < LENS_QUAD_N; ++j) {      // phi = pi u^3: (1/pi) dphi = 3 u^2 du
+        const double phi = M_PI * x[j] * x[j] * x[j];
+        const double s = std::sin(0.5 * phi);
+        q.s2_phi[j] = s * s;
+        q.wt_phi[j] = 3.0 * x[j] * x[j] * w[j];
+    }
+    return q;
+}
+
+constexpr int MAX_DEVICES = 64;
+bool quad_ready[MAX_DEVICES] = {};
+
+int lens_quad_upload(hmg_ctx* c) {
+    REQUIRE(c->device >= 0 && c->device < MAX_DEVICES, "device index out of range");
+    if (quad_ready[c->device]) return 0;
+    REQUIRE(!c->capturing, "the lensing quadrature table cannot be uploaded inside a captured step: run the call once "
+                           "eagerly first");
+    static const LensQuad q = build_lens_quad();
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(lens_quad), &q, sizeof(q), 0, hipMemcpyHostToDevice));
+    quad_ready[c->device] = true;
+    return 0;
+}
+
+constexpr int OFF_WAVES = 4;
+constexpr int K2H_THREADS = 256;
+
+}  // namespace
+
+int hmg_lensing_sigma_nfw(hmg_ctx* c, int n, int nr, int rbins_per_halo, const double* rs, const double* delta_c,
+                          const double* rho_crit, const double* rbins, double* out) {
+    REQUIRE(c && rs && delta_c && rho_crit && rbins && out, "NULL argument");
+    REQUIRE(n > 0 && nr > 0, "empty grid");
+    const size_t total = (size_t)n * nr;
+    REQUIRE((total + 255) / 256 <= 2147483647u, "grid too large");
+    hipLaunchKernelGGL(lensing_sigma_kernel, grid1d(total, 256), dim3(256), 0, c->stream, total, nr,
+                       rbins_per_halo ? nr : 0, rs, delta_c, rho_crit, rbins, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int hmg_lensing_sigma_nfw_off(hmg_ctx* c, int n, int nr, int rbins_per_halo, const double* rs, const double* delta_c,
+                              const double* rho_crit, const double* rbins, const double* offsets, double* out) {
+    REQUIRE(c && rs && delta_c && rho_crit && rbins && offsets && out, "NULL argument");
+    REQUIRE(n > 0 && nr > 0, "empty grid");
+    const size_t total = (size_t)n * nr;
+    REQUIRE((total + OFF_WAVES - 1) / OFF_WAVES <= 2147483647u, "grid too large");
+    if (lens_quad_upload(c)) return 1;
+    hipLaunchKernelGGL(lensing_sigma_off_kernel<OFF_WAVES>, grid1d(total, OFF_WAVES), dim3(64 * OFF_WAVES), 0,
+                       c->stream, total, nr, rbins_per_halo ? nr : 0, rs, delta_c, rho_crit, rbins, offsets, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int hmg_lensing_kappa_2h(hmg_ctx* c, int nz, int nk, int ntheta, int nm, int nM, const double* ks, const double* chi,
+                         const double* pre, const double* Pzk, const double* thetas, double lmin, double lmax,
+                         const double* ms, const double* bh, const double* Ms, double* out) {
+    REQUIRE(c && ks && chi && pre && Pzk && thetas && ms && bh && Ms && out, "NULL argument");
+    REQUIRE(nz > 0 && nk > 0 && ntheta > 0 && nM > 0, "empty grid");
+    REQUIRE(nm >= 2, "the bias interpolation needs at least two masses");
+    REQUIRE(nz <= 65535, "nz too large");
+    hipLaunchKernelGGL(lensing_kappa2h_kernel<K2H_THREADS>, dim3(ntheta, nz), dim3(K2H_THREADS), 0, c->stream, nk,
+                       ntheta, nm, nM, ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}

@@ -1186,6 +1186,99 @@ class HaloModel(Cosmology):
         print("Two-halo consistency1: ", c1, i1)
         print("Two-halo consistency2: ", c2, i2)
 
+    # ------------------------------------------------------------------ cluster lensing
+    # The per-halo scalars are formed on the host one lens redshift at a time (a few values per halo), so that a z slice
+    # of a model with several redshifts is the same computation as a model of that redshift alone.  With one redshift
+    # the results have the reference's shapes; with nz > 1 a leading z axis is added.
+    @staticmethod
+    def _lensing_thetas(thetas):
+        th = np.atleast_1d(np.asarray(thetas, dtype=np.float64)).ravel()
+        if not np.all(np.isfinite(th)) or np.any(th <= 0):
+            raise ValueError("thetas must be finite and positive")
+        return th
+
+    def _lensing_halos(self, Ms, concs, delta, rho, rho_at_z):
+        """(Ms, concs, [(D_A, r_s, delta_c, rho_crit) per z]) of sigma_1h_profiles (hmvec/hmvec.py:574-589)."""
+        Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()
+        concs = np.atleast_1d(np.asarray(concs, dtype=np.float64)).ravel()
+        if Ms.size != concs.size:
+            raise ValueError("Ms and concs must have the same length")
+        if not (np.all(np.isfinite(Ms)) and np.all(Ms > 0) and np.all(np.isfinite(concs)) and np.all(concs > 0)):
+            raise ValueError("masses and concentrations must be finite and positive")
+        if rho == "critical":
+            rhofunc = self.rho_critical_z
+        elif rho == "mean":
+            rhofunc = self.rho_matter_z
+        else:
+            raise ValueError(f"rho must be 'mean' or 'critical', got {rho!r}")
+        fcon = np.log(1.0 + concs) - (concs / (1.0 + concs))      # Fcon (hmvec/hmvec.py:737)
+        rows = []
+        for z in self.zs:
+            zz = np.array([z])
+            rhoz = zz if rho_at_z else zz * 0
+            rs = _R_from_M(Ms, rhofunc(rhoz), delta=delta) / concs
+            rhoc = self.rho_critical_z(zz)
+            delta_c = Ms / 4 / np.pi / rs ** 3 / rhoc / fcon
+            rows.append((float(self.angular_diameter_distance(zz)[0]), rs, delta_c, float(rhoc[0])))
+        return Ms, concs, rows
+
+    def sigma_1h_profiles(self, thetas, Ms, concs, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
+        """One-halo surface density Sigma [Msun/Mpc^2] of NFW halos (masses Ms, concentrations concs) at angles
+        thetas [rad] (hmvec/hmvec.py:574-590): (nM, ntheta), or (nz, nM, ntheta) with several lens redshifts.
+        sig_theta [rad] averages over Rayleigh-distributed miscentring of width D_A(z) sig_theta; 0 is the centred
+        profile."""
+        th = self._lensing_thetas(thetas)
+        Ms, _, rows = self._lensing_halos(Ms, concs, delta, rho, rho_at_z)
+        if sig_theta is not None and (not np.isfinite(sig_theta) or sig_theta < 0):
+            raise ValueError("sig_theta must be finite and non-negative")
+        nz, nM, nt = self._nz, Ms.size, th.size
+        rs = np.concatenate([r[1] for r in rows])
+        dc = np.concatenate([r[2] for r in rows])
+        rhoc = np.repeat([r[3] for r in rows], nM)
+        rbins = np.repeat(np.stack([r[0] * th for r in rows]), nM, axis=0)           # (nz nM, ntheta)
+        offsets = None
+        if sig_theta is not None and sig_theta > 0:
+            offsets = np.repeat([r[0] * float(sig_theta) for r in rows], nM)
+        from .lensing import sigma_nfw
+        sigma = sigma_nfw(rs, dc, rhoc, rbins, offsets=offsets, ctx=self._main()).reshape(nz, nM, nt)
+        return sigma[0] if nz == 1 else sigma
+
+    def kappa_1h_profiles(self, thetas, Ms, concs, zsource, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
+        """sigma_1h_profiles / Sigma_crit(z, zsource) (hmvec/hmvec.py:592-595)."""
+        sigma = self.sigma_1h_profiles(thetas, Ms, concs, sig_theta=sig_theta, delta=delta, rho=rho,
+                                       rho_at_z=rho_at_z)
+        sigmac = np.concatenate([np.atleast_1d(self.sigma_crit(np.array([z]), zsource)) for z in self.zs])
+        return sigma / sigmac[0] if self._nz == 1 else sigma / sigmac[:, None, None]
+
+    def kappa_2h_profiles(self, thetas, Ms, zsource, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
+                          verbose=True):
+        """Two-halo convergence (hmvec/hmvec.py:597-625) at angles thetas [rad] for halo masses Ms: (ntheta, nM), or
+        (nz, ntheta, nM) with several lens redshifts.  delta, rho and rho_at_z are accepted and unused, as in the
+        reference.  Ms outside the model's mass grid raise ValueError (the reference's interp1d does)."""
+        th = self._lensing_thetas(thetas)
+        Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()
+        if not np.all(np.isfinite(Ms)) or np.any(Ms <= 0):
+            raise ValueError("masses must be finite and positive")
+        if np.any(Ms < self.ms[0]) or np.any(Ms > self.ms[-1]):
+            raise ValueError("A value in x_new is outside the interpolation range of the model's mass grid")
+        chi, pre, sigmac = [], [], []
+        for z in self.zs:
+            zz = np.array([z])
+            sc = np.atleast_1d(self.sigma_crit(zz, zsource))
+            dA = self.angular_diameter_distance(zz)
+            pre.append((self.rho_matter_z(zz) / (1 + zz) ** 3.0 / sc / dA ** 2)[0])
+            chi.append(np.atleast_1d(self.comoving_radial_distance(zz))[0])
+            sigmac.append(sc[0])
+        ctx = self._main(needs_aux=True)
+        from .lensing import kappa_2h_integral
+        out = kappa_2h_integral(self.ks, np.array(chi), np.array(pre), self._d_Pzk(), th, lmin, lmax,
+                                self.ms, self._d_bh, Ms, ctx=ctx)
+        if verbose:
+            bhs = np.stack([np.interp(Ms, self.ms, b) for b in self.bh])
+            print("bias ", bhs)
+            print("sigmacr ", np.array(sigmac))
+        return out[0] if self._nz == 1 else out
+
 
 class _HostBlock:
     """The spectra of one batched launch on the host: fetched in one copy on first use.  Every array handed out is the

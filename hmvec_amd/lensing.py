@@ -1,0 +1,112 @@
+"""Cluster-lensing profiles on the GPU: batched functions of plain arrays behind HaloModel.sigma_1h_profiles,
+kappa_1h_profiles and kappa_2h_profiles (hmvec/hmvec.py:574-625).  Definitions: DESIGN.md section 10.
+
+``sigma_nfw`` is the batched counterpart of clusterlensing's ``SurfaceMassDensity(rs, delta_c, rho_crit, rbins,
+offsets).sigma_nfw()`` - the product the reference's sigma_1h_profiles forms - as a plain float64 array in the units
+of its inputs (Msun/Mpc^2 from Mpc and Msun/Mpc^3).  The kernels are in hmvec_amd/csrc/kernels/lensing.hpp.
+"""
+import numpy as np
+
+from . import _native as nat
+
+__all__ = ["sigma_nfw", "kappa_2h_integral"]
+
+
+def _context(ctx):
+    return nat.default_context(0) if ctx is None else ctx
+
+
+def _dev(ctx, a):
+    """A DeviceArray as it is (resident model data), anything else uploaded."""
+    return a if isinstance(a, nat.DeviceArray) else ctx.upload(np.ascontiguousarray(a, dtype=np.float64))
+
+
+def _positive(name, a):
+    a = np.asarray(a, dtype=np.float64)
+    if not np.all(np.isfinite(a)) or np.any(a <= 0):
+        raise ValueError(f"{name} must be finite and positive")
+    return a
+
+
+def sigma_nfw(rs, delta_c, rho_crit, rbins, offsets=None, *, ctx=None):
+    """Projected NFW surface density Sigma[i, j] of halo i at projected radius rbins[i, j] (or rbins[j]).
+
+    rs, delta_c, rho_crit: length-N per-halo arrays (scale radius, characteristic overdensity, critical density).
+    rbins: (N, nR) or (nR,).  offsets: None, or a length-N array of Rayleigh miscentring widths; halos with offset 0
+    take the centred profile (bit for bit the values of offsets=None).  Returns an (N, nR) float64 array."""
+    rs = _positive("rs", np.atleast_1d(rs)).ravel()
+    n = rs.size
+    delta_c = _positive("delta_c", np.atleast_1d(delta_c)).ravel()
+    rho_crit = _positive("rho_crit", np.atleast_1d(rho_crit)).ravel()
+    if delta_c.size != n or rho_crit.size != n:
+        raise ValueError("rs, delta_c and rho_crit must have the same length")
+    rbins = _positive("rbins", rbins)
+    if rbins.ndim == 1:
+        per_halo = 0
+    elif rbins.ndim == 2 and rbins.shape[0] == n:
+        per_halo = 1
+    else:
+        raise ValueError(f"rbins must be (nR,) or ({n}, nR), got {rbins.shape}")
+    nr = rbins.shape[-1]
+    if n == 0 or nr == 0:
+        return np.empty((n, nr))
+    off = None
+    if offsets is not None:
+        off = np.asarray(offsets, dtype=np.float64).ravel()
+        if off.size == 1 and n > 1:
+            off = np.full(n, off[0])
+        if off.size != n or not np.all(np.isfinite(off)) or np.any(off < 0):
+            raise ValueError("offsets must be a non-negative array with one entry per halo")
+        if not np.any(off > 0):
+            off = None
+    ctx = _context(ctx)
+    d_rs, d_dc, d_rho, d_r = (_dev(ctx, a) for a in (rs, delta_c, rho_crit, rbins))
+    out = ctx.empty((n, nr))
+    if off is None or not np.all(off > 0):
+        ctx.call("hmg_lensing_sigma_nfw", n, nr, per_halo, d_rs.ptr, d_dc.ptr, d_rho.ptr, d_r.ptr, out.ptr)
+    if off is None:
+        return out.numpy()
+    centred = out.numpy() if not np.all(off > 0) else None
+    # halos without an offset: the quadrature needs a positive width, so give them one and take the centred values
+    d_off = _dev(ctx, np.where(off > 0, off, 1.0))
+    ctx.call("hmg_lensing_sigma_nfw_off", n, nr, per_halo, d_rs.ptr, d_dc.ptr, d_rho.ptr, d_r.ptr, d_off.ptr, out.ptr)
+    res = out.numpy()
+    if centred is not None:
+        res = np.where((off > 0)[:, None], res, centred)
+    return res
+
+
+def kappa_2h_integral(ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, *, ctx=None):
+    """Two-halo convergence out[z, t, m] = b(z, Ms[m]) pre[z] trapz_l[P(z,k) J0(l thetas[t]) l / 2 pi] over the
+    l = ks chi[z] with lmin < l < lmax (hmvec/hmvec.py:598-625, per lens redshift).
+
+    ks (nk,) increasing, chi and pre (nz,), Pzk (nz, nk), thetas (nt,) in radians, ms (nm,) increasing, bh (nz, nm),
+    Ms (nM,) inside [ms[0], ms[-1]].  Pzk and bh may be DeviceArrays (a model's resident arrays).  Returns an
+    (nz, nt, nM) float64 array."""
+    ks = np.asarray(ks, dtype=np.float64).ravel()
+    chi = np.asarray(chi, dtype=np.float64).ravel()
+    pre = np.asarray(pre, dtype=np.float64).ravel()
+    thetas = _positive("thetas", np.atleast_1d(thetas)).ravel()
+    Ms = _positive("Ms", np.atleast_1d(Ms)).ravel()
+    nz, nk, nt, nM = chi.size, ks.size, thetas.size, Ms.size
+    if pre.size != nz or nz == 0 or nk == 0:
+        raise ValueError("chi and pre need one entry per lens redshift, ks at least one wavenumber")
+    if nk > 1 and not np.all(np.diff(ks) > 0):
+        raise ValueError("ks must be strictly increasing")
+    ms = np.asarray(ms, dtype=np.float64).ravel()
+    nm = ms.size
+    if nm < 2 or not np.all(np.diff(ms) > 0):
+        raise ValueError("ms must be strictly increasing with at least two masses")
+    if np.any(Ms < ms[0]) or np.any(Ms > ms[-1]):
+        raise ValueError("A value in x_new is outside the interpolation range of the mass grid")
+    for name, a, shape in (("Pzk", Pzk, (nz, nk)), ("bh", bh, (nz, nm))):
+        if tuple(np.shape(a) if not isinstance(a, nat.DeviceArray) else a.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}")
+    if nt == 0 or nM == 0:
+        return np.empty((nz, nt, nM))
+    ctx = _context(ctx)
+    d = [_dev(ctx, a) for a in (ks, chi, pre, Pzk, thetas, ms, bh, Ms)]
+    out = ctx.empty((nz, nt, nM))
+    ctx.call("hmg_lensing_kappa_2h", nz, nk, nt, nm, nM, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr,
+             float(lmin), float(lmax), d[5].ptr, d[6].ptr, d[7].ptr, out.ptr)
+    return out.numpy()

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HMG_ABI_VERSION 9
+#define HMG_ABI_VERSION 10
 
 typedef struct hmg_ctx hmg_ctx;
 
@@ -543,6 +543,28 @@ int hmg_profile_fft_table(hmg_ctx* ctx, int nz, int nm, int nk, int nxs, double 
                           const double* d_xs, const double* d_kts, const double* d_rho, int rho_rows,
                           const double* d_cmax, const double* d_rss, const double* d_zs,
                           const double* d_ks, int do_mass_norm, double* d_out);
+
+/* ---- cluster-lensing profiles (hmvec/hmvec.py:574-625) ----------------------------------
+ * Per-halo inputs have n entries: scale radius r_s [Mpc], delta_c and rho_crit(z) [Msun/Mpc^3].  d_rbins holds the
+ * projected radii [Mpc]: (n, nr) when rbins_per_halo != 0, else one row of nr shared by every halo.  d_out is (n, nr),
+ * Sigma in Msun/Mpc^2.  Radii, r_s and offsets must be positive; the Python layer checks values, these check shapes.
+ * hmg_lensing_sigma_nfw: the centred NFW profile (Wright & Brainerd 2000, eq. 11, with a series around x = 1).
+ * hmg_lensing_sigma_nfw_off: the same averaged over Rayleigh-distributed centre offsets of width d_offsets[h] [Mpc]
+ *   (2-D quadrature, one wavefront per output, bit-identical on repeat).  The first call on a device uploads its node
+ *   table and so cannot be inside a captured step.                                                               */
+int hmg_lensing_sigma_nfw(hmg_ctx* ctx, int n, int nr, int rbins_per_halo, const double* d_rs, const double* d_delta_c,
+                          const double* d_rho_crit, const double* d_rbins, double* d_out);
+int hmg_lensing_sigma_nfw_off(hmg_ctx* ctx, int n, int nr, int rbins_per_halo, const double* d_rs,
+                              const double* d_delta_c, const double* d_rho_crit, const double* d_rbins,
+                              const double* d_offsets, double* d_out);
+/* Two-halo convergence, d_out (nz, ntheta, nM):
+ *   b(z, M) pre(z) trapz_l[ P(z,k) J0(l theta) l / 2 pi ],  l = k chi(z) with lmin < l < lmax (strict, grid order),
+ * pre(z) = rho_m(z) / (1+z)^3 / Sigma_crit(z) / D_A(z)^2 (nz), d_ks (nk) increasing, d_Pzk (nz, nk), d_thetas [rad]
+ * (ntheta), b(z, M) the linear interpolation of d_bh (nz, nm) on d_ms (nm >= 2, increasing) at d_Ms (nM).       */
+int hmg_lensing_kappa_2h(hmg_ctx* ctx, int nz, int nk, int ntheta, int nm, int nM, const double* d_ks,
+                         const double* d_chi, const double* d_pre, const double* d_Pzk, const double* d_thetas,
+                         double lmin, double lmax, const double* d_ms, const double* d_bh, const double* d_Ms,
+                         double* d_out);
 
 /* ---- z-slab gather over RCCL/xGMI -------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0

@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads hmvec_amd/csrc/hmgrid.resources.txt and hmgrid.s (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip and lensing.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -29,14 +29,18 @@ KERNELS = [   # (label, regex on the mangled name)
     ("profile_table_kernel<512,2,4,0>  (user callable, run-time plan)", r"profile_table_kernelILi512ELi2ELi4ELi0E"),
     ("stand-alone: profile_fused_kernel<512,2,3,2500>", r"profile_fused_kernelILi512ELi2ELi3ELi2500E"),
     ("stand-alone: nfw_kernel", r"10nfw_kernelE"),
+    ("lensing_sigma_kernel  (centred Sigma, lensing.hip)", r"20lensing_sigma_kernelE"),
+    ("lensing_sigma_off_kernel<4>  (miscentred Sigma, lensing.hip)", r"24lensing_sigma_off_kernelILi4EE"),
+    ("lensing_kappa2h_kernel<256>  (two-halo convergence, lensing.hip)", r"22lensing_kappa2h_kernelILi256EE"),
 ]
 
 
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    res = open(os.path.join(CSRC, "hmgrid.resources.txt")).read() + open(os.path.join(CSRC, "longgrid.resources.txt")).read()
-    asm = open(os.path.join(CSRC, "hmgrid.s")).read() + open(os.path.join(CSRC, "longgrid.s")).read()
+    units = ("hmgrid", "longgrid", "lensing")
+    res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
+    asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
     print(f"# kernel sources {kernel_source_sha16()}  (hipcc -O3 --offload-arch=gfx950 -mllvm -disable-machine-licm; make asm)")
     print("# columns: SGPRs VGPRs | reserved scratch B/lane | occupancy waves/SIMD | SGPR spills, VGPR spills (compiler summary) |")
