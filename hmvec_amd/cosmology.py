@@ -578,6 +578,23 @@ class Cosmology(object):
         poisson = 2.0 * ks ** 2.0 * self.Tk(ks, type="eisenhu_osc") / (3.0 * self.omm0 * self.h_of_z(0) ** 2.0)
         return bg + fnl * (2.0 * deltac * (bg - 1.0)) / (poisson * growth)
 
+    # ------------------------------------------------------------------ kSZ inputs
+    def get_growth_rate_f(self, zs):
+        """Linear growth rate f(z) = d ln D / d ln a, shape (nz,) (hmvec/cosmology.py:345-350, which only has it
+        from CLASS).  From the provider's ``growth_rate_f`` when it has one, else the closed form of the package's
+        Heath D(a) (``D_growth_approx``): see ``heath_growth_rate_f``."""
+        zs = np.atleast_1d(np.asarray(zs, dtype=np.float64))
+        if hasattr(self._background, "growth_rate_f"):
+            return np.asarray(self._background.growth_rate_f(zs), dtype=np.float64).reshape(zs.shape)
+        return heath_growth_rate_f(self, zs)
+
+    def redshift_at_comoving_radial_distance(self, chi):
+        """z(chi) (hmvec/cosmology.py:713-727): the provider's method when it has one (CAMB does), else the
+        inversion of the provider's chi(z) by ``z_of_chi``.  A single value comes back as a float."""
+        if hasattr(self._background, "redshift_at_comoving_radial_distance"):
+            return self._background.redshift_at_comoving_radial_distance(np.asarray(chi))
+        return z_of_chi(self._background, chi)
+
     def P_mm_linear(self, zs, ks):
         """Placeholder in the reference too (hmvec/cosmology.py:104-105: ``pass``)."""
         return None
@@ -585,6 +602,46 @@ class Cosmology(object):
     def P_mm_nonlinear(self, ks, zs, halofit_version="mead"):
         """Placeholder in the reference too (hmvec/cosmology.py:107-108: ``pass``)."""
         return None
+
+
+def heath_growth_rate_f(cosmo, zs):
+    """f = Omega_m(a) (5 a / (2 D(a)) - 3/2) with D = cosmo.D_growth_approx (Heath 1977) and
+    Omega_m(a) = Omega_m a^-3 / E^2(a), E = H(z) / H0 from cosmo.hubble_parameter.  Exact for flat LCDM, where
+    D = (5/2) Omega_m E int_0^a da' / (a' E)^3 and so d ln D / d ln a = d ln E / d ln a + (5/2) Omega_m / (a^2 E^2 D).
+    ``cosmo`` needs ``params`` (H0, w0, wa, omk), ``omm0``, ``D_growth_approx`` and ``hubble_parameter``: any
+    Cosmology of this package or of the reference."""
+    p = cosmo.params
+    if p["w0"] != -1.0 or p["wa"] != 0.0 or p["omk"] != 0.0:
+        raise NotImplementedError("the growth rate from D_growth_approx is exact for flat LCDM only "
+                                  "(w0 = -1, wa = 0, omk = 0); use a provider with growth_rate_f")
+    zs = np.atleast_1d(np.asarray(zs, dtype=np.float64))
+    a = 1.0 / (1.0 + zs)
+    E = np.asarray(cosmo.hubble_parameter(zs), dtype=np.float64) / p["H0"]
+    om_a = cosmo.omm0 * (1.0 + zs) ** 3 / E ** 2
+    return om_a * (2.5 * a / cosmo.D_growth_approx(a) - 1.5)
+
+
+def z_of_chi(background, chi, max_iter=100):
+    """Redshift at comoving radial distance chi [Mpc] by Newton on chi(z) - chi = 0, dchi/dz = 1 / h_of_z(z),
+    vectorised over chi.  Started at z = 0, the iterates of a concave increasing chi(z) (H(z) increasing) rise
+    monotonically to the root, so no bracket is needed; it stops when |chi(z) - chi| <= 1e-14 chi everywhere or a
+    step no longer moves z.  A single value comes back as a float, as the reference does."""
+    c = np.atleast_1d(np.asarray(chi, dtype=np.float64))
+    if not np.all(np.isfinite(c)) or np.any(c < 0):
+        raise ValueError("chi must be finite and non-negative")
+    flat = c.ravel()
+    z = np.zeros_like(flat)
+    for _ in range(max_iter):
+        g = np.asarray(background.comoving_radial_distance(z), dtype=np.float64) - flat
+        if np.all(np.abs(g) <= 1e-14 * flat):
+            break
+        step = g * np.asarray(background.h_of_z(z), dtype=np.float64)
+        znew = z - step
+        if np.array_equal(znew, z):
+            break
+        z = znew
+    z = z.reshape(c.shape)
+    return float(z.ravel()[0]) if z.size == 1 else z
 
 
 _UPLOAD_CACHE_MAX = 64

@@ -566,6 +566,32 @@ int hmg_lensing_kappa_2h(hmg_ctx* ctx, int nz, int nk, int ntheta, int nm, int n
                          double lmin, double lmax, const double* d_ms, const double* d_bh, const double* d_Ms,
                          double* d_out);
 
+/* ---- kSZ forecasts (hmvec/ksz.py) ---------------------------------------------------------
+ * hmg_ksz_pqperp: the Ma-Fry P_q_perp table d_out (nk, nz) for nz redshifts,
+ *   out[k, z] = adotf[z]^2 (2 pi)^-2 trapz_mu trapz_k' nan_to_num(k'^2 k (k - 2k'mu)(1 - mu^2)
+ *                                               / (k'^2 (k'^2 + k^2 - 2 k k' mu)) Pmm[z, k'] Pee[z, |k - k'|]),
+ *   d_ks (nk) ascending (any spacing), d_mus (nmu <= 4096), d_Pee / d_Pmm (nz, nk) paired with d_ks, Pee linear in k
+ *   with 0 outside [ks[0], ks[nk-1]], d_adotf (nz).                                                              */
+int hmg_ksz_pqperp(hmg_ctx* ctx, int nz, int nk, int nmu, const double* d_ks, const double* d_mus,
+                   const double* d_Pee, const double* d_Pmm, const double* d_adotf, double* d_out);
+/* hmg_ksz_nvv: the kSZ reconstruction noise d_out (nz, nmu, nkL),
+ *   Nvv = mu^-2 2 pi chi[z]^2 / F[z]^2 / trapz_kS _sanitize(kS (W Pge)^2 / ((W^2 Pgg + ngg[z]) C(chi[z] kS))),
+ *   C(l) = d_cls[int(l)] for l <= ncl - 1 (0 below l = 2), inf above.  d_sig / d_H (nz) non-NULL: photo-z,
+ *   W = exp(-sig^2 (mu kL)^2 / 2 / H^2), else W = 1.  d_Pge / d_Pgg / d_Pph are (nz, nkS) when rows == 0, or
+ *   (nz, nmu, nkL, nkS) when rows == 1 (no photo-z then); d_Pph non-NULL: the robust term (integrand times
+ *   Pph / (W^2 Pgg + ngg), sanitized).  *d_bad (one int on the device) is set to 1 when any output is non-finite. */
+int hmg_ksz_nvv(hmg_ctx* ctx, int nz, int nmu, int nkL, int nkS, int ncl, int rows, const double* d_mus,
+                const double* d_kLs, const double* d_kSs, const double* d_cls, const double* d_chi, const double* d_F,
+                const double* d_sig, const double* d_H, const double* d_ngg, const double* d_Pge,
+                const double* d_Pgg, const double* d_Pph, double* d_out, int* d_bad);
+/* hmg_ksz_limber_cl: C_ell^kSZ d_out (nell) = trapz over the nchi nodes d_chi[l, :] (redshifts d_zn[l, :]) of
+ *   P(z, ell / chi) / (chi^2 / (1+z)^4) * 0.5 * c2 * T2    (squeezed == 0, Ma-Fry)
+ *   P(z, ell / chi) / chi^2 * (1+z)^4 * c2 * T2            (squeezed == 1)
+ * with P bilinear and edge-clamped on the table d_P (nk, nz) over d_zs (nz >= 2) and d_ks (nk >= 2), ascending. */
+int hmg_ksz_limber_cl(hmg_ctx* ctx, int nell, int nchi, int nz, int nk, const double* d_ells, const double* d_chi,
+                      const double* d_zn, const double* d_zs, const double* d_ks, const double* d_P, int squeezed,
+                      double c2, double T2, double* d_out);
+
 /* ---- z-slab gather over RCCL/xGMI -------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */

@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip and lensing.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip and ksz.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -32,13 +32,18 @@ KERNELS = [   # (label, regex on the mangled name)
     ("lensing_sigma_kernel  (centred Sigma, lensing.hip)", r"20lensing_sigma_kernelE"),
     ("lensing_sigma_off_kernel<4>  (miscentred Sigma, lensing.hip)", r"24lensing_sigma_off_kernelILi4EE"),
     ("lensing_kappa2h_kernel<256>  (two-halo convergence, lensing.hip)", r"22lensing_kappa2h_kernelILi256EE"),
+    ("ksz_pqperp_kernel<true>  (P_q_perp, tables in LDS, ksz.hip)", r"17ksz_pqperp_kernelILb1EE"),
+    ("ksz_pqperp_kernel<false>  (P_q_perp, tables from memory, ksz.hip)", r"17ksz_pqperp_kernelILb0EE"),
+    ("ksz_nvv_shared_kernel  (N_vv, one k_S integral per z, ksz.hip)", r"21ksz_nvv_shared_kernelE"),
+    ("ksz_nvv_rows_kernel  (N_vv, photo-z / per-row, ksz.hip)", r"19ksz_nvv_rows_kernelE"),
+    ("ksz_limber_cl_kernel  (kSZ C_ell, ksz.hip)", r"20ksz_limber_cl_kernelE"),
 ]
 
 
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing")
+    units = ("hmgrid", "longgrid", "lensing", "ksz")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
