@@ -186,6 +186,9 @@ SIGNATURES = {
     "hmg_lensing_sigma_nfw": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
     "hmg_lensing_sigma_nfw_off": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "hmg_lensing_kappa_2h": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P],
+    "hmg_lensing_delta_sigma_nfw": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "hmg_lensing_delta_sigma_nfw_off": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "hmg_lensing_gamma_t_2h": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P],
     "hmg_ksz_pqperp": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "hmg_ksz_nvv": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "hmg_ksz_limber_cl": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _D, _D, _P],
@@ -212,7 +215,7 @@ def kernel_source_sha16():
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
     names = ["hmgrid.hip", "longgrid.hip", "longgrid.hpp", "rowdev.hpp", "sici.hpp", "ldsfft.hpp", "fastmath.hpp", "Makefile",
-             "lensing.hip", "j0.hpp", "ksz.hip"]
+             "lensing.hip", "j0.hpp", "j1.hpp", "ksz.hip"]
     names += sorted(os.path.join("kernels", n) for n in os.listdir(os.path.join(csrc, "kernels")) if n.endswith(".hpp"))
     for name in names:          # (runtime.hip / comm.hip / hmctx.hpp hold no device code: not part of the kernel identity)
         with open(os.path.join(csrc, name), "rb") as f:

@@ -1,6 +1,7 @@
 // Cluster-lensing profiles: the C-ABI entry points hmg_lensing_* (include/hmgrid.h) and their kernels
 // (kernels/lensing.hpp).  A translation unit of its own: the headline path's units (hmgrid.hip, longgrid.hip) do not
-// see these instantiations.  Definitions and accuracy: DESIGN.md section 10.
+// see these instantiations.  Definitions and accuracy: DESIGN.md sections 10 (Sigma, kappa) and 12 (Delta Sigma,
+// gamma_t).
 #include <cmath>
 
 #include "hmctx.hpp"
@@ -53,8 +54,23 @@ LensQuad build_lens_quad() {
     return q;
 }
 
+LensDiscQuad build_lens_disc_quad() {
+    LensDiscQuad q;
+    double x[LENS_QUAD_N], w[LENS_QUAD_N];
+    gauss_legendre01(LENS_QUAD_N, x, w);
+    for (int j = 0; j < LENS_QUAD_N; ++j) {      // psi = pi u^2: dpsi = 2 pi u du
+        const double psi = M_PI * x[j] * x[j];
+        const double s = std::sin(0.5 * psi), c = std::cos(0.5 * psi);
+        q.sp[j] = s * s;
+        q.cp[j] = c * c;
+        q.wt[j] = 2.0 * M_PI * x[j] * w[j] * std::sin(psi);
+    }
+    return q;
+}
+
 constexpr int MAX_DEVICES = 64;
 bool quad_ready[MAX_DEVICES] = {};
+bool disc_quad_ready[MAX_DEVICES] = {};
 
 int lens_quad_upload(hmg_ctx* c) {
     REQUIRE(c->device >= 0 && c->device < MAX_DEVICES, "device index out of range");
@@ -65,6 +81,19 @@ int lens_quad_upload(hmg_ctx* c) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(lens_quad), &q, sizeof(q), 0, hipMemcpyHostToDevice));
     quad_ready[c->device] = true;
+    return 0;
+}
+
+// the miscentred Delta Sigma kernel reads both tables
+int lens_disc_quad_upload(hmg_ctx* c) {
+    if (lens_quad_upload(c)) return 1;
+    if (disc_quad_ready[c->device]) return 0;
+    REQUIRE(!c->capturing, "the lensing quadrature table cannot be uploaded inside a captured step: run the call once "
+                           "eagerly first");
+    static const LensDiscQuad q = build_lens_disc_quad();
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(lens_disc_quad), &q, sizeof(q), 0, hipMemcpyHostToDevice));
+    disc_quad_ready[c->device] = true;
     return 0;
 }
 
@@ -106,6 +135,45 @@ int hmg_lensing_kappa_2h(hmg_ctx* c, int nz, int nk, int ntheta, int nm, int nM,
     REQUIRE(nm >= 2, "the bias interpolation needs at least two masses");
     REQUIRE(nz <= 65535, "nz too large");
     hipLaunchKernelGGL(lensing_kappa2h_kernel<K2H_THREADS>, dim3(ntheta, nz), dim3(K2H_THREADS), 0, c->stream, nk,
+                       ntheta, nm, nM, ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int hmg_lensing_delta_sigma_nfw(hmg_ctx* c, int n, int nr, int rbins_per_halo, const double* rs, const double* delta_c,
+                                const double* rho_crit, const double* rbins, double* out) {
+    REQUIRE(c && rs && delta_c && rho_crit && rbins && out, "NULL argument");
+    REQUIRE(n > 0 && nr > 0, "empty grid");
+    const size_t total = (size_t)n * nr;
+    REQUIRE((total + 255) / 256 <= 2147483647u, "grid too large");
+    hipLaunchKernelGGL(lensing_delta_sigma_kernel, grid1d(total, 256), dim3(256), 0, c->stream, total, nr,
+                       rbins_per_halo ? nr : 0, rs, delta_c, rho_crit, rbins, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int hmg_lensing_delta_sigma_nfw_off(hmg_ctx* c, int n, int nr, int rbins_per_halo, const double* rs,
+                                    const double* delta_c, const double* rho_crit, const double* rbins,
+                                    const double* offsets, double* out) {
+    REQUIRE(c && rs && delta_c && rho_crit && rbins && offsets && out, "NULL argument");
+    REQUIRE(n > 0 && nr > 0, "empty grid");
+    const size_t total = (size_t)n * nr;
+    REQUIRE((total + OFF_WAVES - 1) / OFF_WAVES <= 2147483647u, "grid too large");
+    if (lens_disc_quad_upload(c)) return 1;
+    hipLaunchKernelGGL(lensing_delta_sigma_off_kernel<OFF_WAVES>, grid1d(total, OFF_WAVES), dim3(64 * OFF_WAVES), 0,
+                       c->stream, total, nr, rbins_per_halo ? nr : 0, rs, delta_c, rho_crit, rbins, offsets, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int hmg_lensing_gamma_t_2h(hmg_ctx* c, int nz, int nk, int ntheta, int nm, int nM, const double* ks, const double* chi,
+                           const double* pre, const double* Pzk, const double* thetas, double lmin, double lmax,
+                           const double* ms, const double* bh, const double* Ms, double* out) {
+    REQUIRE(c && ks && chi && pre && Pzk && thetas && ms && bh && Ms && out, "NULL argument");
+    REQUIRE(nz > 0 && nk > 0 && ntheta > 0 && nM > 0, "empty grid");
+    REQUIRE(nm >= 2, "the bias interpolation needs at least two masses");
+    REQUIRE(nz <= 65535, "nz too large");
+    hipLaunchKernelGGL(lensing_gamma2h_kernel<K2H_THREADS>, dim3(ntheta, nz), dim3(K2H_THREADS), 0, c->stream, nk,
                        ntheta, nm, nM, ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, out);
     HIP_TRY(hipGetLastError());
     return 0;

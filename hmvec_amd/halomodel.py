@@ -1227,6 +1227,23 @@ class HaloModel(Cosmology):
         thetas [rad] (hmvec/hmvec.py:574-590): (nM, ntheta), or (nz, nM, ntheta) with several lens redshifts.
         sig_theta [rad] averages over Rayleigh-distributed miscentring of width D_A(z) sig_theta; 0 is the centred
         profile."""
+        from .lensing import sigma_nfw
+        return self._lensing_1h(sigma_nfw, thetas, Ms, concs, sig_theta, delta, rho, rho_at_z)
+
+    def delta_sigma_1h_profiles(self, thetas, Ms, concs, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
+        """One-halo excess surface density Delta Sigma = Sigmabar(<R) - Sigma(R) [Msun/Mpc^2],
+        with the arguments, conventions and shapes of sigma_1h_profiles: (nM, ntheta), or (nz, nM, ntheta)."""
+        from .lensing import delta_sigma_nfw
+        return self._lensing_1h(delta_sigma_nfw, thetas, Ms, concs, sig_theta, delta, rho, rho_at_z)
+
+    def gamma_t_1h_profiles(self, thetas, Ms, concs, zsource, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
+        """One-halo tangential shear: delta_sigma_1h_profiles / Sigma_crit(z, zsource)."""
+        dsigma = self.delta_sigma_1h_profiles(thetas, Ms, concs, sig_theta=sig_theta, delta=delta, rho=rho,
+                                              rho_at_z=rho_at_z)
+        return self._over_sigma_crit(dsigma, zsource)
+
+    def _lensing_1h(self, profile, thetas, Ms, concs, sig_theta, delta, rho, rho_at_z):
+        """sigma_1h_profiles / delta_sigma_1h_profiles: `profile` is lensing.sigma_nfw or lensing.delta_sigma_nfw."""
         th = self._lensing_thetas(thetas)
         Ms, _, rows = self._lensing_halos(Ms, concs, delta, rho, rho_at_z)
         if sig_theta is not None and (not np.isfinite(sig_theta) or sig_theta < 0):
@@ -1239,22 +1256,52 @@ class HaloModel(Cosmology):
         offsets = None
         if sig_theta is not None and sig_theta > 0:
             offsets = np.repeat([r[0] * float(sig_theta) for r in rows], nM)
-        from .lensing import sigma_nfw
-        sigma = sigma_nfw(rs, dc, rhoc, rbins, offsets=offsets, ctx=self._main()).reshape(nz, nM, nt)
-        return sigma[0] if nz == 1 else sigma
+        prof = profile(rs, dc, rhoc, rbins, offsets=offsets, ctx=self._main()).reshape(nz, nM, nt)
+        return prof[0] if nz == 1 else prof
 
     def kappa_1h_profiles(self, thetas, Ms, concs, zsource, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
         """sigma_1h_profiles / Sigma_crit(z, zsource) (hmvec/hmvec.py:592-595)."""
         sigma = self.sigma_1h_profiles(thetas, Ms, concs, sig_theta=sig_theta, delta=delta, rho=rho,
                                        rho_at_z=rho_at_z)
+        return self._over_sigma_crit(sigma, zsource)
+
+    def _over_sigma_crit(self, prof, zsource):
+        """A one-halo profile ((nM, ntheta), or (nz, nM, ntheta)) over Sigma_crit(z, zsource) of its lens redshift."""
         sigmac = np.concatenate([np.atleast_1d(self.sigma_crit(np.array([z]), zsource)) for z in self.zs])
-        return sigma / sigmac[0] if self._nz == 1 else sigma / sigmac[:, None, None]
+        return prof / sigmac[0] if self._nz == 1 else prof / sigmac[:, None, None]
 
     def kappa_2h_profiles(self, thetas, Ms, zsource, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
                           verbose=True):
         """Two-halo convergence (hmvec/hmvec.py:597-625) at angles thetas [rad] for halo masses Ms: (ntheta, nM), or
         (nz, ntheta, nM) with several lens redshifts.  delta, rho and rho_at_z are accepted and unused, as in the
         reference.  Ms outside the model's mass grid raise ValueError (the reference's interp1d does)."""
+        from .lensing import kappa_2h_integral
+        return self._lensing_2h(kappa_2h_integral, thetas, Ms, zsource, lmin, lmax, verbose)
+
+    def gamma_t_2h_profiles(self, thetas, Ms, zsource, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
+                            verbose=True):
+        """Two-halo tangential shear: kappa_2h_profiles with J0(l theta) replaced by J2(l theta)
+        (Oguri & Takada 2011), same arguments, conventions and shapes: (ntheta, nM), or (nz, ntheta, nM)."""
+        from .lensing import gamma_t_2h_integral
+        return self._lensing_2h(gamma_t_2h_integral, thetas, Ms, zsource, lmin, lmax, verbose)
+
+    def delta_sigma_2h_profiles(self, thetas, Ms, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
+                                verbose=True):
+        """Two-halo excess surface density Sigma_crit(z, zsource) gamma_t^2h [Msun/Mpc^2]: gamma_t_2h_profiles without
+        its 1/Sigma_crit, so no source redshift.  Shapes and keywords as kappa_2h_profiles; verbose prints the bias."""
+        from .lensing import gamma_t_2h_integral
+        return self._lensing_2h(gamma_t_2h_integral, thetas, Ms, None, lmin, lmax, verbose)
+
+    def sigma_2h_profiles(self, thetas, Ms, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
+                          verbose=True):
+        """Two-halo surface density Sigma_crit(z, zsource) kappa_2h [Msun/Mpc^2]: kappa_2h_profiles without its
+        1/Sigma_crit, so no source redshift.  Shapes and keywords as kappa_2h_profiles; verbose prints the bias."""
+        from .lensing import kappa_2h_integral
+        return self._lensing_2h(kappa_2h_integral, thetas, Ms, None, lmin, lmax, verbose)
+
+    def _lensing_2h(self, integral, thetas, Ms, zsource, lmin, lmax, verbose):
+        """The two-halo profiles: `integral` is lensing.kappa_2h_integral (J0) or gamma_t_2h_integral (J2); pre(z)
+        carries 1/Sigma_crit(z, zsource) unless zsource is None."""
         th = self._lensing_thetas(thetas)
         Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()
         if not np.all(np.isfinite(Ms)) or np.any(Ms <= 0):
@@ -1264,19 +1311,22 @@ class HaloModel(Cosmology):
         chi, pre, sigmac = [], [], []
         for z in self.zs:
             zz = np.array([z])
-            sc = np.atleast_1d(self.sigma_crit(zz, zsource))
             dA = self.angular_diameter_distance(zz)
-            pre.append((self.rho_matter_z(zz) / (1 + zz) ** 3.0 / sc / dA ** 2)[0])
+            if zsource is None:
+                pre.append((self.rho_matter_z(zz) / (1 + zz) ** 3.0 / dA ** 2)[0])
+            else:
+                sc = np.atleast_1d(self.sigma_crit(zz, zsource))
+                pre.append((self.rho_matter_z(zz) / (1 + zz) ** 3.0 / sc / dA ** 2)[0])
+                sigmac.append(sc[0])
             chi.append(np.atleast_1d(self.comoving_radial_distance(zz))[0])
-            sigmac.append(sc[0])
         ctx = self._main(needs_aux=True)
-        from .lensing import kappa_2h_integral
-        out = kappa_2h_integral(self.ks, np.array(chi), np.array(pre), self._d_Pzk(), th, lmin, lmax,
-                                self.ms, self._d_bh, Ms, ctx=ctx)
+        out = integral(self.ks, np.array(chi), np.array(pre), self._d_Pzk(), th, lmin, lmax, self.ms, self._d_bh, Ms,
+                       ctx=ctx)
         if verbose:
             bhs = np.stack([np.interp(Ms, self.ms, b) for b in self.bh])
             print("bias ", bhs)
-            print("sigmacr ", np.array(sigmac))
+            if zsource is not None:
+                print("sigmacr ", np.array(sigmac))
         return out[0] if self._nz == 1 else out
 
 

@@ -1,15 +1,17 @@
 """Cluster-lensing profiles on the GPU: batched functions of plain arrays behind HaloModel.sigma_1h_profiles,
-kappa_1h_profiles and kappa_2h_profiles (hmvec/hmvec.py:574-625).  Definitions: DESIGN.md section 10.
+kappa_1h_profiles and kappa_2h_profiles (hmvec/hmvec.py:574-625) and behind their excess
+surface density and tangential shear counterparts.
 
 ``sigma_nfw`` is the batched counterpart of clusterlensing's ``SurfaceMassDensity(rs, delta_c, rho_crit, rbins,
 offsets).sigma_nfw()`` - the product the reference's sigma_1h_profiles forms - as a plain float64 array in the units
-of its inputs (Msun/Mpc^2 from Mpc and Msun/Mpc^3).  The kernels are in hmvec_amd/csrc/kernels/lensing.hpp.
+of its inputs (Msun/Mpc^2 from Mpc and Msun/Mpc^3); ``delta_sigma_nfw`` is the counterpart of its ``deltasigma_nfw()``.
+The kernels are in hmvec_amd/csrc/kernels/lensing.hpp.
 """
 import numpy as np
 
 from . import _native as nat
 
-__all__ = ["sigma_nfw", "kappa_2h_integral"]
+__all__ = ["sigma_nfw", "delta_sigma_nfw", "kappa_2h_integral", "gamma_t_2h_integral"]
 
 
 def _context(ctx):
@@ -34,6 +36,18 @@ def sigma_nfw(rs, delta_c, rho_crit, rbins, offsets=None, *, ctx=None):
     rs, delta_c, rho_crit: length-N per-halo arrays (scale radius, characteristic overdensity, critical density).
     rbins: (N, nR) or (nR,).  offsets: None, or a length-N array of Rayleigh miscentring widths; halos with offset 0
     take the centred profile (bit for bit the values of offsets=None).  Returns an (N, nR) float64 array."""
+    return _nfw_profile("hmg_lensing_sigma_nfw", rs, delta_c, rho_crit, rbins, offsets, ctx)
+
+
+def delta_sigma_nfw(rs, delta_c, rho_crit, rbins, offsets=None, *, ctx=None):
+    """Excess surface density Delta Sigma[i, j] = Sigmabar(<R) - Sigma(R) of NFW halo i at R = rbins[i, j] (or
+    rbins[j]); with offsets, Sigmabar_off(<R) - Sigma_off(R) of the Rayleigh-miscentred profile.  Arguments, checks
+    and shapes as sigma_nfw (halos with offset 0 take the centred profile, bit for bit)."""
+    return _nfw_profile("hmg_lensing_delta_sigma_nfw", rs, delta_c, rho_crit, rbins, offsets, ctx)
+
+
+def _nfw_profile(entry, rs, delta_c, rho_crit, rbins, offsets, ctx):
+    """sigma_nfw / delta_sigma_nfw: `entry` is the centred C entry point, entry + "_off" the miscentred one."""
     rs = _positive("rs", np.atleast_1d(rs)).ravel()
     n = rs.size
     delta_c = _positive("delta_c", np.atleast_1d(delta_c)).ravel()
@@ -63,13 +77,13 @@ def sigma_nfw(rs, delta_c, rho_crit, rbins, offsets=None, *, ctx=None):
     d_rs, d_dc, d_rho, d_r = (_dev(ctx, a) for a in (rs, delta_c, rho_crit, rbins))
     out = ctx.empty((n, nr))
     if off is None or not np.all(off > 0):
-        ctx.call("hmg_lensing_sigma_nfw", n, nr, per_halo, d_rs.ptr, d_dc.ptr, d_rho.ptr, d_r.ptr, out.ptr)
+        ctx.call(entry, n, nr, per_halo, d_rs.ptr, d_dc.ptr, d_rho.ptr, d_r.ptr, out.ptr)
     if off is None:
         return out.numpy()
     centred = out.numpy() if not np.all(off > 0) else None
     # halos without an offset: the quadrature needs a positive width, so give them one and take the centred values
     d_off = _dev(ctx, np.where(off > 0, off, 1.0))
-    ctx.call("hmg_lensing_sigma_nfw_off", n, nr, per_halo, d_rs.ptr, d_dc.ptr, d_rho.ptr, d_r.ptr, d_off.ptr, out.ptr)
+    ctx.call(entry + "_off", n, nr, per_halo, d_rs.ptr, d_dc.ptr, d_rho.ptr, d_r.ptr, d_off.ptr, out.ptr)
     res = out.numpy()
     if centred is not None:
         res = np.where((off > 0)[:, None], res, centred)
@@ -83,6 +97,17 @@ def kappa_2h_integral(ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, *, ctx=
     ks (nk,) increasing, chi and pre (nz,), Pzk (nz, nk), thetas (nt,) in radians, ms (nm,) increasing, bh (nz, nm),
     Ms (nM,) inside [ms[0], ms[-1]].  Pzk and bh may be DeviceArrays (a model's resident arrays).  Returns an
     (nz, nt, nM) float64 array."""
+    return _two_halo("hmg_lensing_kappa_2h", ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, ctx)
+
+
+def gamma_t_2h_integral(ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, *, ctx=None):
+    """Two-halo tangential shear out[z, t, m] = b(z, Ms[m]) pre[z] trapz_l[P(z,k) J2(l thetas[t]) l / 2 pi]: the
+    kappa_2h_integral with J0 replaced by J2 (Oguri & Takada 2011), same arguments, checks and shape.  With pre
+    without its 1/Sigma_crit it is the two-halo Delta Sigma."""
+    return _two_halo("hmg_lensing_gamma_t_2h", ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, ctx)
+
+
+def _two_halo(entry, ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, ctx):
     ks = np.asarray(ks, dtype=np.float64).ravel()
     chi = np.asarray(chi, dtype=np.float64).ravel()
     pre = np.asarray(pre, dtype=np.float64).ravel()
@@ -107,6 +132,6 @@ def kappa_2h_integral(ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, *, ctx=
     ctx = _context(ctx)
     d = [_dev(ctx, a) for a in (ks, chi, pre, Pzk, thetas, ms, bh, Ms)]
     out = ctx.empty((nz, nt, nM))
-    ctx.call("hmg_lensing_kappa_2h", nz, nk, nt, nm, nM, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr,
+    ctx.call(entry, nz, nk, nt, nm, nM, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr,
              float(lmin), float(lmax), d[5].ptr, d[6].ptr, d[7].ptr, out.ptr)
     return out.numpy()

@@ -565,6 +565,26 @@ int hmg_lensing_kappa_2h(hmg_ctx* ctx, int nz, int nk, int ntheta, int nm, int n
                          const double* d_chi, const double* d_pre, const double* d_Pzk, const double* d_thetas,
                          double lmin, double lmax, const double* d_ms, const double* d_bh, const double* d_Ms,
                          double* d_out);
+/* Excess surface density Delta Sigma(R) = Sigmabar(<R) - Sigma(R), same arguments, shapes and
+ * checks as hmg_lensing_sigma_nfw / _off; d_out (n, nr) in Msun/Mpc^2.
+ * hmg_lensing_delta_sigma_nfw: centred (Wright & Brainerd 2000, eqs. 13-15, with a series around x = 1 and a
+ *   cancellation-free form at small x).
+ * hmg_lensing_delta_sigma_nfw_off: Rayleigh-miscentred of width d_offsets[h] [Mpc]: Sigma_off and the Rayleigh average
+ *   of the centred profile's mass in an offset disc, one wavefront per output, bit-identical on repeat.  The first call
+ *   on a device uploads its node tables and so cannot be inside a captured step.                                  */
+int hmg_lensing_delta_sigma_nfw(hmg_ctx* ctx, int n, int nr, int rbins_per_halo, const double* d_rs,
+                                const double* d_delta_c, const double* d_rho_crit, const double* d_rbins,
+                                double* d_out);
+int hmg_lensing_delta_sigma_nfw_off(hmg_ctx* ctx, int n, int nr, int rbins_per_halo, const double* d_rs,
+                                    const double* d_delta_c, const double* d_rho_crit, const double* d_rbins,
+                                    const double* d_offsets, double* d_out);
+/* Two-halo tangential shear, d_out (nz, ntheta, nM): hmg_lensing_kappa_2h with J0(l theta) replaced by J2(l theta)
+ * (Oguri & Takada 2011), same arguments and checks.  With pre(z) = rho_m(z) / (1+z)^3 / D_A(z)^2 (no 1/Sigma_crit)
+ * it is the two-halo Delta Sigma [Msun/Mpc^2].                                                                     */
+int hmg_lensing_gamma_t_2h(hmg_ctx* ctx, int nz, int nk, int ntheta, int nm, int nM, const double* d_ks,
+                           const double* d_chi, const double* d_pre, const double* d_Pzk, const double* d_thetas,
+                           double lmin, double lmax, const double* d_ms, const double* d_bh, const double* d_Ms,
+                           double* d_out);
 
 /* ---- kSZ forecasts (hmvec/ksz.py) ---------------------------------------------------------
  * hmg_ksz_pqperp: the Ma-Fry P_q_perp table d_out (nk, nz) for nz redshifts,

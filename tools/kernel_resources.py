@@ -32,6 +32,9 @@ KERNELS = [   # (label, regex on the mangled name)
     ("lensing_sigma_kernel  (centred Sigma, lensing.hip)", r"20lensing_sigma_kernelE"),
     ("lensing_sigma_off_kernel<4>  (miscentred Sigma, lensing.hip)", r"24lensing_sigma_off_kernelILi4EE"),
     ("lensing_kappa2h_kernel<256>  (two-halo convergence, lensing.hip)", r"22lensing_kappa2h_kernelILi256EE"),
+    ("lensing_delta_sigma_kernel  (centred Delta Sigma, lensing.hip)", r"26lensing_delta_sigma_kernelE"),
+    ("lensing_delta_sigma_off_kernel<4>  (miscentred Delta Sigma, lensing.hip)", r"30lensing_delta_sigma_off_kernelILi4EE"),
+    ("lensing_gamma2h_kernel<256>  (two-halo tangential shear, lensing.hip)", r"22lensing_gamma2h_kernelILi256EE"),
     ("ksz_pqperp_kernel<true>  (P_q_perp, tables in LDS, ksz.hip)", r"17ksz_pqperp_kernelILb1EE"),
     ("ksz_pqperp_kernel<false>  (P_q_perp, tables from memory, ksz.hip)", r"17ksz_pqperp_kernelILb0EE"),
     ("ksz_nvv_shared_kernel  (N_vv, one k_S integral per z, ksz.hip)", r"21ksz_nvv_shared_kernelE"),

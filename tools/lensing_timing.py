@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Device time of the cluster-lensing kernels on GPU 0:
+"""Device time of the cluster-lensing kernels (DESIGN.md sections 10 and 12) on GPU 0:
   * Sigma of 10 000 halos x 32 radii, centred (hmg_lensing_sigma_nfw) and miscentred (hmg_lensing_sigma_nfw_off);
-  * kappa_2h at nz = 32, ntheta = 64, nk = 4096 (hmg_lensing_kappa_2h, nM = 16).
+  * Delta Sigma of the same halos and radii, centred (hmg_lensing_delta_sigma_nfw) and miscentred
+    (hmg_lensing_delta_sigma_nfw_off);
+  * kappa_2h and gamma_t_2h at nz = 32, ntheta = 64, nk = 4096 (hmg_lensing_kappa_2h, hmg_lensing_gamma_t_2h, nM = 16).
 Inputs are uploaded once; each kernel is launched --warmup times, then timed --reps times between event records on
 the context's stream.  Prints one JSON line with the median and minimum milliseconds per kernel.
 
@@ -55,6 +57,11 @@ def main():
     res["sigma_miscentred_10000x32"] = timed(ctx, a.reps, a.warmup, "hmg_lensing_sigma_nfw_off", n, nr, 1, d[0].ptr,
                                              d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr, out.ptr)
     assert np.all(np.isfinite(out.numpy()))
+    res["delta_sigma_centred_10000x32"] = timed(ctx, a.reps, a.warmup, "hmg_lensing_delta_sigma_nfw", n, nr, 1,
+                                                d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, out.ptr)
+    res["delta_sigma_miscentred_10000x32"] = timed(ctx, a.reps, a.warmup, "hmg_lensing_delta_sigma_nfw_off", n, nr, 1,
+                                                   d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr, out.ptr)
+    assert np.all(np.isfinite(out.numpy()))
 
     nz, nt, nk, nm, nM = 32, 64, 4096, 64, 16
     ks = np.geomspace(1e-4, 100, nk)
@@ -71,6 +78,10 @@ def main():
     res["kappa_2h_nz32_nt64_nk4096"] = timed(ctx, a.reps, a.warmup, "hmg_lensing_kappa_2h", nz, nk, nt, nm, nM,
                                              e[0].ptr, e[1].ptr, e[2].ptr, e[3].ptr, e[4].ptr, 100.0, 1e4, e[5].ptr,
                                              e[6].ptr, e[7].ptr, out2.ptr)
+    assert np.all(np.isfinite(out2.numpy()))
+    res["gamma_t_2h_nz32_nt64_nk4096"] = timed(ctx, a.reps, a.warmup, "hmg_lensing_gamma_t_2h", nz, nk, nt, nm, nM,
+                                               e[0].ptr, e[1].ptr, e[2].ptr, e[3].ptr, e[4].ptr, 100.0, 1e4, e[5].ptr,
+                                               e[6].ptr, e[7].ptr, out2.ptr)
     assert np.all(np.isfinite(out2.numpy()))
     res["kernel_source_sha16"] = nat.kernel_source_sha16()
     print(json.dumps(res))
