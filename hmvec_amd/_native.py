@@ -512,6 +512,15 @@ def default_context(device=0):
     return c
 
 
+def context_or_default(ctx):
+    return default_context(0) if ctx is None else ctx
+
+
+def as_device(ctx, a):
+    """A DeviceArray as it is (resident model data), anything else uploaded."""
+    return a if isinstance(a, DeviceArray) else ctx.upload(np.ascontiguousarray(a, dtype=np.float64))
+
+
 def ptr(x):
     """Device pointer of a DeviceArray or NULL."""
     return None if x is None else x.ptr

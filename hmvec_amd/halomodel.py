@@ -1303,9 +1303,7 @@ class HaloModel(Cosmology):
         """The two-halo profiles: `integral` is lensing.kappa_2h_integral (J0) or gamma_t_2h_integral (J2); pre(z)
         carries 1/Sigma_crit(z, zsource) unless zsource is None."""
         th = self._lensing_thetas(thetas)
-        Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()
-        if not np.all(np.isfinite(Ms)) or np.any(Ms <= 0):
-            raise ValueError("masses must be finite and positive")
+        Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()       # (finite and positive: `integral` checks)
         if np.any(Ms < self.ms[0]) or np.any(Ms > self.ms[-1]):
             raise ValueError("A value in x_new is outside the interpolation range of the model's mass grid")
         chi, pre, sigmac = [], [], []

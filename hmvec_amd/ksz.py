@@ -20,6 +20,7 @@ import warnings
 import numpy as np
 
 from . import _native as nat
+from ._native import as_device as _dev, context_or_default as _context
 from . import utils
 from .cosmology import Cosmology
 from .halomodel import HaloModel
@@ -128,14 +129,6 @@ def get_interpolated_cls(Cls, chistar, kss):
 
 
 # ---------------------------------------------------------------------------------------------------- device calls
-def _context(ctx):
-    return nat.default_context(0) if ctx is None else ctx
-
-
-def _dev(ctx, a):
-    return a if isinstance(a, nat.DeviceArray) else ctx.upload(np.ascontiguousarray(a, dtype=np.float64))
-
-
 def _cls_array(Cls):
     if not isinstance(Cls, np.ndarray) or Cls.ndim != 1 or Cls.size == 0:
         raise ValueError("Cls must be a non-empty 1-d numpy array starting at l = 0")

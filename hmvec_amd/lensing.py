@@ -10,17 +10,9 @@ The kernels are in hmvec_amd/csrc/kernels/lensing.hpp.
 import numpy as np
 
 from . import _native as nat
+from ._native import as_device as _dev, context_or_default as _context
 
 __all__ = ["sigma_nfw", "delta_sigma_nfw", "kappa_2h_integral", "gamma_t_2h_integral"]
-
-
-def _context(ctx):
-    return nat.default_context(0) if ctx is None else ctx
-
-
-def _dev(ctx, a):
-    """A DeviceArray as it is (resident model data), anything else uploaded."""
-    return a if isinstance(a, nat.DeviceArray) else ctx.upload(np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _positive(name, a):

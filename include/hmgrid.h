@@ -544,43 +544,40 @@ int hmg_profile_fft_table(hmg_ctx* ctx, int nz, int nm, int nk, int nxs, double 
                           const double* d_cmax, const double* d_rss, const double* d_zs,
                           const double* d_ks, int do_mass_norm, double* d_out);
 
-/* ---- cluster-lensing profiles (hmvec/hmvec.py:574-625) ----------------------------------
+/* ---- cluster-lensing profiles (hmvec/hmvec.py:574-625; DESIGN.md sections 10 and 12) ----------------------------
  * Per-halo inputs have n entries: scale radius r_s [Mpc], delta_c and rho_crit(z) [Msun/Mpc^3].  d_rbins holds the
- * projected radii [Mpc]: (n, nr) when rbins_per_halo != 0, else one row of nr shared by every halo.  d_out is (n, nr),
- * Sigma in Msun/Mpc^2.  Radii, r_s and offsets must be positive; the Python layer checks values, these check shapes.
- * hmg_lensing_sigma_nfw: the centred NFW profile (Wright & Brainerd 2000, eq. 11, with a series around x = 1).
+ * projected radii [Mpc]: (n, nr) when rbins_per_halo != 0, else one row of nr shared by every halo.  d_out is (n, nr)
+ * in Msun/Mpc^2.  Radii, r_s and offsets must be positive; the Python layer checks values, these check shapes.
+ * hmg_lensing_sigma_nfw: Sigma of the centred NFW profile (Wright & Brainerd 2000, eq. 11, with a series around
+ *   x = 1).
  * hmg_lensing_sigma_nfw_off: the same averaged over Rayleigh-distributed centre offsets of width d_offsets[h] [Mpc]
  *   (2-D quadrature, one wavefront per output, bit-identical on repeat).  The first call on a device uploads its node
- *   table and so cannot be inside a captured step.                                                               */
+ *   table and so cannot be inside a captured step.
+ * hmg_lensing_delta_sigma_nfw[_off]: same arguments and checks; store the excess surface density
+ *   Delta Sigma(R) = Sigmabar(<R) - Sigma(R) (eqs. 13-15, with a series around x = 1 and a cancellation-free form at
+ *   small x; miscentred: Sigma_off and the Rayleigh average of the centred profile's mass in an offset disc, from the
+ *   same outer nodes and a second node table).                                                                     */
 int hmg_lensing_sigma_nfw(hmg_ctx* ctx, int n, int nr, int rbins_per_halo, const double* d_rs, const double* d_delta_c,
                           const double* d_rho_crit, const double* d_rbins, double* d_out);
 int hmg_lensing_sigma_nfw_off(hmg_ctx* ctx, int n, int nr, int rbins_per_halo, const double* d_rs,
                               const double* d_delta_c, const double* d_rho_crit, const double* d_rbins,
                               const double* d_offsets, double* d_out);
-/* Two-halo convergence, d_out (nz, ntheta, nM):
- *   b(z, M) pre(z) trapz_l[ P(z,k) J0(l theta) l / 2 pi ],  l = k chi(z) with lmin < l < lmax (strict, grid order),
- * pre(z) = rho_m(z) / (1+z)^3 / Sigma_crit(z) / D_A(z)^2 (nz), d_ks (nk) increasing, d_Pzk (nz, nk), d_thetas [rad]
- * (ntheta), b(z, M) the linear interpolation of d_bh (nz, nm) on d_ms (nm >= 2, increasing) at d_Ms (nM).       */
-int hmg_lensing_kappa_2h(hmg_ctx* ctx, int nz, int nk, int ntheta, int nm, int nM, const double* d_ks,
-                         const double* d_chi, const double* d_pre, const double* d_Pzk, const double* d_thetas,
-                         double lmin, double lmax, const double* d_ms, const double* d_bh, const double* d_Ms,
-                         double* d_out);
-/* Excess surface density Delta Sigma(R) = Sigmabar(<R) - Sigma(R), same arguments, shapes and
- * checks as hmg_lensing_sigma_nfw / _off; d_out (n, nr) in Msun/Mpc^2.
- * hmg_lensing_delta_sigma_nfw: centred (Wright & Brainerd 2000, eqs. 13-15, with a series around x = 1 and a
- *   cancellation-free form at small x).
- * hmg_lensing_delta_sigma_nfw_off: Rayleigh-miscentred of width d_offsets[h] [Mpc]: Sigma_off and the Rayleigh average
- *   of the centred profile's mass in an offset disc, one wavefront per output, bit-identical on repeat.  The first call
- *   on a device uploads its node tables and so cannot be inside a captured step.                                  */
 int hmg_lensing_delta_sigma_nfw(hmg_ctx* ctx, int n, int nr, int rbins_per_halo, const double* d_rs,
                                 const double* d_delta_c, const double* d_rho_crit, const double* d_rbins,
                                 double* d_out);
 int hmg_lensing_delta_sigma_nfw_off(hmg_ctx* ctx, int n, int nr, int rbins_per_halo, const double* d_rs,
                                     const double* d_delta_c, const double* d_rho_crit, const double* d_rbins,
                                     const double* d_offsets, double* d_out);
-/* Two-halo tangential shear, d_out (nz, ntheta, nM): hmg_lensing_kappa_2h with J0(l theta) replaced by J2(l theta)
- * (Oguri & Takada 2011), same arguments and checks.  With pre(z) = rho_m(z) / (1+z)^3 / D_A(z)^2 (no 1/Sigma_crit)
- * it is the two-halo Delta Sigma [Msun/Mpc^2].                                                                     */
+/* Two-halo convergence, d_out (nz, ntheta, nM):
+ *   b(z, M) pre(z) trapz_l[ P(z,k) J0(l theta) l / 2 pi ],  l = k chi(z) with lmin < l < lmax (strict, grid order),
+ * pre(z) = rho_m(z) / (1+z)^3 / Sigma_crit(z) / D_A(z)^2 (nz), d_ks (nk) increasing, d_Pzk (nz, nk), d_thetas [rad]
+ * (ntheta), b(z, M) the linear interpolation of d_bh (nz, nm) on d_ms (nm >= 2, increasing) at d_Ms (nM).
+ * hmg_lensing_gamma_t_2h: same arguments and checks; J2(l theta) in place of J0 (Oguri & Takada 2011): the two-halo
+ *   tangential shear, or with pre(z) without its 1/Sigma_crit the two-halo Delta Sigma [Msun/Mpc^2].               */
+int hmg_lensing_kappa_2h(hmg_ctx* ctx, int nz, int nk, int ntheta, int nm, int nM, const double* d_ks,
+                         const double* d_chi, const double* d_pre, const double* d_Pzk, const double* d_thetas,
+                         double lmin, double lmax, const double* d_ms, const double* d_bh, const double* d_Ms,
+                         double* d_out);
 int hmg_lensing_gamma_t_2h(hmg_ctx* ctx, int nz, int nk, int ntheta, int nm, int nM, const double* d_ks,
                            const double* d_chi, const double* d_pre, const double* d_Pzk, const double* d_thetas,
                            double lmin, double lmax, const double* d_ms, const double* d_bh, const double* d_Ms,

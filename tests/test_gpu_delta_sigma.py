@@ -7,6 +7,8 @@ mpmath of the Wright & Brainerd closed forms, the miscentred one against a host 
 miscentred Sigma, the device J2 against mpmath, and the two-halo terms against a numpy restatement on the inputs stored
 with tests/golden/lensing_2h.npz.
 """
+import os
+import sys
 
 import mpmath as mp
 import numpy as np
@@ -15,17 +17,13 @@ from scipy.special import jv
 
 from conftest import load_golden
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from lensing_model import model  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 ARCMIN = np.pi / 180 / 60
 _trapz = getattr(np, "trapezoid", None) or np.trapz
-
-
-def model(zs, ks=None, ms=None):
-    import hmvec_amd as hm
-    ks = np.geomspace(1e-4, 100, 200) if ks is None else ks
-    ms = np.geomspace(2e10, 1e17, 40) if ms is None else ms
-    return hm.HaloModel(np.atleast_1d(zs), ks, ms=ms, accuracy="low", engine="analytic")
 
 
 def mp_delta_sigma_shape(x):
@@ -251,7 +249,7 @@ def test_gamma_t_1h_is_delta_sigma_over_sigma_crit():
     assert np.allclose(G, D / h.sigma_crit(np.array([0.5]), 2.0), rtol=1e-15, atol=0)
 
 
-# ---------------------------------------------------------------- 7. validation
+# ---------------------------------------------------------------- 7. validation (the C ABI's: tests/test_gpu_lensing.py)
 def test_methods_reject_bad_inputs():
     h = model([0.5])
     th = np.array([1.0, 2.0]) * ARCMIN
@@ -286,28 +284,3 @@ def test_methods_reject_bad_inputs():
         gamma_t_2h_integral([1.0, 2.0], [1.0], [1.0], [[1.0, 0.0]], [1e-3], 0.5, 3.0, [1.0, 2.0],
                             [[1.0, 1.0]], [3.0])
 
-
-def test_c_abi_rejects_null_pointers_and_empty_sizes():
-    from hmvec_amd import _native as nat
-    ctx = nat.Context(0)
-    d = ctx.empty((8,))
-    p = d.ptr
-    with pytest.raises(nat.NativeError, match="NULL"):
-        ctx.call("hmg_lensing_delta_sigma_nfw", 2, 2, 0, p, p, None, p, p)
-    with pytest.raises(nat.NativeError, match="empty"):
-        ctx.call("hmg_lensing_delta_sigma_nfw", 0, 2, 0, p, p, p, p, p)
-    with pytest.raises(nat.NativeError, match="NULL"):
-        ctx.call("hmg_lensing_delta_sigma_nfw_off", 2, 2, 0, p, p, p, p, None, p)
-    with pytest.raises(nat.NativeError, match="empty"):
-        ctx.call("hmg_lensing_delta_sigma_nfw_off", 2, 0, 1, p, p, p, p, p, p)
-    g2 = [1, 2, 2, 2, 1, p, p, p, p, p, 100.0, 1e4, p, p, p, p]
-    for i, bad in ((5, None), (15, None), (0, 0), (2, 0)):
-        a = list(g2)
-        a[i] = bad
-        with pytest.raises(nat.NativeError):
-            ctx.call("hmg_lensing_gamma_t_2h", *a)
-    a = list(g2)
-    a[3] = 1
-    with pytest.raises(nat.NativeError, match="two masses"):
-        ctx.call("hmg_lensing_gamma_t_2h", *a)
-    ctx.close()

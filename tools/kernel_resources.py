@@ -29,12 +29,12 @@ KERNELS = [   # (label, regex on the mangled name)
     ("profile_table_kernel<512,2,4,0>  (user callable, run-time plan)", r"profile_table_kernelILi512ELi2ELi4ELi0E"),
     ("stand-alone: profile_fused_kernel<512,2,3,2500>", r"profile_fused_kernelILi512ELi2ELi3ELi2500E"),
     ("stand-alone: nfw_kernel", r"10nfw_kernelE"),
-    ("lensing_sigma_kernel  (centred Sigma, lensing.hip)", r"20lensing_sigma_kernelE"),
-    ("lensing_sigma_off_kernel<4>  (miscentred Sigma, lensing.hip)", r"24lensing_sigma_off_kernelILi4EE"),
-    ("lensing_kappa2h_kernel<256>  (two-halo convergence, lensing.hip)", r"22lensing_kappa2h_kernelILi256EE"),
-    ("lensing_delta_sigma_kernel  (centred Delta Sigma, lensing.hip)", r"26lensing_delta_sigma_kernelE"),
-    ("lensing_delta_sigma_off_kernel<4>  (miscentred Delta Sigma, lensing.hip)", r"30lensing_delta_sigma_off_kernelILi4EE"),
-    ("lensing_gamma2h_kernel<256>  (two-halo tangential shear, lensing.hip)", r"22lensing_gamma2h_kernelILi256EE"),
+    ("lensing_centred_kernel<false>  (centred Sigma, lensing.hip)", r"22lensing_centred_kernelILb0EE"),
+    ("lensing_off_kernel<4,false>  (miscentred Sigma, lensing.hip)", r"18lensing_off_kernelILi4ELb0EE"),
+    ("lensing_2h_kernel<256,0>  (two-halo convergence, lensing.hip)", r"17lensing_2h_kernelILi256ELi0EE"),
+    ("lensing_centred_kernel<true>  (centred Delta Sigma, lensing.hip)", r"22lensing_centred_kernelILb1EE"),
+    ("lensing_off_kernel<4,true>  (miscentred Delta Sigma, lensing.hip)", r"18lensing_off_kernelILi4ELb1EE"),
+    ("lensing_2h_kernel<256,2>  (two-halo tangential shear, lensing.hip)", r"17lensing_2h_kernelILi256ELi2EE"),
     ("ksz_pqperp_kernel<true>  (P_q_perp, tables in LDS, ksz.hip)", r"17ksz_pqperp_kernelILb1EE"),
     ("ksz_pqperp_kernel<false>  (P_q_perp, tables from memory, ksz.hip)", r"17ksz_pqperp_kernelILb0EE"),
     ("ksz_nvv_shared_kernel  (N_vv, one k_S integral per z, ksz.hip)", r"21ksz_nvv_shared_kernelE"),
