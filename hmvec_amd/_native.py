@@ -161,6 +161,10 @@ SIGNATURES = {
     "hmg_profile_fft": [_P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _D,
                         _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     "hmg_profile_fft_logx": [_P, _I, _P, _P],
+    "hmg_prefix_deferral": [_P, _I],
+    "hmg_prefix_fill": [_P, _P],
+    "hmg_prefix_pending": [_P, _P, C.POINTER(_I)],
+    "hmg_prefix_fill_rows": [_P, _P, _P, _P, _I, _I],
     "hmg_hod": [_P, _I, _I, C.POINTER(HodParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "hmg_power": [_P, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), _P, _P, _P, _P, _P, _P,
                   _D, _D, _P, _P],
@@ -441,7 +445,7 @@ class Context:
         check(self.lib.hmg_elapsed_ms(self.handle, s0, s1, C.byref(ms)))
         return ms.value
 
-    _NO_FLUSH = frozenset(["hmg_bracket_next", "hmg_profile_support_epoch"])      # calls that enqueue nothing and read nothing
+    _NO_FLUSH = frozenset(["hmg_bracket_next", "hmg_profile_support_epoch", "hmg_prefix_deferral"])      # calls that enqueue nothing and read nothing
 
     def call(self, name, *args):
         if name not in self._NO_FLUSH:

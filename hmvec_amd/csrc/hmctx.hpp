@@ -88,6 +88,13 @@ struct SupportKey {                       // what a measured bound on a launch's
     }
 };
 
+struct PrefixEntry {                      // a tensor some transform wrote with its left fill deferred (hmg_prefix_deferral)
+    int* nconst = nullptr;                // the hint arrays that describe the unwritten tiles
+    double* cconst = nullptr;
+    int rows = 0, nk = 0;
+    bool pending = false;                 // the tiles are unwritten right now
+};
+
 struct hmg_ctx {
     int device = 0;
     hipStream_t stream = nullptr;             // stream of the current lane
@@ -149,6 +156,12 @@ struct hmg_ctx {
     std::map<int, hipGraphExec_t> graphs;
     std::map<int, int> graph_kernels;              // kernel nodes per captured graph
     int next_graph_id = 1;
+    // deferred left fills: the state per tensor pointer; what the launches of the capture in progress do to it (a
+    // capture executes nothing, so the state itself stays); what each captured step does to it at every replay
+    int prefix_deferral = 0;
+    std::map<void*, PrefixEntry> prefix;
+    std::map<void*, PrefixEntry> prefix_capture;
+    std::map<int, std::map<void*, PrefixEntry>> graph_prefix;
     hmg_ctx() { for (auto& b : bracket) b[0] = b[1] = -1; }
 };
 constexpr size_t FREE_CACHE_LIMIT = (size_t)4 << 30;   // bytes kept in the free list before real frees
@@ -160,4 +173,25 @@ int sync_all(hmg_ctx* c);                                 // all lanes + fault c
 int ensure_scratch(hmg_ctx* c, int slot, size_t bytes);   // grow-only scratch arenas; refuses inside a capture
 int bracket_open(hmg_ctx* c, int kid, int* stop_slot);    // one-shot event brackets around a kernel (hmg_bracket_next)
 int bracket_close(hmg_ctx* c, int stop_slot);
+// ---- deferred left fills (the kernel and its entry points: hmgrid.hip)
+// A transform wrote the tensor at `out`: with hint arrays (e.nconst) and its prefix deferred (e.pending) or whole, or
+// without hint arrays - nothing describes its rows any more.  Entries stay after a fill: a captured step records the
+// fill of every tensor the context knows (hmg_prefix_fill).
+static inline void prefix_note(hmg_ctx* c, void* out, const PrefixEntry& e) {
+    auto& m = c->capturing ? c->prefix_capture : c->prefix;
+    if (e.nconst || c->capturing) m[out] = e;
+    else m.erase(out);
+}
+// a captured step ran: its launches' effects on the state
+static inline void prefix_replayed(hmg_ctx* c, const std::map<void*, PrefixEntry>& fx) {
+    for (auto& kv : fx) {
+        if (kv.second.nconst) c->prefix[kv.first] = kv.second;
+        else c->prefix.erase(kv.first);
+    }
+}
+// the block [p, p + bytes) leaves its owner: no entry may outlive it
+static inline void prefix_drop_block(hmg_ctx* c, void* p, size_t bytes) {
+    auto lo = c->prefix.lower_bound(p), hi = c->prefix.lower_bound((char*)p + bytes);
+    c->prefix.erase(lo, hi);
+}
 static inline dim3 grid1d(size_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }

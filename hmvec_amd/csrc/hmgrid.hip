@@ -712,6 +712,8 @@ static int profile_fft_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_profil
     REQUIRE(c && xs && kts && cmax && rss && zs && ks && p.d_out, "NULL argument");
     REQUIRE((p.d_nconst == nullptr) == (p.d_cconst == nullptr), "pass both hint arrays or neither");
     REQUIRE(nz > 0 && nm > 0 && nk > 0, "empty grid");
+    // every route writes the tensor whole, except the one-row kernels under hmg_prefix_deferral (below)
+    prefix_note(c, p.d_out, PrefixEntry{p.d_nconst, p.d_cconst, nz * nm, nk, false});
     REQUIRE(nxs >= 4, "nxs too small");
     const int nh = nxs / 2;  // rfft output length is nh+1
     const int rows = nz * nm;
@@ -727,6 +729,7 @@ static int profile_fft_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_profil
     }
     if (r.FP) {
         FusedArgs A = fused_args(nm, nk, p, r.FP, R);
+        A.defer = c->prefix_deferral && A.nconst;
         int stop = -1;
         if (bracket_open(c, HMG_KERNEL_PROFILE_FFT, &stop)) return 1;
         if (!table && !A.logx && rows >= 8192) {   // no prepared table: its own launch pays from ~8000 rows (MI355X: -1 % at 16384 rows, +2 % at 4096)
@@ -743,6 +746,7 @@ static int profile_fft_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_profil
         else if (r.grouped) rc = with_shape(r.shape, [&](auto s) { return launch_group<decltype(s)>(c, A, rows, R); });
         else rc = with_shape(r.shape, [&](auto s) { return launch_fused<decltype(s)>(c, A, rows); });
         if (rc) return 1;
+        if (A.defer) prefix_note(c, p.d_out, PrefixEntry{A.nconst, A.cconst, rows, nk, true});
         R.chain_done = r.grouped;
         R.nfw_done = r.grouped && R.N;
         return bracket_close(c, stop);
@@ -801,6 +805,56 @@ int hmg_profile_fft(hmg_ctx* c, int nz, int nm, int nk, int nxs, double step, co
                                  cmax, rss, zs, ks, do_mass_norm, post, out, nconst, cconst, logxs};
     FftRiders R;
     return profile_fft_impl(c, nz, nm, nk, p, R);
+}
+
+// ---- deferred left fill (include/hmgrid.h; the state per tensor: hmctx.hpp)
+int hmg_prefix_deferral(hmg_ctx* c, int on) {
+    REQUIRE(c, "NULL ctx");
+    c->prefix_deferral = on != 0;
+    return 0;
+}
+
+int hmg_prefix_fill_rows(hmg_ctx* c, double* out, const int* nconst, const double* cconst, int rows, int nk) {
+    REQUIRE(c && out && nconst && cconst, "NULL argument");
+    REQUIRE(rows > 0 && nk > 0, "empty grid");
+    hipLaunchKernelGGL(prefix_fill_kernel, dim3(rows), dim3(256), 0, c->stream, nk, nconst, cconst, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int hmg_prefix_pending(hmg_ctx* c, const double* out, int* pending) {
+    REQUIRE(c && out && pending, "NULL argument");
+    REQUIRE(!c->capturing, "the pending state is what replays make it: ask outside the captured step");
+    auto it = c->prefix.find((void*)out);
+    *pending = it != c->prefix.end() && it->second.pending;
+    return 0;
+}
+
+int hmg_prefix_fill(hmg_ctx* c, double* out) {
+    REQUIRE(c && out, "NULL argument");
+    PrefixEntry e;
+    if (c->capturing) {
+        // Nothing runs during a capture, and what is pending when the step is replayed is not known now: the launches of
+        // this capture decide if they wrote the tensor; otherwise the fill is recorded for every tensor the context knows
+        // (filling a prefix that is there writes the same values again).
+        auto ic = c->prefix_capture.find(out);
+        if (ic != c->prefix_capture.end()) {
+            if (!ic->second.nconst || !ic->second.pending) return 0;
+            e = ic->second;
+        } else {
+            auto ig = c->prefix.find(out);
+            if (ig == c->prefix.end()) return 0;
+            e = ig->second;
+        }
+    } else {
+        auto it = c->prefix.find(out);
+        if (it == c->prefix.end() || !it->second.pending) return 0;
+        e = it->second;
+    }
+    if (hmg_prefix_fill_rows(c, out, e.nconst, e.cconst, e.rows, e.nk)) return 1;
+    e.pending = false;
+    prefix_note(c, out, e);
+    return 0;
 }
 
 int hmg_profile_support_epoch(hmg_ctx* c, long long epoch) {

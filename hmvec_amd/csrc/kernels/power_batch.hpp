@@ -237,6 +237,11 @@ template <int NT, int NTR, int V, bool W16, unsigned CODE = 0>
 __global__ __launch_bounds__(W16 ? 1024 : 512) void power_batch_kernel(BatchArgs A) {
     extern __shared__ double red[];  // [8][NACC*V][64]: parked sums / pair exchange, then the cross-wave reduction
     using vec_t = typename VecT<V>::type;
+    // a k tile that lies in a tensor's constant prefix is never loaded (fetch, below): the row kernels may leave whole
+    // HMG_PREFIX_TILE-wide tiles of that prefix unwritten (hmg_prefix_deferral), which holds them apart from every tile
+    // this kernel does load only if its own tiles - 64 V wide, W16 or not - never straddle one of theirs
+    static_assert(V == 1 || V == 2, "k-tile widths the deferred left fill was checked for");
+    static_assert(HMG_PREFIX_TILE % (64 * V) == 0, "HMG_PREFIX_TILE must be a multiple of every k-tile width");
     constexpr int NC1 = 1 + NT;
     constexpr int STRIDE = pb_stride(CODE, NTR, NC1);
     constexpr int NPAIR = NTR * (NTR + 1) / 2;

@@ -293,14 +293,19 @@ __device__ __forceinline__ void profile_fused_row(const FusedArgs& A, int row, d
     if (nleft > 0) {
         typedef double v2d __attribute__((ext_vector_type(2)));
         const double c = u1 * pf;
-        const int head = (int)((reinterpret_cast<uintptr_t>(dst) >> 3) & 1);     // row start not 16-B aligned
-        const int npair = (nleft - head) >> 1;
-        v2d* __restrict__ d2 = reinterpret_cast<v2d*>(dst + head);
+        // deferred left fill (FusedArgs::defer): the whole HMG_PREFIX_TILE-wide tiles of the prefix stay unwritten, only
+        // the partial tile [nskip, nleft) is filled here (nskip is even: the fill keeps the 16-byte phase of the row)
+        const int nskip = A.defer ? (nleft & ~(HMG_PREFIX_TILE - 1)) : 0;
+        double* __restrict__ d0 = dst + nskip;
+        const int nfill = nleft - nskip;
+        const int head = (int)((reinterpret_cast<uintptr_t>(d0) >> 3) & 1);      // row start not 16-B aligned
+        const int npair = (nfill - head) >> 1;
+        v2d* __restrict__ d2 = reinterpret_cast<v2d*>(d0 + head);
         const v2d cc = {c, c};
         for (int q = threadIdx.x; q < npair; q += NT) __builtin_nontemporal_store(cc, &d2[q]);
-        if (threadIdx.x == 0) {
-            if (head) __builtin_nontemporal_store(c, &dst[0]);
-            if ((nleft - head) & 1) __builtin_nontemporal_store(c, &dst[nleft - 1]);
+        if (threadIdx.x == 0 && nfill > 0) {
+            if (head) __builtin_nontemporal_store(c, &d0[0]);
+            if ((nfill - head) & 1) __builtin_nontemporal_store(c, &d0[nfill - 1]);
         }
     }
     auto interp = [&](double k) {
@@ -341,6 +346,29 @@ template <int NT, int MAXB, int MAXP, int SPECM>
 __global__ __launch_bounds__(NT, (fused_occ<MAXB, SPECM>())) void profile_table_kernel(FusedArgs A) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     profile_fused_row<NT, MAXB, MAXP, SPECM, true>(A, blockIdx.x, smem);
+}
+
+// The deferred part of the left fill (FusedArgs::defer), for a reader other than the batched mass integrals: one
+// workgroup per row writes cconst[row] - the value phase D would have written, u_1 * post - into the whole
+// HMG_PREFIX_TILE-wide tiles below nconst[row], in the same 16-byte stores.
+__global__ __launch_bounds__(256) void prefix_fill_kernel(int nk, const int* __restrict__ nconst,
+                                                          const double* __restrict__ cconst, double* __restrict__ out) {
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    const int row = blockIdx.x;
+    int n = nconst[row] & ~(HMG_PREFIX_TILE - 1);
+    n = n < nk ? n : nk;
+    if (n <= 0) return;
+    const double c = cconst[row];
+    double* __restrict__ dst = out + (size_t)row * nk;
+    const int head = (int)((reinterpret_cast<uintptr_t>(dst) >> 3) & 1);     // row start not 16-B aligned
+    const int npair = (n - head) >> 1;
+    v2d* __restrict__ d2 = reinterpret_cast<v2d*>(dst + head);
+    const v2d cc = {c, c};
+    for (int q = threadIdx.x; q < npair; q += 256) __builtin_nontemporal_store(cc, &d2[q]);
+    if (threadIdx.x == 0) {
+        if (head) __builtin_nontemporal_store(c, &dst[0]);
+        if ((n - head) & 1) __builtin_nontemporal_store(c, &dst[n - 1]);
+    }
 }
 
 // (K45p, the long radial grids with short support - profile_pruned_kernel and the chirp route: longgrid.hip, a

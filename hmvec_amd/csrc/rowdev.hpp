@@ -58,6 +58,10 @@ struct FusedArgs {
     // from a table instead of the family - rho_tab[n] shared by every row, or rho_tab[row nxs + n]
     const double* rho_tab;
     int rho_shared;
+    // deferral of the left fill (include/hmgrid.h: hmg_prefix_deferral; needs the hint arrays): the one-row kernels leave
+    // the whole HMG_PREFIX_TILE-wide tiles of a row's constant prefix unwritten - (nconst, cconst) describe them, the
+    // batched mass integrals never load them, hmg_prefix_fill writes them for any other reader
+    int defer;
     // optional: the output-side scalars of every row ([rows][HMG_ROWSC_STRIDE], include/hmgrid.h: hmg_rows_part), left by
     // the launch that computed the rows' length scales; nullptr: one wavefront of the row's workgroup works them out
     const double* rowsc;

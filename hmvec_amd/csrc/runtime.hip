@@ -213,6 +213,7 @@ int hmg_free(hmg_ctx* c, void* p) {
     }
     if (c->lanes_dirty && sync_all(c)) return 1;
     const size_t bytes = it->second;
+    prefix_drop_block(c, p, bytes);       // (a recycled block starts without a pending prefix)
     if (c->cached_bytes + bytes <= FREE_CACHE_LIMIT) {
         c->free_blocks.emplace(bytes, p);
         c->cached_bytes += bytes;
@@ -420,7 +421,7 @@ int hmg_graph_end(hmg_ctx* c, int* id) {
     hipGraphExec_t ge = nullptr;
     hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
     (void)hipGraphDestroy(g);
-    if (e != hipSuccess) release_deferred_frees(c);       // no graph: nothing can refer to them any more
+    if (e != hipSuccess) { release_deferred_frees(c); c->prefix_capture.clear(); }       // no graph: nothing can refer to them any more
     HIP_TRY(e);
     *id = c->next_graph_id++;
     c->graphs[*id] = ge;
@@ -429,6 +430,9 @@ int hmg_graph_end(hmg_ctx* c, int* id) {
     // refused) and may be an operand of a captured launch: it stays out of the free list as long as the
     // graph can be replayed.
     c->graph_blocks[*id].swap(c->freed_in_capture);
+    // ... and what its launches do to the deferred left fills happens at every replay
+    c->graph_prefix[*id].swap(c->prefix_capture);
+    c->prefix_capture.clear();
     return 0;
 }
 int hmg_graph_kernel_nodes(hmg_ctx* c, int id, int* n) {
@@ -443,6 +447,7 @@ int hmg_graph_abort(hmg_ctx* c) {      // leave capture mode after a failed call
     if (!c->capturing) return 0;
     c->capturing = false;
     release_deferred_frees(c);
+    c->prefix_capture.clear();
     c->lane = 0;
     c->stream = c->lanes[0];
     hipGraph_t g = nullptr;
@@ -457,6 +462,8 @@ int hmg_graph_launch(hmg_ctx* c, int id) {
     auto it = c->graphs.find(id);
     REQUIRE(it != c->graphs.end(), "unknown graph id");
     HIP_TRY(hipGraphLaunch(it->second, c->stream));
+    auto gp = c->graph_prefix.find(id);
+    if (gp != c->graph_prefix.end()) prefix_replayed(c, gp->second);
     return 0;
 }
 int hmg_graph_destroy(hmg_ctx* c, int id) {
@@ -466,6 +473,7 @@ int hmg_graph_destroy(hmg_ctx* c, int id) {
     if (sync_all(c)) return 1;
     HIP_TRY(hipGraphExecDestroy(it->second));
     c->graphs.erase(it);
+    c->graph_prefix.erase(id);
     auto gb = c->graph_blocks.find(id);
     if (gb != c->graph_blocks.end()) {
         for (void* p : gb->second) (void)hmg_free(c, p);

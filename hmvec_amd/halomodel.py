@@ -48,8 +48,24 @@ class DeviceDict(MutableMapping):
         self._host = {}
         self._hint = {}       # name -> (d_nconst, d_cconst): constant-prefix hint emitted with the tensor
 
-    def dev(self, name):
-        return self._dev[name]
+    def dev(self, name, fill=True):
+        """The tensor on the device.  A pass of the facade leaves the whole tiles of a hinted tensor's constant prefix
+        unwritten (hmg_prefix_deferral: the batched mass integrals never load them); every other reader gets them
+        filled first - the context knows per buffer whether there is anything to fill.  fill=False is for the
+        batched mass integrals alone."""
+        d = self._dev[name]
+        if fill and name in self._hint:
+            self._ctx_getter().call("hmg_prefix_fill", d.ptr)
+        return d
+
+    def _pending(self, name):
+        """True if a transform has left the prefix of this tensor unwritten since it was last filled."""
+        if name not in self._hint:
+            return False
+        ctx = self._ctx_getter()          # (a transform still in the queue came through set_dev: no cached copy to protect)
+        n = C.c_int()
+        nat.check(ctx.lib.hmg_prefix_pending(ctx.handle, self._dev[name].ptr, C.byref(n)))
+        return bool(n.value)
 
     def hint(self, name):
         """(nconst, cconst) device arrays of a profile produced by hmg_profile_fft, else (None, None)."""
@@ -65,8 +81,12 @@ class DeviceDict(MutableMapping):
         self._on_change()
 
     def __getitem__(self, name):
+        # (a pending prefix means a transform has rewritten the buffer since the cached copy was made - a replayed
+        # or re-issued pass does not come through set_dev)
+        if name in self._host and self._pending(name):
+            del self._host[name]
         if name not in self._host:
-            self._host[name] = self._dev[name].numpy()
+            self._host[name] = self.dev(name).numpy()
         return self._host[name]
 
     def __setitem__(self, name, value):
@@ -152,6 +172,9 @@ class HaloModel(Cosmology):
         self._groups = os.environ.get("HMG_NO_GROUPS", "0") != "1" and not self._use_lanes
         self._stages = []
         self._stage_dims = None
+        # The transforms of this model leave the left fill of a hinted tensor to whoever reads it (DeviceDict.dev;
+        # DESIGN.md section 3).  False (or HMG_NO_PREFIX_DEFERRAL=1): they write every tensor whole (A/B timing, tests).
+        self.prefix_deferral = os.environ.get("HMG_NO_PREFIX_DEFERRAL", "0") != "1"
 
         # (name, name2) -> (state version, P1h, P2h): a fused launch yields both terms, so the
         # usual get_power_1halo(a,b) followed by get_power_2halo(a,b) streams the tensors once
@@ -372,10 +395,12 @@ class HaloModel(Cosmology):
         if "fft" in st and ("massfn" in st or "nfw" in st) and "rows" not in st and not x:
             # tensor group: chain (sigma^2 -> n, b -> HOD sums -> coefficient rows) | profile rows | NFW rows, one launch
             ctx.call_now("hmg_profile_support_epoch", getattr(self, "_epoch", 0))
+            ctx.call_now("hmg_prefix_deferral", int(self.prefix_deferral))
             try:
                 ctx.call_now("hmg_group_tensors", nz, nm, nk, nq, ref("massfn"), ref("hod") if hod_sums else None,
                              C.byref(prep) if prep is not None else None, ref("nfw"), ref("fft"))
             finally:
+                ctx.call_now("hmg_prefix_deferral", 0)
                 ctx.call_now("hmg_profile_support_epoch", 0)
             return prep is not None
         nfw_alone = st.pop("nfw") if "nfw_alone" in x and "nfw" in st else None
@@ -395,10 +420,12 @@ class HaloModel(Cosmology):
             # the support tag is context state: it is set right around the ONE call it describes and restored whatever
             # that call does (a call that raises inside a capture must not leave this model's tag behind: ADVICE r05)
             ctx.call_now("hmg_profile_support_epoch", getattr(self, "_epoch", 0))
+            ctx.call_now("hmg_prefix_deferral", int(self.prefix_deferral))       # (context state, like the tag)
             try:
                 ctx.call_now("hmg_group_profile", nz, nm, nk, ref("fft"), ref("hod") if hod_sums else None,
                              C.byref(prep) if prep is not None else None)
             finally:
+                ctx.call_now("hmg_prefix_deferral", 0)
                 ctx.call_now("hmg_profile_support_epoch", 0)
             return prep is not None
         return False
@@ -621,9 +648,11 @@ class HaloModel(Cosmology):
         else:
             ctx.flush()          # deferred stages of ANY model on this context first: their own flush resets the tag
             ctx.call("hmg_profile_support_epoch", getattr(self, "_epoch", 0))
+            ctx.call("hmg_prefix_deferral", int(self.prefix_deferral))
             try:
                 ctx.call("hmg_profile_fft", nz, nm, nk, *args)
             finally:
+                ctx.call("hmg_prefix_deferral", 0)
                 ctx.call("hmg_profile_support_epoch", 0)
         return out, hint
 
@@ -865,14 +894,15 @@ class HaloModel(Cosmology):
             return trapz_lastaxis(fn2d(FN_BG_INTEGRAND, [self.nzm, Nc, Ns, self.bh]), self.ms) / ngal
 
     # ------------------------------------------------------------------ spectra
-    def _tracer(self, name, order):
+    def _tracer(self, name, order, fill=True):
         """Resolve a tracer name to an hmg_tracer.  `order` is the reference's lookup
         order, which differs between the 1-halo (hods, uk, pk: hmvec.py:516-523) and the
-        2-halo (uk, pk, hods: hmvec.py:537-550) code paths."""
+        2-halo (uk, pk, hods: hmvec.py:537-550) code paths.  fill=False: the tracer is for the batched mass
+        integrals (they read no deferred tile of a hinted tensor) or only its kind is wanted - nothing is enqueued."""
         def tensor(dd, nm_):
             # (a kernel trusts the pointer it is handed: a hand-assigned entry of another shape must stop here - numpy
             # would refuse to broadcast it in the reference, hmvec/hmvec.py:516-550)
-            d_ = dd.dev(nm_)
+            d_ = dd.dev(nm_, fill=fill)
             if tuple(d_.shape) != (self._nz, self._nm, self._nk):
                 raise ValueError(f"profile {nm_!r} has shape {tuple(d_.shape)}, the model's grid is "
                                  f"{(self._nz, self._nm, self._nk)}")
@@ -922,6 +952,7 @@ class HaloModel(Cosmology):
         name2 = name if name2 is None else name2
         keep = []
         want1, want2 = "1h" in want, "2h" in want
+        self._main()          # (the tracers below may enqueue a fill: on the lane of the transforms)
         a1, ka1 = self._tracer(name, "hmp")
         b1, kb1 = self._tracer(name2, "hmp")
         a2, ka2 = self._tracer(name, "mph") if want2 else (a1, ka1)
@@ -958,8 +989,8 @@ class HaloModel(Cosmology):
             for n_ in (a, b):
                 if n_ not in names:
                     names.append(n_)
-        res1 = [self._tracer(n_, "hmp") for n_ in names]
-        res2 = [self._tracer(n_, "mph") for n_ in names]
+        res1 = [self._tracer(n_, "hmp", fill=False) for n_ in names]
+        res2 = [self._tracer(n_, "mph", fill=False) for n_ in names]
         kinds = {n_: r[1] for n_, r in zip(names, res1)}
         batchable = len(names) <= 4 and all(r1[1] == r2[1] for r1, r2 in zip(res1, res2))
         batchable = batchable and not any(a != b and kinds[a] == kinds[b] and kinds[a] in "hp"
@@ -1030,7 +1061,7 @@ class HaloModel(Cosmology):
         """Profile tensors a tracer streams, or None if the 1-halo and 2-halo code paths would
         resolve the name differently (not batchable)."""
         try:
-            k1, k2 = self._tracer(nm_, "hmp")[1], self._tracer(nm_, "mph")[1]
+            k1, k2 = self._tracer(nm_, "hmp", fill=False)[1], self._tracer(nm_, "mph", fill=False)[1]
         except (ValueError, KeyError):
             return None
         if k1 != k2:
@@ -1075,7 +1106,7 @@ class HaloModel(Cosmology):
             if tn is not None and (tn <= need or small) and self._tensors_valid(tn):
                 names.append(cand)
         for n_ in names:
-            kinds[n_] = self._tracer(n_, "hmp")[1]
+            kinds[n_] = self._tracer(n_, "hmp", fill=False)[1]
         pairs = []
         for i, a in enumerate(names):
             for b in names[i:]:

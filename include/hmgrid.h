@@ -294,6 +294,30 @@ int hmg_profile_fft_logx(hmg_ctx* ctx, int nxs, const double* d_xs, double* d_lo
  * that prefix by a search and fills it without loading or testing its wavenumbers; for a target grid in any
  * other order pass NULL for both.                                                                */
 
+/* ---- deferred left fill of a hinted tensor (opt-in; off in a new context) ---------------------------------
+ * 63 % of the Battaglia tensor at the headline shape is the constant prefix the hint arrays describe, and the
+ * batched mass integrals (hmg_power_batch*, given the hints in their tracers) never load a k tile that lies in
+ * it.  With deferral ON, a one-row-in-LDS transform that is given hint arrays leaves the whole
+ * HMG_PREFIX_TILE-wide tiles of every row's prefix UNWRITTEN: elements [0, nconst[row] & ~(HMG_PREFIX_TILE-1))
+ * keep whatever the buffer held; the rest of the row, d_nconst and d_cconst are written as always.  The context
+ * remembers per tensor pointer that its prefix is pending - for eager calls at the call, for a captured step at
+ * every replay - until the next filling call, a transform into the same buffer that writes it whole (deferral
+ * off, no hints, the long-grid and rocFFT routes: they never defer), or the release of its block.
+ * Every reader other than the batched mass integrals - the one-pair entry points, a copy to the host, the
+ * caller's own kernels - must be preceded by the fill below; a filled tensor is bit-identical to the one a
+ * transform without deferral writes.  HMG_PREFIX_TILE is a multiple of every k-tile width of the batched mass
+ * integrals (asserted where they are compiled).                                                              */
+#define HMG_PREFIX_TILE 128
+int hmg_prefix_deferral(hmg_ctx* ctx, int on);
+/* Fill the pending prefix of the tensor at d_out on the current lane; nothing is enqueued when none is pending.
+ * Inside a captured step the fill is recorded whenever the context has ever seen a deferred transform into d_out
+ * (what a replay leaves pending is decided per replay, not at capture time).                                  */
+int hmg_prefix_fill(hmg_ctx* ctx, double* d_out);
+int hmg_prefix_pending(hmg_ctx* ctx, const double* d_out, int* pending);
+/* The fill itself, for a caller that keeps its own books: d_cconst[row] into [0, d_nconst[row] & ~(HMG_PREFIX_TILE-1))
+ * of each of the `rows` rows of nk doubles.                                                                    */
+int hmg_prefix_fill_rows(hmg_ctx* ctx, double* d_out, const int* d_nconst, const double* d_cconst, int rows, int nk);
+
 /* ---- H1-H3: HOD occupations ----------------------------------------------------------------
  * Replaces avg_Nc/avg_Ns/avg_NsNsm1/avg_NcNs, Mstellar_halo/Mhalo_stellar, get_ngal/get_bg
  * (hmvec/hmvec.py:634-731,462-466,936-957).  corr: 0 = "max", 1 = "min".                       */
