@@ -58,71 +58,50 @@ int hmg_sigma2_prepare(hmg_ctx* c, int nz, int nq, const double* sP, double* PT)
     HIP_TRY(hipGetLastError());
     return 0;
 }
+// The first stage of the contraction as every entry point sets it up: the k' segments, the z tile and the padded nz, the
+// three-dimensional grid of a launch of its own (in the front group its blocks line up in x with `riders` others), scratch
+// slot 4 for the partial sums and the record of the shape they have there (massfn_setup asks for it).
+static int sigma2_setup(hmg_ctx* c, int nz, int nm, int nq, const double* PT, const double* kq, const double* wq,
+                        const double* R, double tswitch, size_t riders, SigmaFrontArgs* G, dim3* grid) {
+    const int nseg = (nq + SIG_SEG_LEN - 1) / SIG_SEG_LEN, nzp = sigma2_nzp(nz);
+    *grid = dim3((nm + 15) / 16, nseg, nzp / sigma2_ztile(nz));
+    if (riders) REQUIRE((size_t)grid->x * grid->y * grid->z + riders <= 2147483647u, "grid too large");
+    else REQUIRE(grid->y <= 65535 && grid->z <= 65535, "grid too large");
+    if (ensure_scratch(c, 4, (size_t)nseg * nz * nm * 8)) return 1;
+    *G = SigmaFrontArgs{nz, nzp, nm, nq, (int)grid->x, nseg, PT, kq, wq, R, tswitch, (double*)c->scratch[4]};
+    c->sig_nz = nz; c->sig_nm = nm; c->sig_nq = nq;
+    return 0;
+}
+// ... and as a launch of its own: the matrix-core kernel; G->partial, G->nseg are what the second stage reads
+static int sigma2_first_stage(hmg_ctx* c, int nz, int nm, int nq, const double* PT, const double* kq, const double* wq,
+                              const double* R, double tswitch, SigmaFrontArgs* G) {
+    dim3 grid;
+    if (sigma2_setup(c, nz, nm, nq, PT, kq, wq, R, tswitch, 0, G, &grid)) return 1;
+    if (sigma2_ztile(nz) == 32)
+        hipLaunchKernelGGL(sigma2_mfma_kernel<2>, grid, dim3(64), 0, c->stream, nz, G->nzp, nm, nq,
+                           PT, kq, wq, R, tswitch, G->partial);
+    else
+        hipLaunchKernelGGL(sigma2_mfma_kernel<1>, grid, dim3(64), 0, c->stream, nz, G->nzp, nm, nq,
+                           PT, kq, wq, R, tswitch, G->partial);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 int hmg_sigma2_prepared(hmg_ctx* c, int nz, int nm, int nq, const double* PT, const double* kq,
                         const double* wq, const double* R, double tswitch, double* out) {
     REQUIRE(c && PT && kq && wq && R && out, "NULL argument");
     REQUIRE(nz > 0 && nm > 0 && nq > 0, "empty grid");
-    const int nseg = (nq + SIG_SEG_LEN - 1) / SIG_SEG_LEN;
-    const int ztile = sigma2_ztile(nz), nzp = sigma2_nzp(nz);
-    if (ensure_scratch(c, 4, (size_t)nseg * nz * nm * 8)) return 1;
-    double* partial = (double*)c->scratch[4];
-    dim3 grid((nm + 15) / 16, nseg, nzp / ztile);
-    REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large");
-    if (ztile == 32)
-        hipLaunchKernelGGL(sigma2_mfma_kernel<2>, grid, dim3(64), 0, c->stream, nz, nzp, nm, nq,
-                           PT, kq, wq, R, tswitch, partial);
-    else
-        hipLaunchKernelGGL(sigma2_mfma_kernel<1>, grid, dim3(64), 0, c->stream, nz, nzp, nm, nq,
-                           PT, kq, wq, R, tswitch, partial);
-    HIP_TRY(hipGetLastError());
+    SigmaFrontArgs G;
+    if (sigma2_first_stage(c, nz, nm, nq, PT, kq, wq, R, tswitch, &G)) return 1;
     hipLaunchKernelGGL(sigma2_combine_kernel, grid1d((size_t)nz * nm, 64), dim3(256), 0, c->stream,
-                       nz * nm, nseg, (const double*)partial, out);
+                       nz * nm, G.nseg, (const double*)G.partial, out);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-// first stage of the contraction for hmg_sigma2_massfn / hmg_sigma2_massfn_halo: launches the matrix-core
-// kernel, returns the partial sums' buffer and the number of k' segments
-static int sigma2_partials(hmg_ctx* c, int nz, int nm, int nq, const double* PT, const double* kq, const double* wq,
-                           const double* R, double tswitch, const double** partial_out, int* nseg_out) {
-    const int nseg = (nq + SIG_SEG_LEN - 1) / SIG_SEG_LEN;
-    const int ztile = sigma2_ztile(nz), nzp = sigma2_nzp(nz);
-    if (ensure_scratch(c, 4, (size_t)nseg * nz * nm * 8)) return 1;
-    double* partial = (double*)c->scratch[4];
-    dim3 grid((nm + 15) / 16, nseg, nzp / ztile);
-    REQUIRE(grid.y <= 65535 && grid.z <= 65535, "grid too large");
-    if (ztile == 32)
-        hipLaunchKernelGGL(sigma2_mfma_kernel<2>, grid, dim3(64), 0, c->stream, nz, nzp, nm, nq,
-                           PT, kq, wq, R, tswitch, partial);
-    else
-        hipLaunchKernelGGL(sigma2_mfma_kernel<1>, grid, dim3(64), 0, c->stream, nz, nzp, nm, nq,
-                           PT, kq, wq, R, tswitch, partial);
-    HIP_TRY(hipGetLastError());
-    c->sig_nz = nz; c->sig_nm = nm; c->sig_nq = nq;
-    *partial_out = partial;
-    *nseg_out = nseg;
-    return 0;
-}
-static int sigma2_massfn_check(hmg_ctx* c, int nz, int nm, int nq, const double* PT, const double* kq,
-                               const double* wq, const double* R, const hmg_massfn_params* p, const double* ms,
-                               const double* lnms, const double* tz, double* sigma2, double* nzm, double* bh) {
-    REQUIRE(c && PT && kq && wq && R && p && ms && lnms && sigma2 && nzm && bh, "NULL argument");
-    REQUIRE(nz > 0 && nm > 0 && nq > 0, "empty grid");
+// the mass function's parameters as the kernels take them
+static int massfn_dev(const hmg_massfn_params* p, const double* tz, MassFnDev* P) {
     REQUIRE(p->mode == HMG_MF_SHETH_TORMEN || p->mode == HMG_MF_TINKER10, "unknown mass function");
     REQUIRE(p->mode != HMG_MF_TINKER10 || tz, "Tinker mode needs d_tinker_z");
-    REQUIRE(nz <= 65535, "nz too large");
-    return 0;
-}
-int hmg_sigma2_massfn(hmg_ctx* c, int nz, int nm, int nq, const double* PT, const double* kq, const double* wq,
-                      const double* R, double tswitch, const hmg_massfn_params* p, const double* ms,
-                      const double* lnms, const double* tz, double* sigma2, double* nzm, double* bh) {
-    if (sigma2_massfn_check(c, nz, nm, nq, PT, kq, wq, R, p, ms, lnms, tz, sigma2, nzm, bh)) return 1;
-    const double* partial;
-    int nseg;
-    if (sigma2_partials(c, nz, nm, nq, PT, kq, wq, R, tswitch, &partial, &nseg)) return 1;
-    MassFnDev P{p->mode, p->deltac, p->st_A, p->st_a, p->st_p, p->rho_m0, p->lnm_uniform, p->lnm_step};
-    SigmaMassFnArgs A{nz, nm, nseg, P, partial, ms, lnms, tz, sigma2, nzm, bh};
-    hipLaunchKernelGGL(sigma2_massfn_kernel, dim3((nm + 63) / 64, nz), dim3(512), 0, c->stream, A);
-    HIP_TRY(hipGetLastError());
+    *P = MassFnDev{p->mode, p->deltac, p->st_A, p->st_a, p->st_p, p->rho_m0, p->lnm_uniform, p->lnm_step};
     return 0;
 }
 static int halo_stage_check(hmg_ctx* c, int nz, int nm, const double* ms, const hmg_halo_stage_args* h,
@@ -136,18 +115,39 @@ static int halo_stage_check(hmg_ctx* c, int nz, int nm, const double* ms, const 
                        h->d_r2};
     return 0;
 }
+// hmg_sigma2_massfn / hmg_sigma2_massfn_halo: the checks, the first stage, and the arguments of the second
+static int sigma2_massfn_setup(hmg_ctx* c, int nz, int nm, int nq, const double* PT, const double* kq,
+                               const double* wq, const double* R, double tswitch, const hmg_massfn_params* p,
+                               const double* ms, const double* lnms, const double* tz, double* sigma2, double* nzm,
+                               double* bh, const hmg_halo_stage_args* h, HaloStageArgs* H, SigmaMassFnArgs* A) {
+    REQUIRE(c && PT && kq && wq && R && p && ms && lnms && sigma2 && nzm && bh, "NULL argument");
+    REQUIRE(nz > 0 && nm > 0 && nq > 0, "empty grid");
+    MassFnDev P;
+    if (massfn_dev(p, tz, &P)) return 1;
+    REQUIRE(nz <= 65535, "nz too large");
+    if (H && halo_stage_check(c, nz, nm, ms, h, H)) return 1;
+    SigmaFrontArgs G;
+    if (sigma2_first_stage(c, nz, nm, nq, PT, kq, wq, R, tswitch, &G)) return 1;
+    *A = SigmaMassFnArgs{nz, nm, G.nseg, P, G.partial, ms, lnms, tz, sigma2, nzm, bh};
+    return 0;
+}
+int hmg_sigma2_massfn(hmg_ctx* c, int nz, int nm, int nq, const double* PT, const double* kq, const double* wq,
+                      const double* R, double tswitch, const hmg_massfn_params* p, const double* ms,
+                      const double* lnms, const double* tz, double* sigma2, double* nzm, double* bh) {
+    SigmaMassFnArgs A;
+    if (sigma2_massfn_setup(c, nz, nm, nq, PT, kq, wq, R, tswitch, p, ms, lnms, tz, sigma2, nzm, bh, nullptr, nullptr, &A))
+        return 1;
+    hipLaunchKernelGGL(sigma2_massfn_kernel, dim3((nm + 63) / 64, nz), dim3(512), 0, c->stream, A);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 int hmg_sigma2_massfn_halo(hmg_ctx* c, int nz, int nm, int nq, const double* PT, const double* kq,
                            const double* wq, const double* R, double tswitch, const hmg_massfn_params* p,
                            const double* ms, const double* lnms, const double* tz, double* sigma2, double* nzm,
                            double* bh, const hmg_halo_stage_args* h) {
-    if (sigma2_massfn_check(c, nz, nm, nq, PT, kq, wq, R, p, ms, lnms, tz, sigma2, nzm, bh)) return 1;
+    SigmaMassFnArgs A;
     HaloStageArgs H;
-    if (halo_stage_check(c, nz, nm, ms, h, &H)) return 1;
-    const double* partial;
-    int nseg;
-    if (sigma2_partials(c, nz, nm, nq, PT, kq, wq, R, tswitch, &partial, &nseg)) return 1;
-    MassFnDev P{p->mode, p->deltac, p->st_A, p->st_a, p->st_p, p->rho_m0, p->lnm_uniform, p->lnm_step};
-    SigmaMassFnArgs A{nz, nm, nseg, P, partial, ms, lnms, tz, sigma2, nzm, bh};
+    if (sigma2_massfn_setup(c, nz, nm, nq, PT, kq, wq, R, tswitch, p, ms, lnms, tz, sigma2, nzm, bh, h, &H, &A)) return 1;
     hipLaunchKernelGGL(ctor_stage_kernel, dim3((nm + 63) / 64, nz, 2), dim3(512), 0, c->stream, A, H);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -167,9 +167,8 @@ int hmg_massfn(hmg_ctx* c, int nz, int nm, const hmg_massfn_params* p, const dou
                const double* ms, const double* lnms, const double* tz, double* nzm, double* bh) {
     REQUIRE(c && p && s2 && ms && lnms && nzm && bh, "NULL argument");
     REQUIRE(nz > 0 && nm > 0, "empty grid");
-    REQUIRE(p->mode == HMG_MF_SHETH_TORMEN || p->mode == HMG_MF_TINKER10, "unknown mass function");
-    REQUIRE(p->mode != HMG_MF_TINKER10 || tz, "Tinker mode needs d_tinker_z");
-    MassFnDev P{p->mode, p->deltac, p->st_A, p->st_a, p->st_p, p->rho_m0, p->lnm_uniform, p->lnm_step};
+    MassFnDev P;
+    if (massfn_dev(p, tz, &P)) return 1;
     hipLaunchKernelGGL(massfn_kernel, grid1d((size_t)nz * nm, 256), dim3(256), 0, c->stream, nz, nm,
                        P, s2, ms, lnms, tz, nzm, bh);
     HIP_TRY(hipGetLastError());
@@ -240,6 +239,13 @@ int hmg_nfw_analytic(hmg_ctx* c, int nz, int nm, int nk, const double* cs, const
     return 0;
 }
 
+// the fit of a Battaglia family as the row kernels take it, for a kind they know and with what that kind needs
+static int row_fit(int kind, const double* hz, const double* post, const double f[9], RowFit* F) {
+    REQUIRE(kind == HMG_PROF_BATTAGLIA_GAS || kind == HMG_PROF_BATTAGLIA_PRES, "unknown profile kind");
+    REQUIRE(kind != HMG_PROF_BATTAGLIA_PRES || (hz && post), "pressure needs d_hz and d_post");
+    for (int i = 0; i < 9; ++i) F->f[i] = f[i];
+    return 0;
+}
 int hmg_profile_rowparams(hmg_ctx* c, int kind, int nz, int nm, const double* m200, const double* r200,
                           const double* rvir, const double* zs, const double* rhoc, const double* hz,
                           const double f[9], double gamma, double alpha_const, double pref,
@@ -247,11 +253,9 @@ int hmg_profile_rowparams(hmg_ctx* c, int kind, int nz, int nm, const double* m2
                           double* cmax, double* rscale, double* post) {
     REQUIRE(c && m200 && r200 && rvir && zs && rhoc && f && amp && xc && alpha && expo && cmax && rscale,
             "NULL argument");
-    REQUIRE(kind == HMG_PROF_BATTAGLIA_GAS || kind == HMG_PROF_BATTAGLIA_PRES, "unknown profile kind");
-    REQUIRE(kind != HMG_PROF_BATTAGLIA_PRES || (hz && post), "pressure needs d_hz and d_post");
-    REQUIRE(nz > 0 && nm > 0, "empty grid");
     RowFit F;
-    for (int i = 0; i < 9; ++i) F.f[i] = f[i];
+    if (row_fit(kind, hz, post, f, &F)) return 1;
+    REQUIRE(nz > 0 && nm > 0, "empty grid");
     RowOut O{amp, xc, alpha, expo, cmax, rscale, post};
     hipLaunchKernelGGL(rowparams_kernel, grid1d((size_t)nz * nm, 128), dim3(128), 0, c->stream, kind,
                        nz, nm, m200, r200, rvir, zs, rhoc, hz, F, gamma, alpha_const, pref, post_pref, O);
@@ -267,11 +271,9 @@ int hmg_profile_rows_from_mvir(hmg_ctx* c, int kind, int nz, int nm, const doubl
                                double* cmax, double* rscale, double* post) {
     REQUIRE(c && ms && cs && rvir && zs && drho1 && rhoc && f && m200 && r200 && amp && xc && alpha && expo &&
                 cmax && rscale, "NULL argument");
-    REQUIRE(kind == HMG_PROF_BATTAGLIA_GAS || kind == HMG_PROF_BATTAGLIA_PRES, "unknown profile kind");
-    REQUIRE(kind != HMG_PROF_BATTAGLIA_PRES || (hz && post), "pressure needs d_hz and d_post");
-    REQUIRE(nz > 0 && nm > 0, "empty grid");
     RowFit F;
-    for (int i = 0; i < 9; ++i) F.f[i] = f[i];
+    if (row_fit(kind, hz, post, f, &F)) return 1;
+    REQUIRE(nz > 0 && nm > 0, "empty grid");
     RowOut O{amp, xc, alpha, expo, cmax, rscale, post};
     hipLaunchKernelGGL(rows_from_mvir_kernel, grid1d((size_t)nz * nm, 128), dim3(128), 0, c->stream, kind,
                        nz, nm, ms, cs, rvir, zs, drho1, delta2, rhoc, hz, F, gamma, alpha_const, pref,
@@ -299,6 +301,31 @@ static int get_plan(hmg_ctx* c, int nxs, int batch, FftPlan** out) {
     FFT_TRY(rocfft_execution_info_set_stream(P.info, c->stream));
     auto res = c->plans.emplace(key, P);
     *out = &res.first->second;
+    return 0;
+}
+
+template <class T>
+static int upload_table(const std::vector<T>& h, T** d) {
+    HIP_TRY(hipMalloc((void**)d, h.size() * sizeof(T)));
+    HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// rocFFT route (the profile transform's fallback and hmg_sine_transform).  Rows per chunk: integrand + spectrum of a
+// chunk stay inside the 256 MiB Infinity Cache (budget: 160 MiB unless the context says otherwise), so the R2C input and
+// the spectrum never round-trip through HBM, and the work buffers stay bounded.
+static int fft_chunk(size_t budget, size_t per_row, int rows) {
+    const size_t chunk = budget / per_row;
+    return chunk < 1 ? 1 : (chunk > (size_t)rows ? rows : (int)chunk);
+}
+// nr real-to-complex transforms of length n on the context's stream
+static int fft_r2c(hmg_ctx* c, int n, int nr, double* in, double2* out) {
+    FftPlan* P = nullptr;
+    if (get_plan(c, n, nr, &P)) return 1;
+    void* ib[1] = {in};
+    void* ob[1] = {out};
+    FFT_TRY(rocfft_execution_info_set_stream(P->info, c->stream));
+    FFT_TRY(rocfft_execute(P->plan, ib, ob, P->info));
     return 0;
 }
 
@@ -335,15 +362,7 @@ static int get_fused_plan(hmg_ctx* c, int nxs, FusedPlan** out) {
     }
     // twiddles per pass (ldsfft.hpp: pass_tw_table): element k of a pass's slice is W_M^(k twstep), so that
     // consecutive butterflies read consecutive elements instead of gathering at a stride of twstep from one table
-    const std::vector<cplx> twM = pass_tw_table(P.plan);
-    std::vector<UnpackTw> twN(M / 2 + 1);
-    const long double twopi = 6.283185307179586476925286766559L;
-    for (int j = 0; j <= M / 2; ++j)
-        twN[j] = UnpackTw{(double)cosl(twopi * j / nxs), (double)sinl(twopi * j / nxs), j ? 1.0 / j : 0.0, 1.0 / (M - j)};
-    HIP_TRY(hipMalloc((void**)&P.twM, twM.size() * sizeof(cplx)));
-    HIP_TRY(hipMalloc((void**)&P.twN, twN.size() * sizeof(UnpackTw)));
-    HIP_TRY(hipMemcpy(P.twM, twM.data(), twM.size() * sizeof(cplx), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(P.twN, twN.data(), twN.size() * sizeof(UnpackTw), hipMemcpyHostToDevice));
+    if (upload_table(pass_tw_table(P.plan), &P.twM) || upload_table(unpack_tw_table(nxs), &P.twN)) return 1;
     auto res = c->fused.emplace(nxs, P);
     *out = &res.first->second;
     return 0;
@@ -502,13 +521,6 @@ static int launch_group(hmg_ctx* c, const FusedArgs& A, int rows, const FftRider
 // and covers the support bound of its rows.
 static const int PRUNED_LP[] = {1000, 1024, 1250, 1500, 2000, 2048, 2500};
 
-template <class T>
-static int upload_table(const std::vector<T>& h, T** d) {
-    HIP_TRY(hipMalloc((void**)d, h.size() * sizeof(T)));
-    HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-}
-
 // LP == 0: the tables by mode (chirp and narrow-band routes); LP > 0: the decomposition's tables by residue
 static int get_pruned_plan(hmg_ctx* c, int nxs, int LP, PrunedPlan** out) {
     const auto key = std::make_pair(nxs, LP);
@@ -519,12 +531,9 @@ static int get_pruned_plan(hmg_ctx* c, int nxs, int LP, PrunedPlan** out) {
     PrunedPlan P;
     if (LP == 0) {
         std::vector<cplx> twB(M);
-        std::vector<UnpackTw> twN(M / 2 + 1);
         const long double twopi = 6.283185307179586476925286766559L;
         for (int t = 0; t < M; ++t) twB[t] = cplx{(double)cosl(twopi * t / M), (double)-sinl(twopi * t / M)};
-        for (int j = 0; j <= M / 2; ++j)
-            twN[j] = UnpackTw{(double)cosl(twopi * j / nxs), (double)sinl(twopi * j / nxs), j ? 1.0 / j : 0.0, 1.0 / (M - j)};
-        if (upload_table(twB, &P.twB) || upload_table(twN, &P.twN)) return 1;
+        if (upload_table(twB, &P.twB) || upload_table(unpack_tw_table(nxs), &P.twN)) return 1;
     } else {
         if (upload_table(residue_tw_table(M, LP), &P.twR) || upload_table(residue_unpack_table(M, LP), &P.twNr)) return 1;
     }
@@ -556,12 +565,7 @@ static int get_chirp_plan(hmg_ctx* c, int nxs, int LP, int p0, ChirpPlan** out) 
     const ChirpTables T = chirp_make_tables(nxs / 2, 2 * LP, p0);
     ChirpPlan P;
     P.Jw = T.Jw;
-    HIP_TRY(hipMalloc((void**)&P.chP, T.chP.size() * sizeof(cplx)));
-    HIP_TRY(hipMalloc((void**)&P.chJ, T.chJ.size() * sizeof(cplx)));
-    HIP_TRY(hipMalloc((void**)&P.Bw, T.Bw.size() * sizeof(cplx)));
-    HIP_TRY(hipMemcpy(P.chP, T.chP.data(), T.chP.size() * sizeof(cplx), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(P.chJ, T.chJ.data(), T.chJ.size() * sizeof(cplx), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(P.Bw, T.Bw.data(), T.Bw.size() * sizeof(cplx), hipMemcpyHostToDevice));
+    if (upload_table(T.chP, &P.chP) || upload_table(T.chJ, &P.chJ) || upload_table(T.Bw, &P.Bw)) return 1;
     auto res = c->chirp.emplace(key, P);
     *out = &res.first->second;
     return 0;
@@ -751,13 +755,9 @@ static int profile_fft_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_profil
         R.nfw_done = r.grouped && R.N;
         return bracket_close(c, stop);
     }
-    // ---- rocFFT path.  Chunk the batch so integrand + spectrum of a chunk stay inside the 256 MiB Infinity Cache:
-    // the R2C input written by K4 and the spectrum read by K5 then never round-trip through HBM.
-    const size_t per_row = (size_t)nxs * 8 + (size_t)(nh + 1) * 16;
-    size_t budget = c->fft_chunk_bytes ? c->fft_chunk_bytes : ((size_t)160 << 20);
-    int chunk = (int)(budget / per_row);
-    if (chunk < 1) chunk = 1;
-    if (chunk > rows) chunk = rows;
+    // ---- rocFFT path, in chunks of the batch (fft_chunk)
+    const int chunk = fft_chunk(c->fft_chunk_bytes ? c->fft_chunk_bytes : ((size_t)160 << 20),
+                                (size_t)nxs * 8 + (size_t)(nh + 1) * 16, rows);
     if (ensure_scratch(c, 0, (size_t)chunk * nxs * 8)) return 1;
     if (ensure_scratch(c, 1, (size_t)chunk * (nh + 1) * 16)) return 1;
     if (ensure_scratch(c, 2, (size_t)chunk * 8)) return 1;
@@ -778,12 +778,7 @@ static int profile_fft_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_profil
                                p.d_alpha, p.d_expo, p.amp_const, p.xc_const, p.alpha_const, p.expo_const, p.gamma, cmax,
                                p.do_mass_norm, (int)r.xs_aligned, fin, mnorm);
         HIP_TRY(hipGetLastError());
-        FftPlan* P = nullptr;
-        if (get_plan(c, nxs, nr, &P)) return 1;
-        void* ib[1] = {fin};
-        void* ob[1] = {fout};
-        FFT_TRY(rocfft_execution_info_set_stream(P->info, c->stream));
-        FFT_TRY(rocfft_execute(P->plan, ib, ob, P->info));
+        if (fft_r2c(c, nxs, nr, fin, fout)) return 1;
         if (stage)
             hipLaunchKernelGGL(interp_kernel<true>, dim3(nr), dim3(256), lds, c->stream, nm, nk, nh, r0, step,
                                (const double2*)fout, kts, mnorm, rss, zs, ks, p.d_post, p.d_out, p.d_nconst, p.d_cconst);
@@ -870,19 +865,25 @@ int hmg_profile_fft_logx(hmg_ctx* c, int nxs, const double* xs, double* logxs) {
     return 0;
 }
 
+// the HOD's parameters as the kernels take them, for a mass grid their reduction over m can take
+static int hod_dev(int nm, const hmg_hod_params* p, HodDev* P) {
+    REQUIRE(p->corr == 0 || p->corr == 1, "corr must be 0 (max) or 1 (min)");
+    REQUIRE((nm + 63) / 64 <= HOD_MAX_TILES, "nm too large for the HOD reduction (65536)");
+    *P = HodDev{p->sig_log_mstellar, p->alphasat, p->Bsat, p->betasat, p->Bcut, p->betacut, p->corr};
+    return 0;
+}
+
 int hmg_hod(hmg_ctx* c, int nz, int nm, const hmg_hod_params* p, const double* zs, const double* ms,
             const double* lthr, const double* nzm, const double* bh, const double* wm, double* Nc,
             double* Ns, double* NsNsm1, double* NcNs, double* ngal, double* bg) {
     REQUIRE(c && p && zs && ms && lthr && nzm && bh && wm && Nc && Ns && NsNsm1 && NcNs && ngal && bg,
             "NULL argument");
     REQUIRE(nz > 0 && nm > 0, "empty grid");
-    REQUIRE(p->corr == 0 || p->corr == 1, "corr must be 0 (max) or 1 (min)");
-    HodDev P{p->sig_log_mstellar, p->alphasat, p->Bsat, p->betasat, p->Bcut, p->betacut, p->corr};
-    int hod_threads = 1024;
+    HodDev P;
+    if (hod_dev(nm, p, &P)) return 1;
+    int hod_threads = std::min(1024, std::max(64, (nm + 63) / 64 * 64));
     if (const char* e = getenv("HMG_HOD_THREADS")) hod_threads = atoi(e);
     REQUIRE(hod_threads >= 64 && hod_threads <= 1024 && hod_threads % 64 == 0, "HMG_HOD_THREADS must be a multiple of 64 up to 1024");
-    REQUIRE((nm + 63) / 64 <= HOD_MAX_TILES, "nm too large for the HOD reduction (65536)");
-    if (!getenv("HMG_HOD_THREADS")) hod_threads = std::min(1024, std::max(64, (nm + 63) / 64 * 64));
     const HodRowArgs A{nm, P, zs, ms, lthr, nzm, bh, wm, Nc, Ns, NsNsm1, NcNs, ngal, bg};
     hipLaunchKernelGGL(hod_kernel, dim3(nz), dim3(hod_threads), 0, c->stream, A);
     HIP_TRY(hipGetLastError());
@@ -951,12 +952,8 @@ static int power_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_tracer* ta, 
     A.kstar = kstar; A.nm = nm; A.nk = nk;
     bool vec2 = (nk % 2 == 0);
     for (int i = 0; i < Q.nt; ++i) vec2 = vec2 && (((uintptr_t)tens[i]) % 16 == 0);
-    // enough waves to cover the chip: MS mass slices per block
-    const int V = vec2 ? 2 : 1;
-    const long blocks = (long)((nk + 64 * V - 1) / (64 * V)) * nz;
-    // the number of mass slices fixes the summation order over m: keep it a function of nm only,
+    // the number of mass slices per block fixes the summation order over m: keep it a function of nm only,
     // so that a z-slab run (multi-GPU) reproduces the full-grid numbers bit for bit
-    (void)blocks;
     int ms_split = 8;
     while (ms_split > 1 && ms_split > nm) ms_split >>= 1;
 #define PW_CASE(NT_)                                                      \
@@ -1184,12 +1181,10 @@ static int rows_setup(int nz, int nm, const hmg_rows_part* rows, RowsArgs* out) 
     RowsArgs Rw{};
     REQUIRE(rows->d_m200c && rows->d_r200c && rows->d_rvir && rows->d_zs && rows->d_rhocz && rows->d_amp && rows->d_xc &&
                 rows->d_alpha && rows->d_expo && rows->d_cmax && rows->d_rscale, "NULL argument in the rows part");
-    REQUIRE(rows->kind == HMG_PROF_BATTAGLIA_GAS || rows->kind == HMG_PROF_BATTAGLIA_PRES, "unknown profile kind");
-    REQUIRE(rows->kind != HMG_PROF_BATTAGLIA_PRES || (rows->d_hz && rows->d_post), "pressure needs d_hz and d_post");
+    if (row_fit(rows->kind, rows->d_hz, rows->d_post, rows->fit, &Rw.F)) return 1;
     Rw.n = nz * nm; Rw.kind = rows->kind; Rw.nm = nm;
     Rw.m200 = rows->d_m200c; Rw.r200 = rows->d_r200c; Rw.rvir = rows->d_rvir; Rw.zs = rows->d_zs;
     Rw.rhoc = rows->d_rhocz; Rw.hz = rows->d_hz;
-    for (int i = 0; i < 9; ++i) Rw.F.f[i] = rows->fit[i];
     Rw.gamma = rows->gamma; Rw.alpha_const = rows->alpha_const; Rw.pref = rows->amp_prefactor;
     Rw.post_pref = rows->post_prefactor;
     Rw.O = RowOut{rows->d_amp, rows->d_xc, rows->d_alpha, rows->d_expo, rows->d_cmax, rows->d_rscale, rows->d_post};
@@ -1207,9 +1202,8 @@ static int hod_args(int nm, const hmg_hod_part* hod, HodRowArgs* A) {
                 hod->d_NcNs, "NULL argument in the HOD part");
     REQUIRE(hod->stage == HMG_HOD_OCCUPATIONS || (hod->d_nzm && hod->d_bh && hod->d_wm && hod->d_ngal && hod->d_bg),
             "NULL argument in the HOD part");
-    REQUIRE(p->corr == 0 || p->corr == 1, "corr must be 0 (max) or 1 (min)");
-    REQUIRE((nm + 63) / 64 <= HOD_MAX_TILES, "nm too large for the HOD reduction (65536)");
-    const HodDev P{p->sig_log_mstellar, p->alphasat, p->Bsat, p->betasat, p->Bcut, p->betacut, p->corr};
+    HodDev P;
+    if (hod_dev(nm, p, &P)) return 1;
     *A = HodRowArgs{nm, P, hod->d_zs, hod->d_ms, hod->d_log10mstar_thresh, hod->d_nzm, hod->d_bh, hod->d_wm,
                     hod->d_Nc, hod->d_Ns, hod->d_NsNsm1, hod->d_NcNs, hod->d_ngal, hod->d_bg};
     return 0;
@@ -1235,21 +1229,16 @@ int hmg_sigma2_halo_front(hmg_ctx* c, int nz, int nm, int nq, const double* PT, 
         REQUIRE(h->d_m2 && rows->d_m200c == h->d_m2 && rows->d_r200c == h->d_r2 && rows->d_rvir == h->d_rvir,
                 "row parameters in the front launch take M_200c, R_200c, r_vir from the halo stage of the same call");
     }
-    const int nseg = (nq + SIG_SEG_LEN - 1) / SIG_SEG_LEN;
-    const int ztile = sigma2_ztile(nz), nzp = sigma2_nzp(nz);
-    if (ensure_scratch(c, 4, (size_t)nseg * nz * nm * 8)) return 1;
-    const int gx = (nm + 15) / 16;
-    const size_t nsig = (size_t)gx * nseg * (nzp / ztile);
     const int nhalo = (nz * nm + 63) / 64;
-    REQUIRE(nsig + nhalo + nocc <= 2147483647u, "grid too large");
-    const SigmaFrontArgs G{nz, nzp, nm, nq, gx, nseg, PT, kq, wq, R, tswitch, (double*)c->scratch[4]};
-    const dim3 grid((unsigned)(nsig + nhalo + nocc));
-    if (ztile == 32)
+    SigmaFrontArgs G;
+    dim3 sig;
+    if (sigma2_setup(c, nz, nm, nq, PT, kq, wq, R, tswitch, (size_t)nhalo + nocc, &G, &sig)) return 1;
+    const dim3 grid((unsigned)((size_t)sig.x * sig.y * sig.z + nhalo + nocc));
+    if (sigma2_ztile(nz) == 32)
         hipLaunchKernelGGL(front_group_kernel<2>, grid, dim3(64), 0, c->stream, G, H, nhalo, O, nocc, Rw);
     else
         hipLaunchKernelGGL(front_group_kernel<1>, grid, dim3(64), 0, c->stream, G, H, nhalo, O, nocc, Rw);
     HIP_TRY(hipGetLastError());
-    c->sig_nz = nz; c->sig_nm = nm; c->sig_nq = nq;
     return 0;
 }
 
@@ -1271,14 +1260,22 @@ static int chain_setup(int nm, const hmg_hod_part* hod, const PbPlan* prep, Chai
 static int massfn_setup(hmg_ctx* c, int nz, int nm, int nq, const hmg_massfn_part* mf, SigmaMassFnArgs* S) {
     const hmg_massfn_params* p = mf->h_par;
     REQUIRE(p && mf->d_ms && mf->d_lnms && mf->d_sigma2 && mf->d_nzm && mf->d_bh, "NULL argument in the massfn part");
-    REQUIRE(p->mode == HMG_MF_SHETH_TORMEN || p->mode == HMG_MF_TINKER10, "unknown mass function");
-    REQUIRE(p->mode != HMG_MF_TINKER10 || mf->d_tinker_z, "Tinker mode needs d_tinker_z");
+    MassFnDev P;
+    if (massfn_dev(p, mf->d_tinker_z, &P)) return 1;
     REQUIRE(c->sig_nz == nz && c->sig_nm == nm && c->sig_nq == nq && c->scratch[4],
             "no sigma^2 partial sums of this shape in the context: call hmg_sigma2_halo_front first");
     const int nseg = (nq + SIG_SEG_LEN - 1) / SIG_SEG_LEN;
-    const MassFnDev P{p->mode, p->deltac, p->st_A, p->st_a, p->st_p, p->rho_m0, p->lnm_uniform, p->lnm_step};
     *S = SigmaMassFnArgs{nz, nm, nseg, P, (const double*)c->scratch[4], mf->d_ms, mf->d_lnms, mf->d_tinker_z,
                          mf->d_sigma2, mf->d_nzm, mf->d_bh};
+    return 0;
+}
+
+// the analytic NFW rows of a grouped launch: *blocks workgroups of one 4096-k tile each (hmg_nfw_analytic's default)
+static int nfw_setup(hmg_ctx* c, int nz, int nm, int nk, const hmg_nfw_part* nfw, NfwArgs* N, size_t* blocks) {
+    REQUIRE(nfw->d_cs && nfw->d_rs && nfw->d_zs && nfw->d_ks && nfw->d_nfw_series && nfw->d_uk, "NULL argument in the NFW part");
+    const int ktile = 4096;
+    *blocks = (size_t)nz * nm * ((nk + ktile - 1) / ktile);
+    *N = NfwArgs{c->d_sici, nfw->d_nfw_series, ktile, nm, nk, nfw->d_cs, nfw->d_rs, nfw->d_zs, nfw->d_ks, nfw->d_uk};
     return 0;
 }
 
@@ -1320,10 +1317,7 @@ int hmg_group_rows(hmg_ctx* c, int nz, int nm, int nk, int nq, const hmg_massfn_
     int stop = -1;
     if (nfw) {
         REQUIRE(nk > 0, "empty grid");
-        REQUIRE(nfw->d_cs && nfw->d_rs && nfw->d_zs && nfw->d_ks && nfw->d_nfw_series && nfw->d_uk, "NULL argument in the NFW part");
-        const int ktile = 4096;
-        nfw_blocks = (size_t)nz * nm * ((nk + ktile - 1) / ktile);
-        N = NfwArgs{c->d_sici, nfw->d_nfw_series, ktile, nm, nk, nfw->d_cs, nfw->d_rs, nfw->d_zs, nfw->d_ks, nfw->d_uk};
+        if (nfw_setup(c, nz, nm, nk, nfw, &N, &nfw_blocks)) return 1;
         if (bracket_open(c, HMG_KERNEL_NFW, &stop)) return 1;
     }
     if (launch_rows_group(c, nz, nm, C, one ? nz : 0, mf ? &S : nullptr, Rw, nfw ? &N : nullptr, nfw_blocks)) return 1;
@@ -1393,12 +1387,7 @@ int hmg_group_tensors(hmg_ctx* c, int nz, int nm, int nk, int nq, const hmg_mass
     }
     NfwArgs N{};
     size_t nfw_blocks = 0;
-    if (nfw) {
-        REQUIRE(nfw->d_cs && nfw->d_rs && nfw->d_zs && nfw->d_ks && nfw->d_nfw_series && nfw->d_uk, "NULL argument in the NFW part");
-        const int ktile = 4096;
-        nfw_blocks = (size_t)nz * nm * ((nk + ktile - 1) / ktile);
-        N = NfwArgs{c->d_sici, nfw->d_nfw_series, ktile, nm, nk, nfw->d_cs, nfw->d_rs, nfw->d_zs, nfw->d_ks, nfw->d_uk};
-    }
+    if (nfw && nfw_setup(c, nz, nm, nk, nfw, &N, &nfw_blocks)) return 1;
     bool nfw_done = false;
     if (profile_group_launches(c, nz, nm, nk, fft, C, one, prep, P, nfw ? &N : nullptr, nfw_blocks, &nfw_done)) return 1;
     REQUIRE(!nfw || nfw_done, "internal: the transform did not take the route the tensor group was set up for");
@@ -1470,10 +1459,7 @@ int hmg_sine_transform(hmg_ctx* c, int rows, int n, const double* x, const doubl
     REQUIRE(c && x && y && uk, "NULL argument");
     REQUIRE(rows > 0 && n >= 2, "bad sizes");
     const int nh1 = n / 2 + 1;
-    // chunk the batch like the profile path so the work buffers stay bounded
-    int chunk = (int)(((size_t)160 << 20) / ((size_t)n * 8 + (size_t)nh1 * 16));
-    if (chunk < 1) chunk = 1;
-    if (chunk > rows) chunk = rows;
+    const int chunk = fft_chunk((size_t)160 << 20, (size_t)n * 8 + (size_t)nh1 * 16, rows);
     if (ensure_scratch(c, 0, (size_t)chunk * n * 8)) return 1;
     if (ensure_scratch(c, 1, (size_t)chunk * nh1 * 16)) return 1;
     double* fin = (double*)c->scratch[0];
@@ -1489,12 +1475,7 @@ int hmg_sine_transform(hmg_ctx* c, int rows, int n, const double* x, const doubl
         hipLaunchKernelGGL(xy_kernel, grid1d((size_t)nr * n, 256), dim3(256), 0, c->stream, nr, n, x,
                            y + (size_t)r0 * n, fin);
         HIP_TRY(hipGetLastError());
-        FftPlan* P = nullptr;
-        if (get_plan(c, n, nr, &P)) return 1;
-        void* ib[1] = {fin};
-        void* ob[1] = {fout};
-        FFT_TRY(rocfft_execution_info_set_stream(P->info, c->stream));
-        FFT_TRY(rocfft_execute(P->plan, ib, ob, P->info));
+        if (fft_r2c(c, n, nr, fin, fout)) return 1;
         hipLaunchKernelGGL(neg_imag_kernel, grid1d((size_t)nr * nh1, 256), dim3(256), 0, c->stream,
                            (size_t)nr * nh1, step, (const double2*)fout, uk + (size_t)r0 * nh1);
         HIP_TRY(hipGetLastError());

@@ -407,6 +407,15 @@ HMG_HD void pruned_unpack(const cplx* buf, int LP, int R, int M, int s, int ob, 
         if (hi && M - pr.j >= 1) um[pr.qp] = fb * sc * w.rmj;
     }
 }
+// unpack constants by mode j <= M/2 of a real transform of length nxs = 2 M (one row in LDS; chirp and narrow-band routes)
+inline std::vector<UnpackTw> unpack_tw_table(int nxs) {
+    const int M = nxs / 2;
+    std::vector<UnpackTw> t(M / 2 + 1);
+    const long double twopi = 6.283185307179586476925286766559L;
+    for (int j = 0; j <= M / 2; ++j)
+        t[j] = UnpackTw{(double)cosl(twopi * j / nxs), (double)sinl(twopi * j / nxs), j ? 1.0 / j : 0.0, 1.0 / (M - j)};
+    return t;
+}
 inline std::vector<UnpackTw> residue_unpack_table(int M, int LP) {
     const int R = M / LP, QS = pruned_qs(LP), n = 2 * M;
     std::vector<UnpackTw> t((size_t)R * QS, UnpackTw{1.0, 0.0, 0.0, 0.0});

@@ -10,6 +10,7 @@ array, ``hods`` maps name -> dict, plus ``sigma2``, ``nzm``, ``bh``, ``Pzk``.  R
 those return numpy arrays (copied from the device on first access, then cached);
 assigning a numpy array to ``uk_profiles[name]`` uploads it.
 """
+import contextlib
 import ctypes as C
 import itertools
 import os
@@ -359,6 +360,26 @@ class HaloModel(Cosmology):
         self._stages.append((kind, part, keep))
         self._ctx().defer(self)
 
+    @contextlib.contextmanager
+    def _tagged(self, call):
+        """This model's support tag and deferral flag around ONE native call, issued with `call` (ctx.call_now or
+        ctx.call).  Both are context state: set right around the call they describe and restored whatever that call
+        does (a call that raises inside a capture must not leave this model's tag behind: ADVICE r05)."""
+        call("hmg_profile_support_epoch", getattr(self, "_epoch", 0))
+        call("hmg_prefix_deferral", int(self.prefix_deferral))
+        try:
+            yield
+        finally:
+            call("hmg_prefix_deferral", 0)
+            call("hmg_profile_support_epoch", 0)
+
+    def _ks_ascending(self):
+        """Is the target k grid ascending (the promise of the hint arrays and the row scalars)?  Cached per model."""
+        if "ks_ascending" not in self._dcache:
+            self._dcache["ks_ascending"] = (bool(np.all(np.diff(self.ks) > 0))
+                                            and os.environ.get("HMG_NO_HINTS", "0") != "1")   # debugging switch
+        return self._dcache["ks_ascending"]
+
     def _flush(self, prep=None):
         """Issue the queued stages as grouped launches: front (sigma^2 contraction | halo stage | HOD occupations |
         Battaglia row parameters: inputs only), then the tensor group (per-z chain: sigma^2 second stage + n, b -> HOD sums ->
@@ -394,14 +415,9 @@ class HaloModel(Cosmology):
                          h.d_Nc, h.d_Ns, h.d_NsNsm1, h.d_NcNs, h.d_ngal, h.d_bg)
         if "fft" in st and ("massfn" in st or "nfw" in st) and "rows" not in st and not x:
             # tensor group: chain (sigma^2 -> n, b -> HOD sums -> coefficient rows) | profile rows | NFW rows, one launch
-            ctx.call_now("hmg_profile_support_epoch", getattr(self, "_epoch", 0))
-            ctx.call_now("hmg_prefix_deferral", int(self.prefix_deferral))
-            try:
+            with self._tagged(ctx.call_now):
                 ctx.call_now("hmg_group_tensors", nz, nm, nk, nq, ref("massfn"), ref("hod") if hod_sums else None,
                              C.byref(prep) if prep is not None else None, ref("nfw"), ref("fft"))
-            finally:
-                ctx.call_now("hmg_prefix_deferral", 0)
-                ctx.call_now("hmg_profile_support_epoch", 0)
             return prep is not None
         nfw_alone = st.pop("nfw") if "nfw_alone" in x and "nfw" in st else None
         if any(k in st for k in ("massfn", "rows", "nfw")):
@@ -417,16 +433,9 @@ class HaloModel(Cosmology):
                              C.byref(prep) if prep is not None else None)
                 ctx.call_now("hmg_group_profile", nz, nm, nk, ref("fft"), None, None)
                 return prep is not None
-            # the support tag is context state: it is set right around the ONE call it describes and restored whatever
-            # that call does (a call that raises inside a capture must not leave this model's tag behind: ADVICE r05)
-            ctx.call_now("hmg_profile_support_epoch", getattr(self, "_epoch", 0))
-            ctx.call_now("hmg_prefix_deferral", int(self.prefix_deferral))       # (context state, like the tag)
-            try:
+            with self._tagged(ctx.call_now):
                 ctx.call_now("hmg_group_profile", nz, nm, nk, ref("fft"), ref("hod") if hod_sums else None,
                              C.byref(prep) if prep is not None else None)
-            finally:
-                ctx.call_now("hmg_prefix_deferral", 0)
-                ctx.call_now("hmg_profile_support_epoch", 0)
             return prep is not None
         return False
 
@@ -532,30 +541,26 @@ class HaloModel(Cosmology):
                     float(self.p["Wkr_taylor_switch"]), C.byref(par), d_ms.ptr, d_lnm.ptr, nat.ptr(d_tz),
                     self._d_sigma2.ptr, self._d_nzm.ptr, self._d_bh.ptr)
         duffy = tuple(float(self.p[f"duffy_{k}_{sfx}"]) for k in ("A", "alpha", "beta"))
+        halo_args = (self._d_zs().ptr, d_delta.ptr, d_rho.ptr, *duffy, float(self.h),
+                     self._d_cs.ptr, self._d_rvir.ptr, self._d_rs.ptr, self._d_nfw_series.ptr,
+                     d_drho1.ptr, 200.0, d_rhoc.ptr, m2.ptr, r2.ptr)
+        halo = nat.HaloStageArgs(*halo_args)
         if self._groups:
             # front group: the contraction beside the halo stage (both need inputs only); the second stage of
             # the contraction and n(z,m), b(z,m) are queued as the first link of the per-z chain
-            halo = nat.HaloStageArgs(self._d_zs().ptr, d_delta.ptr, d_rho.ptr, *duffy, float(self.h),
-                                     self._d_cs.ptr, self._d_rvir.ptr, self._d_rs.ptr, self._d_nfw_series.ptr,
-                                     d_drho1.ptr, 200.0, d_rhoc.ptr, m2.ptr, r2.ptr)
             self._nq = int(d_kq.size)
             self._queue("front", sig_args[:8] + (d_ms.ptr, halo))
             self._queue("massfn", nat.MassFnPart(C.pointer(par), d_ms.ptr, d_lnm.ptr, nat.ptr(d_tz), self._d_sigma2.ptr,
                                                  self._d_nzm.ptr, self._d_bh.ptr), keep=(par,))
         elif not self._use_lanes:
             # one launch behind the contraction: mass function and halo stage side by side
-            halo = nat.HaloStageArgs(self._d_zs().ptr, d_delta.ptr, d_rho.ptr, *duffy, float(self.h),
-                                     self._d_cs.ptr, self._d_rvir.ptr, self._d_rs.ptr, self._d_nfw_series.ptr,
-                                     d_drho1.ptr, 200.0, d_rhoc.ptr, m2.ptr, r2.ptr)
             ctx.call("hmg_sigma2_massfn_halo", *sig_args, C.byref(halo))
         else:
             # two-lane scheme: n, b on the auxiliary lane, the halo stage on the main lane ahead of the profiles
             ctx.call("hmg_sigma2_massfn", *sig_args)
             self._aux_done()
             ctx = self._main()
-            ctx.call("hmg_halo_stage", nz, nm, d_ms.ptr, self._d_zs().ptr, d_delta.ptr, d_rho.ptr,
-                     *duffy, float(self.h), self._d_cs.ptr, self._d_rvir.ptr, self._d_rs.ptr,
-                     self._d_nfw_series.ptr, d_drho1.ptr, 200.0, d_rhoc.ptr, m2.ptr, r2.ptr)
+            ctx.call("hmg_halo_stage", nz, nm, d_ms.ptr, *halo_args)
         self._m200c_valid = True
 
     def get_fsigmaz(self):
@@ -628,11 +633,8 @@ class HaloModel(Cosmology):
         nz, nm, nk = self._nz, self._nm, self._nk
         d_xs, d_kts, step, d_lx = self._fft_grids(xmax, nxs)
         out = self._buf(key, (nz, nm, nk))
-        if "ks_ascending" not in self._dcache:
-            self._dcache["ks_ascending"] = (bool(np.all(np.diff(self.ks) > 0))
-                                            and os.environ.get("HMG_NO_HINTS", "0") != "1")   # debugging switch
         hint = None
-        if self._dcache["ks_ascending"]:
+        if self._ks_ascending():
             # nconst is an int32 array: allocated as (nz*nm+1)//2 doubles, viewed as integers on read
             hint = (self._buf((key, "nconst"), ((nz * nm + 1) // 2,)), self._buf((key, "cconst"), (nz, nm)))
         amp, xc, alpha, expo = rowp
@@ -647,13 +649,8 @@ class HaloModel(Cosmology):
             self._queue("fft", nat.ProfileFftPart(*args, nat.ptr(d_rowsc if hint else None)))
         else:
             ctx.flush()          # deferred stages of ANY model on this context first: their own flush resets the tag
-            ctx.call("hmg_profile_support_epoch", getattr(self, "_epoch", 0))
-            ctx.call("hmg_prefix_deferral", int(self.prefix_deferral))
-            try:
+            with self._tagged(ctx.call):
                 ctx.call("hmg_profile_fft", nz, nm, nk, *args)
-            finally:
-                ctx.call("hmg_prefix_deferral", 0)
-                ctx.call("hmg_profile_support_epoch", 0)
         return out, hint
 
     def _battaglia_rowparams(self, key, kind, fit9, gamma, alpha_const, pref, post_pref, nxs=None, xmax=None):
@@ -679,10 +676,7 @@ class HaloModel(Cosmology):
         if self._groups:
             d_rowsc, extra = None, (None, None, 0, 0, None)
             if nxs is not None and nxs % 2 == 0 and os.environ.get("HMG_NO_ROWSC", "0") != "1":
-                if "ks_ascending" not in self._dcache:
-                    self._dcache["ks_ascending"] = (bool(np.all(np.diff(self.ks) > 0))
-                                                    and os.environ.get("HMG_NO_HINTS", "0") != "1")
-                if self._dcache["ks_ascending"]:
+                if self._ks_ascending():
                     d_kts = self._fft_grids(xmax, nxs)[1]
                     d_rowsc = self._buf((key, "rowsc"), (nz, nm, nat.ROWSC_STRIDE))
                     extra = (self._d_ks().ptr, d_kts.ptr, self._nk, int(nxs) // 2, d_rowsc.ptr)

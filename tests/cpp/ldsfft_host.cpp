@@ -3,6 +3,7 @@
 // Built by tests/test_ldsfft_cpu.py with g++; not part of the product.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 #include "../../hmvec_amd/csrc/ldsfft.hpp"
 
@@ -327,4 +328,17 @@ extern "C" int ldsfft_band_rfft_imag(const double* y, int n, int LB, int nthread
         case 1250: return band_rfft_imag<1250>(y, n, nthreads, jn, imF);
         default: return 3;
     }
+}
+
+// unpack_tw_table(nxs) against the loop the plan builders of hmgrid.hip ran before they shared it, byte for byte (the row
+// kernels read these tables: a change of arithmetic is a change of results).  0: identical, 1: another size, 2: other bytes.
+extern "C" int ldsfft_unpack_table_check(int nxs) {
+    const int M = nxs / 2;
+    std::vector<UnpackTw> twN(M / 2 + 1);
+    const long double twopi = 6.283185307179586476925286766559L;
+    for (int j = 0; j <= M / 2; ++j)
+        twN[j] = UnpackTw{(double)cosl(twopi * j / nxs), (double)sinl(twopi * j / nxs), j ? 1.0 / j : 0.0, 1.0 / (M - j)};
+    const std::vector<UnpackTw> t = unpack_tw_table(nxs);
+    if (t.size() != twN.size()) return 1;
+    return memcmp(t.data(), twN.data(), twN.size() * sizeof(UnpackTw)) ? 2 : 0;
 }

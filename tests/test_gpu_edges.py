@@ -111,6 +111,34 @@ def test_c_abi_rejects_bad_arguments():
     ctx.close()
 
 
+@pytest.mark.parametrize("nz,nm", [(3, 20), (17, 20)])
+def test_sigma2_equals_its_two_halves(nz, nm):
+    """hmg_sigma2 is hmg_sigma2_prepare + hmg_sigma2_prepared, bit for bit: both z tiles (nz <= 16, nz > 16), a mass grid
+    that is no multiple of the 16-wide tile, three k' segments with a ragged last one.  (A composition check: random
+    positive inputs.)"""
+    import os
+    import re
+    from conftest import REPO
+    from hmvec_amd import _native as nat
+    with open(os.path.join(REPO, "hmvec_amd", "csrc", "kernels", "sigma2.hpp")) as f:
+        seg = int(re.search(r"#define HMG_SIG_SEG_LEN (\d+)", f.read()).group(1))
+    nq = 2 * seg + 5
+    rng = np.random.default_rng(nz * 100 + nm)
+    ctx = nat.default_context()
+    d_sP, d_wq, d_R = (ctx.upload(rng.uniform(0.5, 2.0, s)) for s in ((nz, nq), (nq,), (nm,)))
+    d_kq = ctx.upload(np.sort(rng.uniform(1e-3, 10.0, nq)))
+    whole, halves = (ctx.upload(np.full((nz, nm), np.nan)) for _ in range(2))
+    ctx.call("hmg_sigma2", nz, nm, nq, d_sP.ptr, d_kq.ptr, d_wq.ptr, d_R.ptr, 0.01, whole.ptr)
+    n = C.c_size_t()
+    nat.check(ctx.lib.hmg_sigma2_layout_size(nz, nq, C.byref(n)))
+    d_PT = ctx.empty((n.value,))
+    ctx.call("hmg_sigma2_prepare", nz, nq, d_sP.ptr, d_PT.ptr)
+    ctx.call("hmg_sigma2_prepared", nz, nm, nq, d_PT.ptr, d_kq.ptr, d_wq.ptr, d_R.ptr, 0.01, halves.ptr)
+    a, b = whole.numpy(), halves.numpy()
+    assert np.all(np.isfinite(a)) and np.all(a > 0)
+    assert np.array_equal(a, b)
+
+
 def test_spectrum_cache_is_invalidated_by_state_changes():
     """get_power_1halo(a,b) + get_power_2halo(a,b) share one fused launch; any change of the
     profiles / HOD / mass function must drop the cached pair."""

@@ -338,3 +338,99 @@ def test_tensor_group_rejects_bad_arguments_and_falls_back_for_other_routes(defa
     for p in PAIRS:
         assert np.array_equal(g.get_power(*p), e.get_power(*p)), p
     assert_same(state(g), state(e))
+
+
+# ---- one check, every door: the shared builders of the launch code (hmgrid.hip) validate for every entry point that uses
+# them, so each door must refuse the same bad input with the same message - in validation, before anything is launched
+# (all pointers are one small real buffer, large enough for every array of the 1 x 4 x 8 grid all the same).
+DOORS = {
+    "mode = 7": (b"unknown mass function", ["hmg_massfn", "hmg_sigma2_massfn", "hmg_sigma2_massfn_halo", "hmg_group_rows:massfn"]),
+    "tinker without tz": (b"Tinker mode needs d_tinker_z",
+                          ["hmg_massfn", "hmg_sigma2_massfn", "hmg_sigma2_massfn_halo", "hmg_group_rows:massfn"]),
+    "unknown kind": (b"unknown profile kind", ["hmg_profile_rowparams", "hmg_profile_rows_from_mvir", "hmg_group_rows:rows",
+                                               "hmg_sigma2_halo_front:rows"]),
+    "pressure without hz": (b"pressure needs d_hz and d_post", ["hmg_profile_rowparams", "hmg_profile_rows_from_mvir",
+                                                                "hmg_group_rows:rows", "hmg_sigma2_halo_front:rows"]),
+    "pressure without post": (b"pressure needs d_hz and d_post", ["hmg_profile_rowparams", "hmg_profile_rows_from_mvir",
+                                                                  "hmg_group_rows:rows", "hmg_sigma2_halo_front:rows"]),
+    "corr = 2": (b"corr must be 0 (max) or 1 (min)", ["hmg_hod", "hmg_group_profile:hod", "hmg_group_rows:hod",
+                                                      "hmg_sigma2_halo_front:hod"]),
+    "NFW part without series": (b"NFW part", ["hmg_group_rows:nfw"]),
+}
+
+
+@pytest.mark.parametrize("case,door", [(c, d) for c, (_, doors) in DOORS.items() for d in doors])
+def test_one_check_every_door(case, door):
+    from hmvec_amd import _native as nat
+    ctx = nat.default_context()
+    ctx.flush()
+    lib, h = ctx.lib, ctx.handle
+    p = ctx.empty((4096,)).ptr
+    nz, nm, nk, nq = 1, 4, 8, 8
+    par = nat.MassFnParams(mode={"mode = 7": 7, "tinker without tz": nat.MF_TINKER10}.get(case, nat.MF_SHETH_TORMEN),
+                           deltac=1.686, st_A=0.3222, st_a=0.707, st_p=0.3, rho_m0=1.0, lnm_uniform=0, lnm_step=0.0)
+    tz = None if case == "tinker without tz" else p
+    kind = 99 if case == "unknown kind" else (nat.PROF_BATTAGLIA_PRES if case.startswith("pressure") else nat.PROF_BATTAGLIA_GAS)
+    hz = None if case == "pressure without hz" else p
+    post = None if case == "pressure without post" else p
+    hp = nat.HodParams(0.2, 1.0, 10.0, 1.0, 1.0, 1.0, 2 if case == "corr = 2" else 0)
+    fit = (C.c_double * 9)(*range(1, 10))
+    halo = nat.HaloStageArgs(p, p, p, 1.0, 0.1, 0.1, 0.7, p, p, p, p, p, 200.0, p, p, p)
+    mf = nat.MassFnPart(C.pointer(par), p, p, tz, p, p, p)
+    rows = nat.RowsPart(kind, p, p, p, p, p, hz, fit, 1.0, 1.0, 1.0, 1.0, p, p, p, p, p, p, post, None, None, 0, 0, None)
+    nfw = nat.NfwPart(p, p, p, p, None if case == "NFW part without series" else p, p)
+
+    def hod(stage):
+        return C.byref(nat.HodPart(stage, C.pointer(hp), *([p] * 12)))
+    sig = (nz, nm, nq, p, p, p, p, 0.01)
+    sigmf = sig + (C.byref(par), p, p, tz, p, p, p)
+    rowp = (C.byref(fit), 1.0, 1.0, 1.0, 1.0)
+    calls = {
+        "hmg_massfn": lambda: lib.hmg_massfn(h, nz, nm, C.byref(par), p, p, p, tz, p, p),
+        "hmg_sigma2_massfn": lambda: lib.hmg_sigma2_massfn(h, *sigmf),
+        "hmg_sigma2_massfn_halo": lambda: lib.hmg_sigma2_massfn_halo(h, *sigmf, C.byref(halo)),
+        "hmg_group_rows:massfn": lambda: lib.hmg_group_rows(h, nz, nm, nk, nq, C.byref(mf), None, None, None),
+        "hmg_profile_rowparams": lambda: lib.hmg_profile_rowparams(h, kind, nz, nm, p, p, p, p, p, hz, *rowp,
+                                                                   p, p, p, p, p, p, post),
+        "hmg_profile_rows_from_mvir": lambda: lib.hmg_profile_rows_from_mvir(h, kind, nz, nm, p, p, p, p, p, 200.0, p, hz,
+                                                                             *rowp, p, p, p, p, p, p, p, p, post),
+        "hmg_group_rows:rows": lambda: lib.hmg_group_rows(h, nz, nm, nk, nq, None, None, C.byref(rows), None),
+        "hmg_sigma2_halo_front:rows": lambda: lib.hmg_sigma2_halo_front(h, *sig, p, C.byref(halo), None, C.byref(rows)),
+        "hmg_hod": lambda: lib.hmg_hod(h, nz, nm, C.byref(hp), *([p] * 12)),
+        "hmg_group_profile:hod": lambda: lib.hmg_group_profile(h, nz, nm, nk, None, hod(nat.HOD_SUMS), None),
+        "hmg_group_rows:hod": lambda: lib.hmg_group_rows(h, nz, nm, nk, nq, None, hod(nat.HOD_SUMS), None, None),
+        "hmg_sigma2_halo_front:hod": lambda: lib.hmg_sigma2_halo_front(h, *sig, p, C.byref(halo), hod(nat.HOD_OCCUPATIONS), None),
+        "hmg_group_rows:nfw": lambda: lib.hmg_group_rows(h, nz, nm, nk, nq, None, None, None, C.byref(nfw)),
+    }
+    assert calls[door]() != 0
+    assert DOORS[case][0] in lib.hmg_last_error()
+
+
+@pytest.mark.parametrize("nm_other", [24, 16])
+def test_sigma2_prepared_records_the_shape_of_the_partial_sums_it_leaves(monkeypatch, nm_other):
+    """The partial sums of the last contraction live in one scratch slot of the context, and the massfn part of a grouped
+    launch reads them: after hmg_sigma2_prepared has overwritten the slot with sums of another shape, a massfn part of the
+    front's shape is refused; after one of the same shape it is accepted and finds the sums the front left."""
+    import hmvec_amd as hm
+    from hmvec_amd import _native as nat
+    monkeypatch.setenv("HMG_NO_GROUPS", "0")
+    zs, ms, ks = np.array([0.3, 1.2]), np.geomspace(1e11, 1e16, 16), np.geomspace(1e-3, 10, 24)
+    h = hm.HaloModel(zs, ks, ms=ms, accuracy="low", engine="analytic")
+    assert h._groups and any(k == "front" for k, _, _ in h._stages)
+    ctx = h._ctx()
+    ctx.flush()
+    before = h._d_sigma2.numpy()
+    nz, nm, nk, nq = 2, 16, ks.size, h._nq
+    d_PT, d_kq, d_wq, d_R = h._dcache["sig_in"]
+    par, d_lnm, d_tz = h._dcache["mf_in"][:3]
+    mf = nat.MassFnPart(C.pointer(par), h._d_ms().ptr, d_lnm.ptr, nat.ptr(d_tz), h._d_sigma2.ptr, h._d_nzm.ptr, h._d_bh.ptr)
+    d_R2 = ctx.upload(h.R_of_m(np.geomspace(1e11, 1e16, nm_other)))
+    out = ctx.empty((nz, nm_other))
+    ctx.call("hmg_sigma2_prepared", nz, nm_other, nq, d_PT.ptr, d_kq.ptr, d_wq.ptr, d_R2.ptr,
+             float(h.p["Wkr_taylor_switch"]), out.ptr)
+    rc = ctx.lib.hmg_group_rows(ctx.handle, nz, nm, nk, nq, C.byref(mf), None, None, None)
+    if nm_other != nm:
+        assert rc != 0 and b"hmg_sigma2_halo_front" in ctx.lib.hmg_last_error()
+    else:
+        assert rc == 0
+        assert np.array_equal(h._d_sigma2.numpy(), before)

@@ -30,6 +30,8 @@ def lib(tmp_path_factory):
     lib.ldsfft_band_rfft_imag.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_void_p]
     lib.ldsfft_band_rfft_imag.restype = ctypes.c_int
+    lib.ldsfft_unpack_table_check.argtypes = [ctypes.c_int]
+    lib.ldsfft_unpack_table_check.restype = ctypes.c_int
     return lib
 
 
@@ -158,3 +160,10 @@ def test_narrow_band_route_matches_numpy(lib, n, LB, nonzero, jn):
     need = np.arange(1, jn + 1)
     assert need.size == 0 or np.max(np.abs(out[need] - ref.imag[need])) < 1e-14 * scale * np.log2(n)
     assert lib.ldsfft_band_rfft_imag(y.ctypes.data, n, LB, 512, LB // 2, out.ctypes.data) == 5      # band too wide
+
+
+@pytest.mark.parametrize("nxs", [8, 5000])
+def test_unpack_table_is_the_plan_builders_loop_byte_for_byte(lib, nxs):
+    """The by-mode unpack constants (ldsfft.hpp: unpack_tw_table) that the one-row and the long-grid plan builders upload:
+    the same bytes as the loop both of them used to carry, long double cos/sin and the zero at j = 0 included."""
+    assert lib.ldsfft_unpack_table_check(nxs) == 0
