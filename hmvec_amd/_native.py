@@ -427,18 +427,15 @@ class Context:
         check(self.lib.hmg_sync(self.handle))
 
     def record(self, slot):
-        self.flush()
-        self.call_now("hmg_event_record", slot)
+        self.call("hmg_event_record", slot)
 
     def lane(self, i):
         """Route subsequent launches to lane i (0 = main stream)."""
-        self.flush()
-        self.call_now("hmg_lane_set", i)
+        self.call("hmg_lane_set", i)
 
     def wait(self, slot):
         """Current lane waits for the event last recorded in `slot`."""
-        self.flush()
-        self.call_now("hmg_event_wait", slot)
+        self.call("hmg_event_wait", slot)
 
     def elapsed_ms(self, s0, s1):
         ms = C.c_double()
@@ -466,7 +463,7 @@ class Context:
             self.flush()                  # ... and those queued inside it are
         except BaseException:
             for o in self._deferred:       # whatever was queued inside the failed capture is dropped with it
-                o._stages = []
+                o._drop_queue()
             self._deferred.clear()
             self.lib.hmg_graph_abort(self.handle)
             self.capture_serial += 1
@@ -485,19 +482,15 @@ class Context:
         return n.value
 
     def replay(self, gid):
-        self.flush()
-        self.call_now("hmg_graph_launch", gid)
+        self.call("hmg_graph_launch", gid)
 
     def copy_to_pinned(self, pinned, src):
         """Asynchronous D2H of DeviceArray ``src`` into PinnedArray ``pinned`` on the current lane."""
-        self.flush()
-        self.call_now("hmg_memcpy_d2h_async", pinned.ptr, src.ptr, src.nbytes)
-
+        self.call("hmg_memcpy_d2h_async", pinned.ptr, src.ptr, src.nbytes)
 
     def copy_from_pinned(self, dst, pinned):
         """Asynchronous H2D of PinnedArray ``pinned`` into DeviceArray ``dst`` on the current lane."""
-        self.flush()
-        self.call_now("hmg_memcpy_h2d_async", dst.ptr, pinned.ptr, dst.nbytes)
+        self.call("hmg_memcpy_h2d_async", dst.ptr, pinned.ptr, dst.nbytes)
 
     def event_synchronize(self, slot):
         """Block the host until the event last recorded in ``slot`` has happened (other work keeps running)."""

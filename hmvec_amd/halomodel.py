@@ -10,7 +10,6 @@ array, ``hods`` maps name -> dict, plus ``sigma2``, ``nzm``, ``bh``, ``Pzk``.  R
 those return numpy arrays (copied from the device on first access, then cached);
 assigning a numpy array to ``uk_profiles[name]`` uploads it.
 """
-import contextlib
 import ctypes as C
 import itertools
 import os
@@ -20,6 +19,7 @@ import numpy as np
 import scipy.constants as constants
 
 from . import _native as nat
+from . import stages
 from .cosmology import Cosmology, _is_shared_product, sigma2_kgrid, sigma2_weights
 from .params import battaglia_defaults, default_params
 from .quadrature import gradient_is_uniform, simpson_weights, trapz_weights
@@ -159,6 +159,9 @@ class HaloModel(Cosmology):
         self.ks = np.asarray(ks, dtype=np.float64)
         self._device = device
         self.ctx = ctx
+        self.ms = self._ms_key = self._sync_serial = self._rho_m0_val = None
+        self._version = self._epoch = self._nq = 0      # spectra-cache version; content tag of the (z,m) arrays; sigma^2 grid size
+        self._aux_pending = self._m200c_valid = False
         Cosmology.__init__(self, params, halofit, engine=engine, accuracy=accuracy, background=background)
 
         self.mdef = mdef
@@ -180,7 +183,6 @@ class HaloModel(Cosmology):
         # (name, name2) -> (state version, P1h, P2h): a fused launch yields both terms, so the
         # usual get_power_1halo(a,b) followed by get_power_2halo(a,b) streams the tensors once
         self._pcache = {}
-        self._version = 0
         self.uk_profiles = DeviceDict(self._ctx, self._bump)
         self.pk_profiles = DeviceDict(self._ctx, self._bump)
 
@@ -228,7 +230,7 @@ class HaloModel(Cosmology):
     # ------------------------------------------------------------------ device plumbing
     def _bump(self):
         """Any change of profiles / HODs / mass function invalidates cached spectra."""
-        self._version = getattr(self, "_version", 0) + 1
+        self._version += 1
 
     def _release_inputs(self, keys):
         """Drop cached device inputs.  Stages queued earlier (the constructor queues three) hold raw pointers to
@@ -267,7 +269,7 @@ class HaloModel(Cosmology):
         """Route the next launches to the auxiliary lane (no-op without lanes)."""
         ctx = self._ctx()
         if self._use_lanes:
-            if getattr(self, "_sync_serial", None) != ctx.capture_serial:
+            if self._sync_serial != ctx.capture_serial:
                 self._sync_point()          # first auxiliary launch of this capture / eager epoch
             ctx.lane(self._AUX)
             ctx.wait(self._EV_SYNC)
@@ -285,7 +287,7 @@ class HaloModel(Cosmology):
         ctx = self._ctx()
         if self._use_lanes:
             ctx.lane(0)
-            if needs_aux and getattr(self, "_aux_pending", False):
+            if needs_aux and self._aux_pending:
                 ctx.wait(self._EV_AUX)
         return ctx
 
@@ -339,39 +341,41 @@ class HaloModel(Cosmology):
     bh = property(lambda self: self._lazy_host("bh"))
 
     # ------------------------------------------------------------------ grouped launches
-    # Which queued stage must not run before which (a stage kind appears at most once in the queue):
-    # the HOD reads n, b; the profile FFT reads the row parameters.
-    _RUNS_AFTER = {"hod": ("massfn",), "fft": ("rows",)}
-
-    def _queue(self, kind, part, keep=()):
-        """Queue a launch-only stage.  Anything that reads device state goes through the context, which
-        issues the queue first (Context.flush), so deferral is invisible to callers."""
-        pend = [st[0] for st in self._stages]
+    def _stage(self, kind, part, keep=()):
+        """One launch-only stage (stages.py).  With groups it is queued: anything that reads device state goes through
+        the context, which issues the queue first (Context.flush), so deferral is invisible to callers.  Without, it is
+        issued here as its own launch."""
+        ctx = self._ctx()
         # The grid sizes a stage was built for travel with it: the raw pointers inside `part` belong to buffers
         # of exactly these sizes, whatever self.ms / self.ks are by the time the queue is issued.
-        dims = (self._nz, self._nm if getattr(self, "ms", None) is not None else 0, self._nk, getattr(self, "_nq", 0))
-        # same kind twice, a producer queued behind its own consumer (it would overwrite what the consumer
-        # still has to read), the front of a new pass (it rewrites what every queued stage reads), or a stage
-        # built for another grid than the queued ones: issue what is queued first
-        if pend and (kind == "front" or kind in pend or any(kind in self._RUNS_AFTER.get(k, ()) for k in pend)
-                     or dims != self._stage_dims):
-            self._ctx().flush()
+        dims = (self._nz, self._nm if self.ms is not None else 0, self._nk, self._nq)
+        if not self._groups:
+            ctx.flush()          # deferred stages of ANY model on this context first: their own flush resets the tag
+            return self._issue(ctx.call, [stages.alone(kind, part, dims)])
+        if stages.must_issue_first([st[0] for st in self._stages], self._stage_dims, kind, dims):
+            ctx.flush()
         self._stage_dims = dims
         self._stages.append((kind, part, keep))
-        self._ctx().defer(self)
+        ctx.defer(self)
 
-    @contextlib.contextmanager
-    def _tagged(self, call):
-        """This model's support tag and deferral flag around ONE native call, issued with `call` (ctx.call_now or
-        ctx.call).  Both are context state: set right around the call they describe and restored whatever that call
-        does (a call that raises inside a capture must not leave this model's tag behind: ADVICE r05)."""
-        call("hmg_profile_support_epoch", getattr(self, "_epoch", 0))
-        call("hmg_prefix_deferral", int(self.prefix_deferral))
-        try:
-            yield
-        finally:
-            call("hmg_prefix_deferral", 0)
-            call("hmg_profile_support_epoch", 0)
+    def _drop_queue(self):       # (Context.capture: the capture these stages were queued in has failed)
+        self._stages = []
+
+    def _issue(self, call, launches):
+        """Issue (entry, args, tagged) launches with `call` (ctx.call_now or ctx.call), a tagged one between this model's
+        support tag and deferral flag.  Both are context state: set right around the ONE call they describe and restored
+        whatever that call does (a call that raises inside a capture must not leave this model's tag behind: ADVICE r05)."""
+        for entry, args, tagged in launches:
+            if not tagged:
+                call(entry, *args)
+                continue
+            call("hmg_profile_support_epoch", self._epoch)
+            call("hmg_prefix_deferral", int(self.prefix_deferral))
+            try:
+                call(entry, *args)
+            finally:
+                call("hmg_prefix_deferral", 0)
+                call("hmg_profile_support_epoch", 0)
 
     def _ks_ascending(self):
         """Is the target k grid ascending (the promise of the hint arrays and the row scalars)?  Cached per model."""
@@ -381,63 +385,12 @@ class HaloModel(Cosmology):
         return self._dcache["ks_ascending"]
 
     def _flush(self, prep=None):
-        """Issue the queued stages as grouped launches: front (sigma^2 contraction | halo stage | HOD occupations |
-        Battaglia row parameters: inputs only), then the tensor group (per-z chain: sigma^2 second stage + n, b -> HOD sums ->
-        coefficient rows of the mass integrals `prep` describes | profile FFT rows | NFW rows) - or, when no profile
-        transform is queued or its row parameters could not ride with a front, the rows group (n, b tiles | row parameters |
-        NFW rows) followed by the profile group (chain | profile FFT rows).  Returns True if `prep` was issued
-        (hmg_power_batch_run then skips its preparation launch)."""
-        stages, self._stages = self._stages, []
-        st = {k: p for k, p, _ in stages}
-        if not st:
-            return False
-        ctx = self._ctx()
-        nz, nm, nk, nq = self._stage_dims          # the sizes at queue time, not the model's current ones
-        ref = lambda k: C.byref(st[k]) if k in st else None      # noqa: E731
-        x = os.environ.get("HMG_X", "")          # experiment switches (tuning only)
-        if "prep_alone" in x:
-            prep = None
-        hod_sums = False
-        if "front" in st:
-            occ = None
-            if "hod" in st:      # the occupation numbers need inputs only: they ride in the front launch ...
-                occ = nat.HodPart.from_buffer_copy(st["hod"])
-                occ.stage, st["hod"].stage = nat.HOD_OCCUPATIONS, nat.HOD_SUMS
-                hod_sums = True  # ... and n_gal, b_g, which need the n, b of this pass, in the chain of the tensor (or profile) group
-            args = st.pop("front")
-            # ... and so do the Battaglia row parameters: the thread that solves for M_200c goes on to them
-            rows = st.pop("rows") if "rows" in st and "rows_alone" not in x else None
-            ctx.call_now("hmg_sigma2_halo_front", *args[:-1], C.byref(args[-1]), C.byref(occ) if occ is not None else None,
-                         C.byref(rows) if rows is not None else None)
-        elif "hod" in st:        # no front to ride with: the HOD's own kernel (n, b are there already)
-            h = st.pop("hod")
-            ctx.call_now("hmg_hod", nz, nm, h.h_par, h.d_zs, h.d_ms, h.d_log10mstar_thresh, h.d_nzm, h.d_bh, h.d_wm,
-                         h.d_Nc, h.d_Ns, h.d_NsNsm1, h.d_NcNs, h.d_ngal, h.d_bg)
-        if "fft" in st and ("massfn" in st or "nfw" in st) and "rows" not in st and not x:
-            # tensor group: chain (sigma^2 -> n, b -> HOD sums -> coefficient rows) | profile rows | NFW rows, one launch
-            with self._tagged(ctx.call_now):
-                ctx.call_now("hmg_group_tensors", nz, nm, nk, nq, ref("massfn"), ref("hod") if hod_sums else None,
-                             C.byref(prep) if prep is not None else None, ref("nfw"), ref("fft"))
-            return prep is not None
-        nfw_alone = st.pop("nfw") if "nfw_alone" in x and "nfw" in st else None
-        if any(k in st for k in ("massfn", "rows", "nfw")):
-            ctx.call_now("hmg_group_rows", nz, nm, nk, nq, ref("massfn"), None, ref("rows"), ref("nfw"))
-        if nfw_alone is not None:
-            ctx.call_now("hmg_nfw_analytic", nz, nm, nk, nfw_alone.d_cs, nfw_alone.d_rs, nfw_alone.d_zs, nfw_alone.d_ks,
-                         nfw_alone.d_nfw_series, nfw_alone.d_uk)
-        if "fft" in st or hod_sums:
-            if "chain_alone" in x and "fft" in st and (hod_sums or prep is not None):
-                # experiment (VERDICT r03 #3): the per-z chain as a launch of its own in front of the stand-alone
-                # row kernel (no private segment) instead of a role of the profile group
-                ctx.call_now("hmg_group_profile", nz, nm, nk, None, ref("hod") if hod_sums else None,
-                             C.byref(prep) if prep is not None else None)
-                ctx.call_now("hmg_group_profile", nz, nm, nk, ref("fft"), None, None)
-                return prep is not None
-            with self._tagged(ctx.call_now):
-                ctx.call_now("hmg_group_profile", nz, nm, nk, ref("fft"), ref("hod") if hod_sums else None,
-                             C.byref(prep) if prep is not None else None)
-            return prep is not None
-        return False
+        """Issue the queued stages as the grouped launches stages.plan makes of them.  Returns True if `prep` was issued
+        with them (hmg_power_batch_run then skips its preparation launch)."""
+        queued, self._stages = self._stages, []
+        launches, prepared = stages.plan(queued, self._stage_dims, prep, os.environ.get("HMG_X", ""))
+        self._issue(self._ctx().call_now, launches)
+        return prepared
 
     # ------------------------------------------------------------------ mass function
     def get_sigma2(self):
@@ -463,7 +416,7 @@ class HaloModel(Cosmology):
         """sigma2, n(z,m), b(z,m), c(z,m), rvir(z,m) on the device (hmvec/hmvec.py:127-185).
         Inputs are uploaded on the first call; later calls only launch kernels."""
         ms = np.asarray(ms, dtype=np.float64)
-        if getattr(self, "_ms_key", None) is None or not np.array_equal(ms, self._ms_key):
+        if self._ms_key is None or not np.array_equal(ms, self._ms_key):
             self._release_inputs([k for k in self._dcache if k != "zs" and k != "ks" and k != "Pzk"
                                   and not (isinstance(k, tuple) and k[0] == "fftgrid")])
             self._ms_key = ms.copy()
@@ -531,36 +484,31 @@ class HaloModel(Cosmology):
         d_ms = self._d_ms()
         # c(z,m), rvir(z,m), rs(z,m), the series rows of the analytic NFW kernel and the vir -> 200c mass
         # conversion the Battaglia profiles need: one thread per (z,m), independent of sigma2
-        sfx = self.mdef
         self._d_cs, self._d_rvir, self._d_rs = (self._buf(k, (nz, nm)) for k in ("cs", "rvir", "rs"))
         self._d_nfw_series = self._buf("nfw_series", (nz, nm, nat.NFW_SERIES_STRIDE))
-        m2, r2 = self._buf("m200c", (nz, nm)), self._buf("r200c", (nz, nm))
-        d_drho1 = self._d_drho1()
-        d_rhoc = self._dev("rhocz", lambda: self.rho_critical_z(self.zs))
-        sig_args = (nz, nm, d_kq.size, d_PT.ptr, d_kq.ptr, d_wq.ptr, d_R.ptr,
-                    float(self.p["Wkr_taylor_switch"]), C.byref(par), d_ms.ptr, d_lnm.ptr, nat.ptr(d_tz),
-                    self._d_sigma2.ptr, self._d_nzm.ptr, self._d_bh.ptr)
-        duffy = tuple(float(self.p[f"duffy_{k}_{sfx}"]) for k in ("A", "alpha", "beta"))
-        halo_args = (self._d_zs().ptr, d_delta.ptr, d_rho.ptr, *duffy, float(self.h),
-                     self._d_cs.ptr, self._d_rvir.ptr, self._d_rs.ptr, self._d_nfw_series.ptr,
-                     d_drho1.ptr, 200.0, d_rhoc.ptr, m2.ptr, r2.ptr)
-        halo = nat.HaloStageArgs(*halo_args)
+        m2, r2, d_drho1, d_rhoc = self._m200c_io()
+        duffy = tuple(float(self.p[f"duffy_{k}_{self.mdef}"]) for k in ("A", "alpha", "beta"))
+        halo = nat.HaloStageArgs(self._d_zs().ptr, d_delta.ptr, d_rho.ptr, *duffy, float(self.h),
+                                 self._d_cs.ptr, self._d_rvir.ptr, self._d_rs.ptr, self._d_nfw_series.ptr,
+                                 d_drho1.ptr, 200.0, d_rhoc.ptr, m2.ptr, r2.ptr)
+        massfn = nat.MassFnPart(C.pointer(par), d_ms.ptr, d_lnm.ptr, nat.ptr(d_tz), self._d_sigma2.ptr, self._d_nzm.ptr, self._d_bh.ptr)
+        front = stages.FrontArgs((nz, nm, d_kq.size, d_PT.ptr, d_kq.ptr, d_wq.ptr, d_R.ptr,
+                                  float(self.p["Wkr_taylor_switch"])), d_ms.ptr, halo)
         if self._groups:
             # front group: the contraction beside the halo stage (both need inputs only); the second stage of
             # the contraction and n(z,m), b(z,m) are queued as the first link of the per-z chain
             self._nq = int(d_kq.size)
-            self._queue("front", sig_args[:8] + (d_ms.ptr, halo))
-            self._queue("massfn", nat.MassFnPart(C.pointer(par), d_ms.ptr, d_lnm.ptr, nat.ptr(d_tz), self._d_sigma2.ptr,
-                                                 self._d_nzm.ptr, self._d_bh.ptr), keep=(par,))
+            self._stage("front", front)
+            self._stage("massfn", massfn, keep=(par,))
         elif not self._use_lanes:
             # one launch behind the contraction: mass function and halo stage side by side
-            ctx.call("hmg_sigma2_massfn_halo", *sig_args, C.byref(halo))
+            ctx.call("hmg_sigma2_massfn_halo", *front.sigma2, *stages.fields(massfn), C.byref(halo))
         else:
             # two-lane scheme: n, b on the auxiliary lane, the halo stage on the main lane ahead of the profiles
-            ctx.call("hmg_sigma2_massfn", *sig_args)
+            ctx.call("hmg_sigma2_massfn", *front.sigma2, *stages.fields(massfn))
             self._aux_done()
             ctx = self._main()
-            ctx.call("hmg_halo_stage", nz, nm, d_ms.ptr, *halo_args)
+            ctx.call("hmg_halo_stage", nz, nm, d_ms.ptr, *stages.fields(halo))
         self._m200c_valid = True
 
     def get_fsigmaz(self):
@@ -590,16 +538,17 @@ class HaloModel(Cosmology):
         return self._d_cs.numpy()
 
     # ------------------------------------------------------------------ profiles
+    def _m200c_io(self):
+        """Outputs and inputs of the vir -> 200c mass conversion on the device: (m200c, r200c, Delta rho_vir(z), rho_crit(z))."""
+        return (self._buf("m200c", (self._nz, self._nm)), self._buf("r200c", (self._nz, self._nm)), self._d_drho1(),
+                self._dev("rhocz", lambda: self.rho_critical_z(self.zs)))
+
     def _m200c(self):
         """(m200c, r200c) on the device (hmvec/hmvec.py:216-225)."""
-        ctx = self._ctx()
-        nz, nm = self._nz, self._nm
-        m2, r2 = self._buf("m200c", (nz, nm)), self._buf("r200c", (nz, nm))
-        if not getattr(self, "_m200c_valid", False):
-            d1 = self._d_drho1()
-            d_rhoc = self._dev("rhocz", lambda: self.rho_critical_z(self.zs))
-            ctx.call("hmg_mdelta_convert", nz, nm, self._d_ms().ptr, self._d_cs.ptr, d1.ptr, 200.0,
-                     d_rhoc.ptr, m2.ptr, r2.ptr)
+        m2, r2, d1, d_rhoc = self._m200c_io()
+        if not self._m200c_valid:
+            self._ctx().call("hmg_mdelta_convert", self._nz, self._nm, self._d_ms().ptr, self._d_cs.ptr, d1.ptr, 200.0,
+                             d_rhoc.ptr, m2.ptr, r2.ptr)
             self._m200c_valid = True
         return m2, r2
 
@@ -625,69 +574,50 @@ class HaloModel(Cosmology):
         return self._dcache[key]
 
     def _profile_fft(self, key, nxs, xmax, rowp, consts, gamma, d_cmax, d_rss, do_mass_norm, d_post=None, d_rowsc=None):
-        """One hmg_profile_fft launch; returns (tensor, hint).  The hint - how many leading target
-        wavenumbers of each row lie below the row's first FFT mode, and the value np.interp's left
-        fill gives them all - lets the batched mass integrals skip those parts of the tensor.  It
-        is only requested when the target k grid is ascending."""
-        ctx = self._ctx()
+        """One hmg_profile_fft launch; returns (tensor, hint).  The hint - how many leading target wavenumbers of each row
+        lie below the row's first FFT mode, and the value np.interp's left fill gives them all - lets the batched mass
+        integrals skip those parts of the tensor.  It is only requested when the target k grid is ascending."""
         nz, nm, nk = self._nz, self._nm, self._nk
         d_xs, d_kts, step, d_lx = self._fft_grids(xmax, nxs)
         out = self._buf(key, (nz, nm, nk))
-        hint = None
-        if self._ks_ascending():
-            # nconst is an int32 array: allocated as (nz*nm+1)//2 doubles, viewed as integers on read
-            hint = (self._buf((key, "nconst"), ((nz * nm + 1) // 2,)), self._buf((key, "cconst"), (nz, nm)))
-        amp, xc, alpha, expo = rowp
-        args = (int(nxs), step, d_xs.ptr, d_kts.ptr,
-                nat.ptr(amp), nat.ptr(xc), nat.ptr(alpha), nat.ptr(expo),
-                float(consts[0]), float(consts[1]), float(consts[2]), float(consts[3]), float(gamma),
-                d_cmax.ptr, d_rss.ptr, self._d_zs().ptr, self._d_ks().ptr, int(do_mass_norm),
-                nat.ptr(d_post), out.ptr, nat.ptr(hint[0] if hint else None), nat.ptr(hint[1] if hint else None),
-                d_lx.ptr)
-        if self._groups:
-            # (the row scalars only travel with the hint arrays: they carry the left-fill count, which needs ks ascending)
-            self._queue("fft", nat.ProfileFftPart(*args, nat.ptr(d_rowsc if hint else None)))
-        else:
-            ctx.flush()          # deferred stages of ANY model on this context first: their own flush resets the tag
-            with self._tagged(ctx.call):
-                ctx.call("hmg_profile_fft", nz, nm, nk, *args)
+        # nconst is an int32 array: allocated as (nz*nm+1)//2 doubles, viewed as integers on read
+        hint = ((self._buf((key, "nconst"), ((nz * nm + 1) // 2,)), self._buf((key, "cconst"), (nz, nm)))
+                if self._ks_ascending() else None)
+        # (the row scalars only travel with the hint arrays: they carry the left-fill count, which needs ks ascending)
+        self._stage("fft", nat.ProfileFftPart(
+            int(nxs), step, d_xs.ptr, d_kts.ptr, *(nat.ptr(r) for r in rowp), *(float(c) for c in consts), float(gamma),
+            d_cmax.ptr, d_rss.ptr, self._d_zs().ptr, self._d_ks().ptr, int(do_mass_norm), nat.ptr(d_post), out.ptr,
+            nat.ptr(hint[0] if hint else None), nat.ptr(hint[1] if hint else None), d_lx.ptr,
+            nat.ptr(d_rowsc if hint else None)))
         return out, hint
 
     def _battaglia_rowparams(self, key, kind, fit9, gamma, alpha_const, pref, post_pref, nxs=None, xmax=None):
         """Row parameters of a Battaglia family; returns (outs, d_rowsc): with a radial grid (nxs, xmax) and an ascending
         k grid the queued stage also leaves the output-side scalars of every row for the transform (hmg_rows_part,
         ABI 8), d_rowsc is then the buffer to hand to _profile_fft, else None."""
-        ctx = self._ctx()
         nz, nm = self._nz, self._nm
         outs = [self._buf((key, "rowp", i), (nz, nm)) for i in range(7)]
         fit = (C.c_double * 9)(*fit9)
         d_hz = self._dev("hz", lambda: self.h_of_z(self.zs))
-        d_rhoc = self._dev("rhocz", lambda: self.rho_critical_z(self.zs))
-        if not getattr(self, "_m200c_valid", False):
+        m200c, r200c, d_drho1, d_rhoc = self._m200c_io()
+        if not self._m200c_valid:
             # mass conversion and row parameters in one launch
-            m2, r2 = self._buf("m200c", (nz, nm)), self._buf("r200c", (nz, nm))
-            ctx.call("hmg_profile_rows_from_mvir", kind, nz, nm, self._d_ms().ptr, self._d_cs.ptr,
-                     self._d_rvir.ptr, self._d_zs().ptr, self._d_drho1().ptr, 200.0, d_rhoc.ptr, d_hz.ptr,
-                     C.byref(fit), float(gamma), float(alpha_const), float(pref), float(post_pref),
-                     m2.ptr, r2.ptr, *[o.ptr for o in outs])
+            self._ctx().call("hmg_profile_rows_from_mvir", kind, nz, nm, self._d_ms().ptr, self._d_cs.ptr,
+                             self._d_rvir.ptr, self._d_zs().ptr, d_drho1.ptr, 200.0, d_rhoc.ptr, d_hz.ptr,
+                             C.byref(fit), float(gamma), float(alpha_const), float(pref), float(post_pref),
+                             m200c.ptr, r200c.ptr, *[o.ptr for o in outs])
             self._m200c_valid = True
             return outs, None
-        m200c, r200c = self._m200c()
-        if self._groups:
-            d_rowsc, extra = None, (None, None, 0, 0, None)
-            if nxs is not None and nxs % 2 == 0 and os.environ.get("HMG_NO_ROWSC", "0") != "1":
-                if self._ks_ascending():
-                    d_kts = self._fft_grids(xmax, nxs)[1]
-                    d_rowsc = self._buf((key, "rowsc"), (nz, nm, nat.ROWSC_STRIDE))
-                    extra = (self._d_ks().ptr, d_kts.ptr, self._nk, int(nxs) // 2, d_rowsc.ptr)
-            self._queue("rows", nat.RowsPart(kind, m200c.ptr, r200c.ptr, self._d_rvir.ptr, self._d_zs().ptr, d_rhoc.ptr,
-                                             d_hz.ptr, fit, float(gamma), float(alpha_const), float(pref),
-                                             float(post_pref), *[o.ptr for o in outs], *extra))
-            return outs, d_rowsc
-        ctx.call("hmg_profile_rowparams", kind, nz, nm, m200c.ptr, r200c.ptr, self._d_rvir.ptr,
-                 self._d_zs().ptr, d_rhoc.ptr, d_hz.ptr, C.byref(fit), float(gamma), float(alpha_const),
-                 float(pref), float(post_pref), *[o.ptr for o in outs])
-        return outs, None
+        d_rowsc, extra = None, (None, None, 0, 0, None)
+        if (self._groups and nxs is not None and nxs % 2 == 0 and os.environ.get("HMG_NO_ROWSC", "0") != "1"
+                and self._ks_ascending()):
+            d_kts = self._fft_grids(xmax, nxs)[1]
+            d_rowsc = self._buf((key, "rowsc"), (nz, nm, nat.ROWSC_STRIDE))
+            extra = (self._d_ks().ptr, d_kts.ptr, self._nk, int(nxs) // 2, d_rowsc.ptr)
+        self._stage("rows", nat.RowsPart(kind, m200c.ptr, r200c.ptr, self._d_rvir.ptr, self._d_zs().ptr, d_rhoc.ptr,
+                                         d_hz.ptr, fit, float(gamma), float(alpha_const), float(pref),
+                                         float(post_pref), *[o.ptr for o in outs], *extra))
+        return outs, d_rowsc
 
     def add_battaglia_profile(self, name, family=None, param_override=None, nxs=None, xmax=None,
                               ignore_existing=False):
@@ -765,22 +695,15 @@ class HaloModel(Cosmology):
             nxs = self.p["nfw_integral_numxs"]
         if xmax is None:
             xmax = self.p["nfw_integral_xmax"]
-        ctx = self._ctx()
-        nz, nm, nk = self._nz, self._nm, self._nk
-        hint = None
-        ctx = self._main()
+        self._main()
         if numeric:
             # rho = 1/x/(1+x)^2 is the gamma=-1, alpha=1, expo=2 member of the family
             out, hint = self._profile_fft(("uk", name), nxs, xmax, (None, None, None, None), (1.0, 1.0, 1.0, 2.0),
                                           -1.0, self._d_cs, self._d_rs, True)
         else:
-            out = self._buf(("uk", name), (nz, nm, nk))
-            if self._groups:
-                self._queue("nfw", nat.NfwPart(self._d_cs.ptr, self._d_rs.ptr, self._d_zs().ptr, self._d_ks().ptr,
-                                               self._d_nfw_series.ptr, out.ptr))
-            else:
-                ctx.call("hmg_nfw_analytic", nz, nm, nk, self._d_cs.ptr, self._d_rs.ptr, self._d_zs().ptr,
-                         self._d_ks().ptr, self._d_nfw_series.ptr, out.ptr)
+            out, hint = self._buf(("uk", name), (self._nz, self._nm, self._nk)), None
+            self._stage("nfw", nat.NfwPart(self._d_cs.ptr, self._d_rs.ptr, self._d_zs().ptr, self._d_ks().ptr,
+                                           self._d_nfw_series.ptr, out.ptr))
         self.uk_profiles.set_dev(name, out, hint)
         return self.ks, _LazyArray(self.uk_profiles, name)
 
@@ -795,8 +718,7 @@ class HaloModel(Cosmology):
         ctx = self._ctx()
         nz, nm = self._nz, self._nm
         par = nat.HodParams(pparams["hod_sig_log_mstellar"], pparams["hod_alphasat"], pparams["hod_Bsat"],
-                            pparams["hod_betasat"], pparams["hod_Bcut"], pparams["hod_betacut"],
-                            {"max": 0, "min": 1}[corr])
+                            pparams["hod_betasat"], pparams["hod_Bcut"], pparams["hod_betacut"], {"max": 0, "min": 1}[corr])
         thr = np.ascontiguousarray(log10mstar_thresh, dtype=np.float64)
         cached = self._dcache.get(("thr", key))
         if cached is None or cached[0].shape != thr.shape:
@@ -811,17 +733,11 @@ class HaloModel(Cosmology):
             cached[0][...] = thr
         d_thr = cached[1]
         out = {k: self._buf((key, k), (nz, nm)) for k in ("Nc", "Ns", "NsNsm1", "NcNs")}
-        out["ngal"], out["bg"] = self._buf((key, "ngal"), (nz,)), self._buf((key, "bg"), (nz,))
+        out["ngal"], out["bg"] = self._buf((key, "ngal"), (nz,)), self._buf((key, "bg"), (nz,))      # (HodPart's order)
         d_wm, d_ms, d_zs = self._d_wm(), self._d_ms(), self._d_zs()     # (uploads, if any, before the lane switch)
-        if self._groups:
-            self._queue("hod", nat.HodPart(nat.HOD_ALL, C.pointer(par), d_zs.ptr, d_ms.ptr, d_thr.ptr, self._d_nzm.ptr,
-                                           self._d_bh.ptr, d_wm.ptr, out["Nc"].ptr, out["Ns"].ptr, out["NsNsm1"].ptr,
-                                           out["NcNs"].ptr, out["ngal"].ptr, out["bg"].ptr), keep=(par,))
-            return out
-        ctx = self._aux()
-        ctx.call("hmg_hod", nz, nm, C.byref(par), d_zs.ptr, d_ms.ptr, d_thr.ptr,
-                 self._d_nzm.ptr, self._d_bh.ptr, d_wm.ptr, out["Nc"].ptr, out["Ns"].ptr,
-                 out["NsNsm1"].ptr, out["NcNs"].ptr, out["ngal"].ptr, out["bg"].ptr)
+        self._aux()              # (both are no-ops without lanes, and a model with lanes queues nothing)
+        self._stage("hod", nat.HodPart(nat.HOD_ALL, C.pointer(par), d_zs.ptr, d_ms.ptr, d_thr.ptr, self._d_nzm.ptr,
+                                       self._d_bh.ptr, d_wm.ptr, *(o.ptr for o in out.values())), keep=(par,))
         self._aux_done()
         return out
 
@@ -902,26 +818,23 @@ class HaloModel(Cosmology):
                                  f"{(self._nz, self._nm, self._nk)}")
             return d_
         for kind in order:
-            if kind == "h" and name in self.hods:
-                hod = self.hods[name]
+            dd = self.hods if kind == "h" else self.uk_profiles if kind == "m" else self.pk_profiles
+            if name not in dd:
+                continue
+            if kind == "h":
+                hod = dd[name]
                 cn = hod["central_profile"]
                 d = hod.dev
                 sn = hod["satellite_profile"]
                 hs = self.uk_profiles.hint(sn)
                 hc = self.uk_profiles.hint(cn) if cn is not None else (None, None)
-                t = nat.Tracer(nat.TRACER_HOD, tensor(self.uk_profiles, sn).ptr,
-                               None if cn is None else tensor(self.uk_profiles, cn).ptr,
-                               d["Nc"].ptr, d["Ns"].ptr, d["NcNs"].ptr, d["NsNsm1"].ptr, d["ngal"].ptr, None,
-                               nat.ptr(hs[0]), nat.ptr(hs[1]), nat.ptr(hc[0]), nat.ptr(hc[1]))
-                return t, "h"
-            if kind == "m" and name in self.uk_profiles:
-                hp = self.uk_profiles.hint(name)
-                return nat.Tracer(nat.TRACER_MATTER, tensor(self.uk_profiles, name).ptr, None, None, None, None, None,
-                                  None, None, nat.ptr(hp[0]), nat.ptr(hp[1])), "m"
-            if kind == "p" and name in self.pk_profiles:
-                hp = self.pk_profiles.hint(name)
-                return nat.Tracer(nat.TRACER_PRESSURE, tensor(self.pk_profiles, name).ptr, None, None, None, None, None,
-                                  None, None, nat.ptr(hp[0]), nat.ptr(hp[1])), "p"
+                return nat.Tracer(nat.TRACER_HOD, tensor(self.uk_profiles, sn).ptr,
+                                  None if cn is None else tensor(self.uk_profiles, cn).ptr,
+                                  d["Nc"].ptr, d["Ns"].ptr, d["NcNs"].ptr, d["NsNsm1"].ptr, d["ngal"].ptr, None,
+                                  nat.ptr(hs[0]), nat.ptr(hs[1]), nat.ptr(hc[0]), nat.ptr(hc[1])), kind
+            hp = dd.hint(name)
+            return nat.Tracer(nat.TRACER_MATTER if kind == "m" else nat.TRACER_PRESSURE, tensor(dd, name).ptr, None, None,
+                              None, None, None, None, None, nat.ptr(hp[0]), nat.ptr(hp[1])), kind
         raise ValueError
 
     def _power_launch(self, ta, tb, want1, want2, out1=None, out2=None):
@@ -936,7 +849,7 @@ class HaloModel(Cosmology):
         return d1, d2
 
     def _rho_m0(self):
-        if getattr(self, "_rho_m0_val", None) is None:
+        if self._rho_m0_val is None:
             self._rho_m0_val = float(self.rho_matter_z(0)[0])
         return self._rho_m0_val
 

@@ -434,3 +434,28 @@ def test_sigma2_prepared_records_the_shape_of_the_partial_sums_it_leaves(monkeyp
     else:
         assert rc == 0
         assert np.array_equal(h._d_sigma2.numpy(), before)
+
+
+@pytest.mark.parametrize("grouped", [True, False])
+def test_second_pass_on_the_device_makes_the_calls_of_the_recording_stand_in(monkeypatch, grouped):
+    """tests/test_stage_plan_cpu.py checks the facade's native call sequence against a stand-in for the library; this ties
+    the stand-in to the real binding: the call list Context.trace records of the second pass on (3, 48, 96) with the
+    default radial grids has the same entry names on a real context and on the stand-in."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+    import recording_context as rc
+    from hmvec_amd import _native as nat
+    for sw in ("HMG_LANES", "HMG_X"):
+        monkeypatch.delenv(sw, raising=False)
+    monkeypatch.setenv("HMG_NO_GROUPS", "0" if grouped else "1")
+    names = []
+    for ctx in (nat.Context(0), rc.recording_context()):
+        h = rc.build_model(ctx)
+        assert h._groups == grouped
+        names.append([name for name, _ in ctx.trace(lambda: rc.second_pass(h))])
+        ctx.sync()
+        del h
+        ctx.close()
+    assert names[0] == names[1] and len(names[0]) >= 14
+    assert ("hmg_group_tensors" in names[0]) == grouped and ("hmg_profile_fft" in names[0]) == (not grouped)
