@@ -13,13 +13,14 @@ assigning a numpy array to ``uk_profiles[name]`` uploads it.
 import ctypes as C
 import itertools
 import os
+from collections import namedtuple
 from collections.abc import MutableMapping
 
 import numpy as np
 import scipy.constants as constants
 
 from . import _native as nat
-from . import stages
+from . import spectra, stages
 from .cosmology import Cosmology, _is_shared_product, sigma2_kgrid, sigma2_weights
 from .params import battaglia_defaults, default_params
 from .quadrature import gradient_is_uniform, simpson_weights, trapz_weights
@@ -30,6 +31,9 @@ from .utils import vectorized_bisection_search
 _trapz = getattr(np, "trapezoid", None) or np.trapz
 _EPOCHS = itertools.count(1)      # content tags of the per-model (z,m) arrays (hmg_profile_support_epoch)
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
+# A cached pair of spectra: the model's state version it was computed for, P_1h and P_2h on the device and, from a batched
+# launch, the host block of that launch (_HostBlock) with the two spectra's places in it
+_Spectra = namedtuple("_Spectra", "version p1h p2h host i1h i2h", defaults=(None, None, None))
 
 
 def _tinker_alpha_table():
@@ -58,6 +62,11 @@ class DeviceDict(MutableMapping):
         if fill and name in self._hint:
             self._ctx_getter().call("hmg_prefix_fill", d.ptr)
         return d
+
+    def on_device(self, name, shape):
+        """Is there a tensor of that name and shape?  No copy, no fill."""
+        d = self._dev.get(name)
+        return d is not None and d.shape == tuple(shape)
 
     def _pending(self, name):
         """True if a transform has left the prefix of this tensor unwritten since it was last filled."""
@@ -180,8 +189,8 @@ class HaloModel(Cosmology):
         # DESIGN.md section 3).  False (or HMG_NO_PREFIX_DEFERRAL=1): they write every tensor whole (A/B timing, tests).
         self.prefix_deferral = os.environ.get("HMG_NO_PREFIX_DEFERRAL", "0") != "1"
 
-        # (name, name2) -> (state version, P1h, P2h): a fused launch yields both terms, so the
-        # usual get_power_1halo(a,b) followed by get_power_2halo(a,b) streams the tensors once
+        # (name, name2) -> _Spectra: a fused launch yields both terms, so the usual get_power_1halo(a,b) followed by
+        # get_power_2halo(a,b) streams the tensors once; a batched launch enters every pair it computed, in both orders
         self._pcache = {}
         self.uk_profiles = DeviceDict(self._ctx, self._bump)
         self.pk_profiles = DeviceDict(self._ctx, self._bump)
@@ -804,38 +813,43 @@ class HaloModel(Cosmology):
             return trapz_lastaxis(fn2d(FN_BG_INTEGRAND, [self.nzm, Nc, Ns, self.bh]), self.ms) / ngal
 
     # ------------------------------------------------------------------ spectra
-    def _tracer(self, name, order, fill=True):
-        """Resolve a tracer name to an hmg_tracer.  `order` is the reference's lookup
-        order, which differs between the 1-halo (hods, uk, pk: hmvec.py:516-523) and the
-        2-halo (uk, pk, hods: hmvec.py:537-550) code paths.  fill=False: the tracer is for the batched mass
-        integrals (they read no deferred tile of a hinted tensor) or only its kind is wanted - nothing is enqueued."""
-        def tensor(dd, nm_):
+    # What a request becomes is decided in spectra.py, on records: a public call resolves each of its names once
+    # (_resolve) and hands the records on.
+    def _resolve(self, *names):
+        """One spectra.Resolved per name."""
+        memo = {}
+        for nm_ in names:
+            if nm_ not in memo:
+                memo[nm_] = spectra.resolve(nm_, self.hods, self.uk_profiles, self.pk_profiles)
+        return [memo[nm_] for nm_ in names]
+
+    def _resolve_pairs(self, pairs):
+        recs = self._resolve(*[nm_ for a, b in pairs for nm_ in (a, a if b is None else b)])
+        return list(zip(recs[0::2], recs[1::2]))
+
+    def _tracer(self, rec, term, fill=True):
+        """The hmg_tracer of a resolved name as the 1-halo (term 1) or the 2-halo lookup (term 2) finds it.  fill=False:
+        the tracer is for the batched mass integrals (they read no deferred tile of a hinted tensor) - nothing is enqueued."""
+        kind, tensors = rec.found(term)
+        shape = (self._nz, self._nm, self._nk)
+        got = []          # per tensor: its pointer and those of its hint arrays
+        for tag, nm_ in tensors:
+            dd = self.uk_profiles if tag == "uk" else self.pk_profiles
             # (a kernel trusts the pointer it is handed: a hand-assigned entry of another shape must stop here - numpy
             # would refuse to broadcast it in the reference, hmvec/hmvec.py:516-550)
             d_ = dd.dev(nm_, fill=fill)
-            if tuple(d_.shape) != (self._nz, self._nm, self._nk):
-                raise ValueError(f"profile {nm_!r} has shape {tuple(d_.shape)}, the model's grid is "
-                                 f"{(self._nz, self._nm, self._nk)}")
-            return d_
-        for kind in order:
-            dd = self.hods if kind == "h" else self.uk_profiles if kind == "m" else self.pk_profiles
-            if name not in dd:
-                continue
-            if kind == "h":
-                hod = dd[name]
-                cn = hod["central_profile"]
-                d = hod.dev
-                sn = hod["satellite_profile"]
-                hs = self.uk_profiles.hint(sn)
-                hc = self.uk_profiles.hint(cn) if cn is not None else (None, None)
-                return nat.Tracer(nat.TRACER_HOD, tensor(self.uk_profiles, sn).ptr,
-                                  None if cn is None else tensor(self.uk_profiles, cn).ptr,
-                                  d["Nc"].ptr, d["Ns"].ptr, d["NcNs"].ptr, d["NsNsm1"].ptr, d["ngal"].ptr, None,
-                                  nat.ptr(hs[0]), nat.ptr(hs[1]), nat.ptr(hc[0]), nat.ptr(hc[1])), kind
-            hp = dd.hint(name)
-            return nat.Tracer(nat.TRACER_MATTER if kind == "m" else nat.TRACER_PRESSURE, tensor(dd, name).ptr, None, None,
-                              None, None, None, None, None, nat.ptr(hp[0]), nat.ptr(hp[1])), kind
-        raise ValueError
+            if d_.shape != shape:
+                raise ValueError(f"profile {nm_!r} has shape {d_.shape}, the model's grid is {shape}")
+            nconst, cconst = dd.hint(nm_)
+            got.append((d_.ptr, nat.ptr(nconst), nat.ptr(cconst)))
+        prof, nconst, cconst = got[0]
+        if kind != "h":
+            return nat.Tracer(nat.TRACER_MATTER if kind == "m" else nat.TRACER_PRESSURE, prof, None, None, None, None, None,
+                              None, None, nconst, cconst)
+        d = self.hods[rec.name].dev
+        cprof, cnconst, ccconst = got[1] if len(got) > 1 else (None, None, None)
+        return nat.Tracer(nat.TRACER_HOD, prof, cprof, d["Nc"].ptr, d["Ns"].ptr, d["NcNs"].ptr, d["NsNsm1"].ptr, d["ngal"].ptr,
+                          None, nconst, cconst, cnconst, ccconst)
 
     def _power_launch(self, ta, tb, want1, want2, out1=None, out2=None):
         ctx = self._main(needs_aux=True)
@@ -856,14 +870,15 @@ class HaloModel(Cosmology):
     def power_device(self, name, name2=None, b1_in=None, b2_in=None, want=("1h", "2h"), out1=None, out2=None):
         """Device-resident (P1h, P2h) DeviceArrays of shape (nz, nk) — one fused pass over the
         profile tensors when the 1-halo and 2-halo code paths resolve the names identically."""
-        name2 = name if name2 is None else name2
+        return self._power_pair(*self._resolve(name, name if name2 is None else name2), b1_in, b2_in, want, out1, out2)
+
+    def _power_pair(self, ra, rb, b1_in=None, b2_in=None, want=("1h", "2h"), out1=None, out2=None):
         keep = []
         want1, want2 = "1h" in want, "2h" in want
+        same = ra.same and rb.same
         self._main()          # (the tracers below may enqueue a fill: on the lane of the transforms)
-        a1, ka1 = self._tracer(name, "hmp")
-        b1, kb1 = self._tracer(name2, "hmp")
-        a2, ka2 = self._tracer(name, "mph") if want2 else (a1, ka1)
-        b2, kb2 = self._tracer(name2, "mph") if want2 else (b1, kb1)
+        a1, b1 = self._tracer(ra, 1), self._tracer(rb, 1)
+        a2, b2 = (self._tracer(ra, 2), self._tracer(rb, 2)) if want2 and not same else (a1, b1)
         if want2:
             if b1_in is not None:
                 keep.append(self._ctx().upload(np.asarray(b1_in, dtype=np.float64).reshape(-1)))
@@ -872,7 +887,6 @@ class HaloModel(Cosmology):
                 n = b1_in.shape[0]     # reference reshapes b2_in with b1_in's length (hmvec.py:561)
                 keep.append(self._ctx().upload(np.asarray(b2_in, dtype=np.float64).reshape((n, 1))))
                 b2.d_bias_override = keep[-1].ptr
-        same = (ka1 == ka2) and (kb1 == kb2)
         if want1 and want2 and same:
             d1, d2 = self._power_launch(a2, b2, True, True, out1, out2)
         else:
@@ -886,52 +900,41 @@ class HaloModel(Cosmology):
         """(P1h, P2h) DeviceArrays for SEVERAL (name, name2) pairs with every distinct profile
         tensor streamed from HBM once for the whole batch (hmg_power_batch) instead of once
         per pair.  Falls back to one fused launch per pair when the batch cannot express the
-        reference's semantics (two different HOD / two different pressure names, a name that
-        the 1-halo and 2-halo code paths resolve differently, more than 4 tracers)."""
+        reference's semantics (spectra.batchable: two different HOD / two different pressure names, a name
+        that the 1-halo and 2-halo code paths resolve differently, more than 4 tracers)."""
+        return self._power_batch(self._resolve_pairs(pairs), outs1, outs2)
+
+    def _power_batch(self, pairs, outs1=None, outs2=None):
         ctx = self._ctx()
         nz, nm, nk = self._nz, self._nm, self._nk
-        pairs = [(a, a if b is None else b) for a, b in pairs]
-        names = []
-        for a, b in pairs:
-            for n_ in (a, b):
-                if n_ not in names:
-                    names.append(n_)
-        res1 = [self._tracer(n_, "hmp", fill=False) for n_ in names]
-        res2 = [self._tracer(n_, "mph", fill=False) for n_ in names]
-        kinds = {n_: r[1] for n_, r in zip(names, res1)}
-        batchable = len(names) <= 4 and all(r1[1] == r2[1] for r1, r2 in zip(res1, res2))
-        batchable = batchable and not any(a != b and kinds[a] == kinds[b] and kinds[a] in "hp"
-                                          for a, b in pairs)
+        recs, uniq, alias, first = spectra.pair_plan(pairs)
+        # (every tensor of the request is checked before anything is allocated or launched)
+        tr = [self._tracer(r, 1, fill=False) for r in recs]
+        for r in recs:
+            if not r.same:
+                self._tracer(r, 2, fill=False)
         o1 = [outs1[i] if outs1 is not None else ctx.empty((nz, nk)) for i in range(len(pairs))]
         o2 = [outs2[i] if outs2 is not None else ctx.empty((nz, nk)) for i in range(len(pairs))]
-        if not batchable:
+        if not spectra.batchable(recs, pairs):
             for i, (a, b) in enumerate(pairs):
-                self.power_device(a, b, out1=o1[i], out2=o2[i])
+                self._power_pair(a, b, out1=o1[i], out2=o2[i])
             return o1, o2
-        # (a,b) and (b,a) are the same spectrum here: compute each unordered pair once
-        uniq, alias = [], []
-        for a, b in pairs:
-            key = tuple(sorted((names.index(a), names.index(b))))
-            if key not in uniq:
-                uniq.append(key)
-            alias.append(uniq.index(key))
-        first = [alias.index(u) for u in range(len(uniq))]
         n = len(uniq)
         ctx = self._main(needs_aux=True)
-        tr = (nat.Tracer * len(names))(*[r[0] for r in res1])
+        tr = (nat.Tracer * len(recs))(*tr)
         pa = (C.c_int * n)(*[u[0] for u in uniq])
         pb = (C.c_int * n)(*[u[1] for u in uniq])
         p1 = (C.c_void_p * n)(*[o1[i].ptr for i in first])
         p2 = (C.c_void_p * n)(*[o2[i].ptr for i in first])
         d_wm, d_Pzk = self._d_wm(), self._d_Pzk()         # (uploads, if any, before the queue is issued)
-        desc = nat.PowerBatchDesc(len(names), tr, n, pa, pb, self._d_nzm.ptr, self._d_bh.ptr, self._d_ms().ptr,
+        desc = nat.PowerBatchDesc(len(recs), tr, n, pa, pb, self._d_nzm.ptr, self._d_bh.ptr, self._d_ms().ptr,
                                   d_wm.ptr, self._d_ks().ptr, d_Pzk.ptr, self._rho_m0(),
                                   float(self.p["kstar_damping"]), p1, p2)
         # the coefficient rows of this batch ride in the tensor / profile group of the queued stages, if there is one
         prepared = self._flush(prep=desc) if self._stages else False
         ctx.call("hmg_power_batch_run", nz, nm, nk, C.byref(desc), nat.PB_PREPARED if prepared else 0)
         self._sync_point()
-        for i, u in enumerate(alias):
+        for i, u in enumerate(alias):      # (a, b) and (b, a) are the same spectrum here: computed once, copied
             if first[u] != i:
                 ctx.call("hmg_memcpy_d2d", o1[i].ptr, o1[first[u]].ptr, o1[i].nbytes)
                 ctx.call("hmg_memcpy_d2d", o2[i].ptr, o2[first[u]].ptr, o2[i].nbytes)
@@ -948,139 +951,73 @@ class HaloModel(Cosmology):
     def get_power_all(self, pairs):
         """Extension of the reference API: {(name, name2): P_1h + P_2h} for several pairs in one
         pass over the profile tensors."""
-        seen = []
-        for a, b in pairs:
-            for nm_ in (a, a if b is None else b):
-                if nm_ not in seen:
-                    seen.append(nm_)
-        self._tsz_notice(*seen)
-        o1, o2 = self.power_device_batch(pairs)
+        rpairs = self._resolve_pairs(pairs)
+        self._tsz_notice(*dict.fromkeys(r for rp in rpairs for r in rp))
+        o1, o2 = self._power_batch(rpairs)
         return {tuple(p): self._sum_on_device(a, b) for p, a, b in zip(pairs, o1, o2)}
 
-    def _tsz_notice(self, *names):
+    @staticmethod
+    def _tsz_notice(*recs):
         """The reference prints this once per pressure tracer in every 2-halo evaluation
         (hmvec/hmvec.py:544)."""
-        for nm_ in names:
-            if nm_ not in self.uk_profiles and nm_ in self.pk_profiles:
+        for r in recs:
+            if r.kind2 == "p":
                 print("Check the consistency relation for tSZ")
-
-    def _tensor_names(self, nm_):
-        """Profile tensors a tracer streams, or None if the 1-halo and 2-halo code paths would
-        resolve the name differently (not batchable)."""
-        try:
-            k1, k2 = self._tracer(nm_, "hmp", fill=False)[1], self._tracer(nm_, "mph", fill=False)[1]
-        except (ValueError, KeyError):
-            return None
-        if k1 != k2:
-            return None
-        if k1 == "h":
-            hod = self.hods[nm_]
-            return {("uk", hod["satellite_profile"])} | (
-                {("uk", hod["central_profile"])} if hod["central_profile"] is not None else set())
-        return {("uk" if k1 == "m" else "pk", nm_)}
 
     _SMALL_GRID_BYTES = 32 << 20       # tensors up to this size: every registered tracer rides in the first batch
 
-    def _tensors_valid(self, tn):
-        shape = (self._nz, self._nm, self._nk)
-        for kind, nm_ in tn:
-            d = (self.uk_profiles if kind == "uk" else self.pk_profiles)._dev.get(nm_)
-            if d is None or tuple(d.shape) != shape:
-                return False
-        return True
-
-    def _free_riders(self, name, name2):
-        """Other registered tracers whose tensors are a subset of what (name, name2) streams
-        anyway: their spectra with each other and with the requested pair cost no extra HBM
-        traffic in the batched kernel, so they are computed in the same pass and cached."""
-        need = self._tensor_names(name)
-        need2 = self._tensor_names(name2)
-        if need is None or need2 is None:
-            return None
-        need = need | need2
-        kinds = {}
-        names = [name] + ([name2] if name2 != name else [])
-        # On a small grid (a tensor below 32 MB: the README grid's are 32 MB for all three) a tensor more in the batch
-        # costs microseconds while a batch more costs a launch and a result copy: every registered tracer rides along
-        # in the first request.  On a large grid only those whose tensors are streamed anyway.
-        small = self._nz * self._nm * self._nk * 8 <= self._SMALL_GRID_BYTES
-        for cand in list(self.hods) + list(self.uk_profiles) + list(self.pk_profiles):
-            if cand in names or len(names) >= 4:
-                continue
-            tn = self._tensor_names(cand)
-            # a rider must not be able to break the request it rides with: only tracers whose tensors are on the
-            # device in this model's (nz, nm, nk) shape (a hand-assigned uk_profiles entry can be anything)
-            if tn is not None and (tn <= need or small) and self._tensors_valid(tn):
-                names.append(cand)
-        for n_ in names:
-            kinds[n_] = self._tracer(n_, "hmp", fill=False)[1]
-        pairs = []
-        for i, a in enumerate(names):
-            for b in names[i:]:
-                # two different HOD (or pressure) names use the first name's square term in the
-                # reference (hmvec.py:510-513): order-dependent, leave those to the per-pair kernel
-                if a != b and kinds[a] == kinds[b] and kinds[a] in "hp":
-                    continue
-                pairs.append((a, b))
-        return pairs
-
-    def _power_cached(self, name, name2):
-        name2 = name if name2 is None else name2
-        ent = self._pcache.get((name, name2))
-        if ent is not None and ent[0] == self._version:
-            return ent[1], ent[2]
-        pairs = self._free_riders(name, name2)
+    def _power_cached(self, ra, rb):
+        """The cache entry of a pair, computed if it is not there or older than the model's state."""
+        ent = self._pcache.get((ra.name, rb.name))
+        if ent is not None and ent.version == self._version:
+            return ent
+        nz, nm, nk = self._nz, self._nm, self._nk
+        dicts = {"uk": self.uk_profiles, "pk": self.pk_profiles}
         # Batchable requests always go through the batched kernel, also when nothing rides along: a pair's
         # sums do not depend on what else is in the batch (foreign tensors enter with exact-zero coefficients),
         # so a spectrum has the same bits whatever was asked for before it.  The one-pair kernel (another
         # summation order, ~1e-16 away) is left with what the batch cannot do: bias overrides, the verbose
         # terms, names the 1-halo and 2-halo lookups resolve differently, two different HOD/pressure names.
-        if pairs and ((name, name2) in pairs or (name2, name) in pairs):
+        # On a small grid (a tensor below 32 MB: the README grid's are 32 MB for all three) every registered tracer rides.
+        registered = (spectra.resolve(nm_, self.hods, self.uk_profiles, self.pk_profiles)
+                      for nm_ in itertools.chain(self.hods, self.uk_profiles, self.pk_profiles))
+        pairs = spectra.with_riders(ra, rb, registered, lambda tag, nm_: dicts[tag].on_device(nm_, (nz, nm, nk)),
+                                    nz * nm * nk * 8 <= self._SMALL_GRID_BYTES)
+        if pairs:
             # every spectrum of the batch in ONE device block: the host side then fetches the block in one copy the
             # first time any of them is asked for (_HostBlock) instead of one synchronising copy per spectrum
             n = len(pairs)
-            blk = self._ctx().empty((2 * n, self._nz, self._nk))
-            per = self._nz * self._nk
-            o1 = [blk.view(i * per, (self._nz, self._nk)) for i in range(n)]
-            o2 = [blk.view((n + i) * per, (self._nz, self._nk)) for i in range(n)]
-            try:
-                self.power_device_batch(pairs, outs1=o1, outs2=o2)
-            except Exception:
-                # a rider turned out bad after all: the request itself must not fail for it - the minimal batch
-                minimal = [(a, b) for a, b in pairs if {a, b} <= {name, name2}]
-                if len(minimal) == len(pairs):
-                    raise
-                pairs, n = minimal, len(minimal)
-                o1 = [blk.view(i * per, (self._nz, self._nk)) for i in range(n)]
-                o2 = [blk.view((n + i) * per, (self._nz, self._nk)) for i in range(n)]
-                self.power_device_batch(pairs, outs1=o1, outs2=o2)
+            blk = self._ctx().empty((2 * n, nz, nk))
+            o1 = [blk.view(i * nz * nk, (nz, nk)) for i in range(n)]
+            o2 = [blk.view((n + i) * nz * nk, (nz, nk)) for i in range(n)]
+            # Issued once: what rides was validated above, so whatever this raises is a failure of the pass itself
+            # (its queued stages are gone with it) - it reaches the caller and nothing is cached.
+            self._power_batch(pairs, o1, o2)
             hb = _HostBlock(blk)
             for i, ((a, b), d1, d2) in enumerate(zip(pairs, o1, o2)):
-                self._pcache[(a, b)] = (self._version, d1, d2, hb, i, n + i)
-                self._pcache[(b, a)] = (self._version, d1, d2, hb, i, n + i)
+                self._pcache[(a.name, b.name)] = self._pcache[(b.name, a.name)] = _Spectra(self._version, d1, d2, hb, i, n + i)
         else:
-            d1, d2 = self.power_device(name, name2)
-            self._pcache[(name, name2)] = (self._version, d1, d2)
-        ent = self._pcache[(name, name2)]
-        return ent[1], ent[2]
+            self._pcache[(ra.name, rb.name)] = _Spectra(self._version, *self._power_pair(ra, rb))
+        return self._pcache[(ra.name, rb.name)]
 
-    def _power_host(self, name, name2, term):
+    def _power_host(self, ra, rb, term):
         """Host copy of P_1h (term 0) or P_2h (term 1) of a cached pair."""
-        d = self._power_cached(name, name2)
-        ent = self._pcache[(name, name if name2 is None else name2)]
-        if len(ent) > 3:
-            return ent[3].take(ent[4 + term])
-        return d[term].numpy()
+        ent = self._power_cached(ra, rb)
+        if ent.host is not None:
+            return ent.host.take((ent.i1h, ent.i2h)[term])
+        return (ent.p1h, ent.p2h)[term].numpy()
 
     def get_power(self, name, name2=None, verbose=False, b1=None, b2=None):
         """P_1h + P_2h in one pass (hmvec/hmvec.py:500-502)."""
-        self._tsz_notice(name, name if name2 is None else name2)
+        ra, rb = self._resolve(name, name if name2 is None else name2)
+        self._tsz_notice(ra, rb)
         if b1 is None and b2 is None:
-            d1, d2 = self._power_cached(name, name2)
+            ent = self._power_cached(ra, rb)
+            d1, d2 = ent.p1h, ent.p2h
         else:
-            d1, d2 = self.power_device(name, name2, b1, b2)
+            d1, d2 = self._power_pair(ra, rb, b1, b2)
         if verbose:
-            self._print_consistency(name, name2)
+            self._print_consistency(ra, rb)
         return self._sum_on_device(d1, d2)
 
     def _sum_on_device(self, d1, d2):
@@ -1092,35 +1029,38 @@ class HaloModel(Cosmology):
 
     def get_power_1halo(self, name="nfw", name2=None):
         """hmvec/hmvec.py:504-526."""
-        return self._power_host(name, name2, 0)
+        return self._power_host(*self._resolve(name, name if name2 is None else name2), 0)
 
     def get_power_2halo(self, name="nfw", name2=None, verbose=False, b1_in=None, b2_in=None):
         """hmvec/hmvec.py:528-572."""
-        self._tsz_notice(name, name if name2 is None else name2)
+        ra, rb = self._resolve(name, name if name2 is None else name2)
+        self._tsz_notice(ra, rb)
         if b1_in is None and b2_in is None:
-            out = self._power_host(name, name2, 1)
+            out = self._power_host(ra, rb, 1)
         else:
-            out = self.power_device(name, name2, b1_in, b2_in, want=("2h",))[1].numpy()
+            out = self._power_pair(ra, rb, b1_in, b2_in, want=("2h",))[1].numpy()
         if verbose:
-            self._print_consistency(name, name2)
+            self._print_consistency(ra, rb)
         return out
 
     def two_halo_terms(self, name, name2=None):
         """(I_1, C_1, I_2, C_2) of the 2-halo term (hmvec/hmvec.py:563-568): the mass integrals
         I(z,k) = int dm n b W(k), shape (nz,nk), and their k -> 0 consistency limits C(z), shape (nz,1)."""
-        name2 = name if name2 is None else name2
+        return self._two_halo_terms(*self._resolve(name, name if name2 is None else name2))
+
+    def _two_halo_terms(self, ra, rb):
         ctx = self._main(needs_aux=True)
         nz, nm, nk = self._nz, self._nm, self._nk
-        ta, tb = self._tracer(name, "mph")[0], self._tracer(name2, "mph")[0]
+        ta, tb = self._tracer(ra, 2), self._tracer(rb, 2)
         d_i1, d_i2, d_c = ctx.empty((nz, nk)), ctx.empty((nz, nk)), ctx.empty((nz, 2))
         ctx.call("hmg_power_2halo_terms", nz, nm, nk, C.byref(ta), C.byref(tb), self._d_nzm.ptr, self._d_bh.ptr,
                  self._d_ms().ptr, self._d_wm().ptr, self._d_ks().ptr, self._rho_m0(), d_i1.ptr, d_i2.ptr, d_c.ptr)
         c = d_c.numpy()
         return d_i1.numpy(), c[:, 0:1].copy(), d_i2.numpy(), c[:, 1:2].copy()
 
-    def _print_consistency(self, name, name2):
+    def _print_consistency(self, ra, rb):
         """The two lines get_power_2halo(verbose=True) prints (hmvec/hmvec.py:569-571)."""
-        i1, c1, i2, c2 = self.two_halo_terms(name, name2)
+        i1, c1, i2, c2 = self._two_halo_terms(ra, rb)
         print("Two-halo consistency1: ", c1, i1)
         print("Two-halo consistency2: ", c2, i2)
 

@@ -223,8 +223,10 @@ def _cl_prefactors(pksz):
 
 def _power_on_device(h, name, name2):
     """h.get_power(name, name2) left on the device: the P_1h and P_2h the model holds, added there."""
-    h._tsz_notice(name, name2)
-    d1, d2 = h._power_cached(name, name2)
+    ra, rb = h._resolve(name, name if name2 is None else name2)
+    h._tsz_notice(ra, rb)
+    ent = h._power_cached(ra, rb)
+    d1, d2 = ent.p1h, ent.p2h
     ctx = h._ctx()
     out = ctx.empty(d1.shape)
     ctx.call("hmg_add", d1.size, d1.ptr, d2.ptr, out.ptr)

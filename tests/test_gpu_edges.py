@@ -197,6 +197,43 @@ def test_free_rider_batching_matches_single_pair_kernel(small_grid_rule, monkeyp
     assert h._version == v and np.array_equal(p, h.get_power_1halo("nfw"))
 
 
+def test_the_cached_doors_agree_with_the_one_pair_kernel_for_every_pair_of_names():
+    """Every ordered pair of registered names through get_power_1halo / get_power_2halo against power_device, one
+    name being an HOD and a matter profile at once (the 1-halo lookup finds the HOD, the 2-halo lookup the profile:
+    such a pair is two launches of the one-pair kernel from either door, so the bits are equal; the other pairs come
+    from the batched kernel through the cache - another summation order, the 1e-12 of the free-rider test).  A second
+    call returns the same bits and leaves the state version alone."""
+    import hmvec_amd as hm
+    zs = np.array([0.3, 0.9])
+    ms = np.geomspace(1e11, 1e16, 12)
+    ks = np.geomspace(1e-3, 20, 20)
+    h = hm.HaloModel(zs, ks, ms=ms, accuracy="low", engine="analytic")
+    h.add_battaglia_profile("electron", nxs=200, xmax=20)
+    h.add_hod("g", mthresh=10 ** 10.5 + zs * 0.0)
+    h.add_hod("electron", mthresh=10 ** 11.0 + zs * 0.0, ignore_existing=True)
+    names = ["nfw", "electron", "g"]
+    ref = {}
+    for a in names:
+        for b in names:
+            d1, d2 = h.power_device(a, b)
+            ref[(a, b)] = (d1.numpy(), d2.numpy())
+    assert not np.array_equal(ref[("electron", "electron")][0], ref[("g", "g")][0])      # (the HOD named electron is another HOD)
+    v = h._version
+    for a in names:
+        for b in names:
+            got = h.get_power_1halo(a, b), h.get_power_2halo(a, b)
+            batched = "electron" not in (a, b)
+            assert (h._pcache[(a, b)].host is not None) == batched, (a, b)
+            for g, r in zip(got, ref[(a, b)]):
+                assert np.all(np.isfinite(g))
+                if batched:
+                    assert np.allclose(g, r, rtol=1e-12, atol=0), (a, b)
+                else:
+                    assert np.array_equal(g, r), (a, b)
+            again = h.get_power_1halo(a, b), h.get_power_2halo(a, b)
+            assert np.array_equal(again[0], got[0]) and np.array_equal(again[1], got[1]) and h._version == v, (a, b)
+
+
 def test_results_handed_out_are_the_callers_own_and_shared_inputs_survive_eviction():
     """Round 5 host-side sharing.  (a) A batch of spectra reaches the host in one copy and every get_power_* call hands
     out an array of the caller's own, as the reference does: writing into one result changes no later one.  (b) The device
