@@ -20,7 +20,7 @@ import numpy as np
 import scipy.constants as constants
 
 from . import _native as nat
-from . import spectra, stages
+from . import realspace, spectra, stages
 from .cosmology import Cosmology, _is_shared_product, sigma2_kgrid, sigma2_weights
 from .params import battaglia_defaults, default_params
 from .quadrature import gradient_is_uniform, simpson_weights, trapz_weights
@@ -1022,10 +1022,13 @@ class HaloModel(Cosmology):
 
     def _sum_on_device(self, d1, d2):
         """P_1h + P_2h added on the device: one array crosses PCIe (hmvec/hmvec.py:500-502)."""
+        return self._sum_device(d1, d2).numpy()
+
+    def _sum_device(self, d1, d2):
         ctx = self._ctx()
         out = ctx.empty(d1.shape)
         ctx.call("hmg_add", d1.size, d1.ptr, d2.ptr, out.ptr)
-        return out.numpy()
+        return out
 
     def get_power_1halo(self, name="nfw", name2=None):
         """hmvec/hmvec.py:504-526."""
@@ -1063,6 +1066,65 @@ class HaloModel(Cosmology):
         i1, c1, i2, c2 = self._two_halo_terms(ra, rb)
         print("Two-halo consistency1: ", c1, i1)
         print("Two-halo consistency2: ", c2, i2)
+
+    # ------------------------------------------------------------------ correlation functions
+    # xi(r) of the model's spectra: the rows stay on the device from the mass integrals to the transform
+    # (realspace.py); only the (nz, nr) results cross to the host.
+    _XI_TERMS = ("total", "1h", "2h")
+
+    def _xi_request(self, rs, term):
+        """The checked radii of a get_xi / get_xi_all call (everything that can be refused is, before any launch)."""
+        if term not in self._XI_TERMS:
+            raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
+        realspace.check_ks(self.ks)
+        return realspace.check_rs(rs)
+
+    def _xi_rows(self, d1, d2, term):
+        """The device rows a term transforms; "total" is the device sum get_power brings to the host."""
+        return d1 if term == "1h" else d2 if term == "2h" else self._sum_device(d1, d2)
+
+    def get_xi(self, rs, name="nfw", name2=None, term="total"):
+        """Correlation function xi(z, r), shape (nz, nr), of the spectrum of (name, name2) - of P_1h + P_2h
+        (term="total"), P_1h ("1h") or P_2h ("2h") - by the exact transform of realspace.xi_from_power: bit for bit
+        xi_from_power(ks, get_power(name, name2), rs) and its get_power_1halo / get_power_2halo counterparts."""
+        rs = self._xi_request(rs, term)
+        ra, rb = self._resolve(name, name if name2 is None else name2)
+        if term != "1h":          # (get_power and get_power_2halo print it, get_power_1halo does not)
+            self._tsz_notice(ra, rb)
+        if rs.size == 0:
+            return np.empty((self._nz, 0))
+        ent = self._power_cached(ra, rb)
+        rows = self._xi_rows(ent.p1h, ent.p2h, term)
+        return realspace.transform_rows(self._ctx(), self._d_ks(), rows, self._nz, self._nk, rs)
+
+    def get_xi_all(self, pairs, rs, term="total"):
+        """{(name, name2): xi(z, r)} for several pairs: their spectra from one pass over the profile tensors
+        (get_power_all's) and all of them through ONE transform launch of len(pairs) * nz rows.  Each entry is bit for
+        bit get_xi of that pair."""
+        rs = self._xi_request(rs, term)
+        pairs = [tuple(p) for p in pairs]
+        rpairs = self._resolve_pairs(pairs)
+        if term != "1h":
+            self._tsz_notice(*dict.fromkeys(r for rp in rpairs for r in rp))
+        n, nz, nk = len(pairs), self._nz, self._nk
+        if rs.size == 0 or n == 0:
+            return {p: np.empty((nz, rs.size)) for p in pairs}
+        ctx = self._ctx()
+        blk = ctx.empty((2 * n, nz, nk))
+        o1 = [blk.view(i * nz * nk, (nz, nk)) for i in range(n)]
+        o2 = [blk.view((n + i) * nz * nk, (nz, nk)) for i in range(n)]
+        if spectra.batchable(spectra.pair_plan(rpairs)[0], rpairs):
+            self._power_batch(rpairs, o1, o2)
+        else:
+            # one pair the batch cannot express sends all of them to the one-pair kernel there (another summation
+            # order): take each pair's spectra as get_xi does, so that the entries keep get_xi's bits
+            for (ra, rb), d1, d2 in zip(rpairs, o1, o2):
+                ent = self._power_cached(ra, rb)
+                ctx.call("hmg_memcpy_d2d", d1.ptr, ent.p1h.ptr, d1.nbytes)
+                ctx.call("hmg_memcpy_d2d", d2.ptr, ent.p2h.ptr, d2.nbytes)
+        rows = self._xi_rows(blk.view(0, (n * nz, nk)), blk.view(n * nz * nk, (n * nz, nk)), term)
+        xi = realspace.transform_rows(ctx, self._d_ks(), rows, n * nz, nk, rs).reshape(n, nz, rs.size)
+        return {p: xi[i] for i, p in enumerate(pairs)}
 
     # ------------------------------------------------------------------ cluster lensing (DESIGN.md section 10)
     # The per-halo scalars are formed on the host one lens redshift at a time (a few values per halo), so that a z slice

@@ -633,6 +633,16 @@ int hmg_ksz_limber_cl(hmg_ctx* ctx, int nell, int nchi, int nz, int nk, const do
                       const double* d_zn, const double* d_zs, const double* d_ks, const double* d_P, int squeezed,
                       double c2, double T2, double* d_out);
 
+/* ---- correlation function of tabulated spectra -------------------------------------------
+ * hmg_xi_transform: d_out (rows, nr), out[row, j] = xi(rs[j]) of the row d_P[row, :],
+ *   xi(r) = 1/(2 pi^2 r) int f~(k) sin(k r) dk,
+ * f~ the piecewise-linear interpolant of f_i = ks[i] P[row, i] on [ks[0], ks[nk-1]] and zero outside, the integral
+ * exact panel by panel (no quadrature in k r).  d_ks (nk >= 2) positive and strictly increasing, d_P (rows, nk) finite,
+ * d_rs (nr) positive, shared by all rows; the Python layer checks values, this checks shapes.  fp64, no atomics:
+ * bit-identical on repeat, and a row's results do not depend on the other rows or radii of the launch.            */
+int hmg_xi_transform(hmg_ctx* ctx, int rows, int nk, int nr, const double* d_ks, const double* d_P,
+                     const double* d_rs, double* d_out);
+
 /* ---- z-slab gather over RCCL/xGMI -------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */

@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip and ksz.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip and realspace.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -40,13 +40,14 @@ KERNELS = [   # (label, regex on the mangled name)
     ("ksz_nvv_shared_kernel  (N_vv, one k_S integral per z, ksz.hip)", r"21ksz_nvv_shared_kernelE"),
     ("ksz_nvv_rows_kernel  (N_vv, photo-z / per-row, ksz.hip)", r"19ksz_nvv_rows_kernelE"),
     ("ksz_limber_cl_kernel  (kSZ C_ell, ksz.hip)", r"20ksz_limber_cl_kernelE"),
+    ("xi_transform_kernel<256,4>  (correlation function, realspace.hip)", r"19xi_transform_kernelILi256ELi4EE"),
 ]
 
 
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
