@@ -13,10 +13,10 @@ from .halomodel import HaloModel  # noqa: F401
 from .functions import *  # noqa: F401,F403  (the reference's free functions, GPU-backed)
 from .fft import generic_profile_fft  # noqa: F401  (hmvec/hmvec.py:3 star-imports it into the package)
 from .lensing import delta_sigma_nfw, sigma_nfw  # noqa: F401  (cluster lensing: batched projected NFW profiles)
-from .realspace import xi_from_power  # noqa: F401  (correlation function of a tabulated spectrum)
+from .realspace import projected_from_power, xi_from_power  # noqa: F401  (xi(r) and the J0 / J2 transforms of a tabulated spectrum)
 from . import cosmology, fft, functions, ksz, lensing, params, quadrature, realspace, tinker, utils  # noqa: F401
 from .functions import __all__ as _fn_all
 
 __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "generic_profile_fft", "sigma_nfw",
-           "delta_sigma_nfw", "xi_from_power",
+           "delta_sigma_nfw", "xi_from_power", "projected_from_power",
            "fft", "tinker", "utils", "cosmology", "params"] + list(_fn_all)

@@ -1067,13 +1067,13 @@ class HaloModel(Cosmology):
         print("Two-halo consistency1: ", c1, i1)
         print("Two-halo consistency2: ", c2, i2)
 
-    # ------------------------------------------------------------------ correlation functions
-    # xi(r) of the model's spectra: the rows stay on the device from the mass integrals to the transform
-    # (realspace.py); only the (nz, nr) results cross to the host.
+    # ------------------------------------------------------- configuration-space statistics (DESIGN.md sections 13, 14)
+    # xi(r), w_p(r_p), Sigma(R) and Delta Sigma(R) of the model's spectra: the rows stay on the device from the mass
+    # integrals to the transform (realspace.py); only the (nz, nr) results cross to the host.
     _XI_TERMS = ("total", "1h", "2h")
 
     def _xi_request(self, rs, term):
-        """The checked radii of a get_xi / get_xi_all call (everything that can be refused is, before any launch)."""
+        """The checked radii of a transform request (everything that can be refused is, before any launch)."""
         if term not in self._XI_TERMS:
             raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
         realspace.check_ks(self.ks)
@@ -1083,24 +1083,29 @@ class HaloModel(Cosmology):
         """The device rows a term transforms; "total" is the device sum get_power brings to the host."""
         return d1 if term == "1h" else d2 if term == "2h" else self._sum_device(d1, d2)
 
-    def get_xi(self, rs, name="nfw", name2=None, term="total"):
-        """Correlation function xi(z, r), shape (nz, nr), of the spectrum of (name, name2) - of P_1h + P_2h
-        (term="total"), P_1h ("1h") or P_2h ("2h") - by the exact transform of realspace.xi_from_power: bit for bit
-        xi_from_power(ks, get_power(name, name2), rs) and its get_power_1halo / get_power_2halo counterparts."""
+    def _transform_rows(self, rows, nrows, rs, orders):
+        """The transforms of nrows device rows at the radii rs as a tuple of (nrows, nr) host arrays: (xi,) for
+        orders=None, else (W_n for n in orders), one launch either way."""
+        if orders is None:
+            return (realspace.transform_rows(self._ctx(), self._d_ks(), rows, nrows, self._nk, rs),)
+        return realspace.hankel_rows(self._ctx(), self._d_ks(), rows, nrows, self._nk, rs, orders)
+
+    def _realspace_pair(self, rs, name, name2, term, orders):
+        """What get_xi and the projected statistics of one pair share: the request's checks, the tSZ notice, the
+        pair's cached device spectra and one transform launch.  A tuple of (nz, nr) arrays (see _transform_rows)."""
         rs = self._xi_request(rs, term)
         ra, rb = self._resolve(name, name if name2 is None else name2)
         if term != "1h":          # (get_power and get_power_2halo print it, get_power_1halo does not)
             self._tsz_notice(ra, rb)
         if rs.size == 0:
-            return np.empty((self._nz, 0))
+            return tuple(np.empty((self._nz, 0)) for _ in (orders or (None,)))
         ent = self._power_cached(ra, rb)
-        rows = self._xi_rows(ent.p1h, ent.p2h, term)
-        return realspace.transform_rows(self._ctx(), self._d_ks(), rows, self._nz, self._nk, rs)
+        return self._transform_rows(self._xi_rows(ent.p1h, ent.p2h, term), self._nz, rs, orders)
 
-    def get_xi_all(self, pairs, rs, term="total"):
-        """{(name, name2): xi(z, r)} for several pairs: their spectra from one pass over the profile tensors
-        (get_power_all's) and all of them through ONE transform launch of len(pairs) * nz rows.  Each entry is bit for
-        bit get_xi of that pair."""
+    def _realspace_all(self, pairs, rs, term, orders):
+        """The same for several pairs: their spectra from one pass over the profile tensors (get_power_all's) into one
+        block and all of them through ONE transform launch of len(pairs) * nz rows.  (pairs, tuple of (n, nz, nr)
+        arrays); every [i] is bit for bit what _realspace_pair gives for pairs[i]."""
         rs = self._xi_request(rs, term)
         pairs = [tuple(p) for p in pairs]
         rpairs = self._resolve_pairs(pairs)
@@ -1108,7 +1113,7 @@ class HaloModel(Cosmology):
             self._tsz_notice(*dict.fromkeys(r for rp in rpairs for r in rp))
         n, nz, nk = len(pairs), self._nz, self._nk
         if rs.size == 0 or n == 0:
-            return {p: np.empty((nz, rs.size)) for p in pairs}
+            return pairs, tuple(np.empty((n, nz, rs.size)) for _ in (orders or (None,)))
         ctx = self._ctx()
         blk = ctx.empty((2 * n, nz, nk))
         o1 = [blk.view(i * nz * nk, (nz, nk)) for i in range(n)]
@@ -1117,14 +1122,66 @@ class HaloModel(Cosmology):
             self._power_batch(rpairs, o1, o2)
         else:
             # one pair the batch cannot express sends all of them to the one-pair kernel there (another summation
-            # order): take each pair's spectra as get_xi does, so that the entries keep get_xi's bits
+            # order): take each pair's spectra as the one-pair call does, so that the entries keep its bits
             for (ra, rb), d1, d2 in zip(rpairs, o1, o2):
                 ent = self._power_cached(ra, rb)
                 ctx.call("hmg_memcpy_d2d", d1.ptr, ent.p1h.ptr, d1.nbytes)
                 ctx.call("hmg_memcpy_d2d", d2.ptr, ent.p2h.ptr, d2.nbytes)
         rows = self._xi_rows(blk.view(0, (n * nz, nk)), blk.view(n * nz * nk, (n * nz, nk)), term)
-        xi = realspace.transform_rows(ctx, self._d_ks(), rows, n * nz, nk, rs).reshape(n, nz, rs.size)
+        return pairs, tuple(o.reshape(n, nz, rs.size) for o in self._transform_rows(rows, n * nz, rs, orders))
+
+    def get_xi(self, rs, name="nfw", name2=None, term="total"):
+        """Correlation function xi(z, r), shape (nz, nr), of the spectrum of (name, name2) - of P_1h + P_2h
+        (term="total"), P_1h ("1h") or P_2h ("2h") - by the exact transform of realspace.xi_from_power: bit for bit
+        xi_from_power(ks, get_power(name, name2), rs) and its get_power_1halo / get_power_2halo counterparts."""
+        return self._realspace_pair(rs, name, name2, term, None)[0]
+
+    def get_xi_all(self, pairs, rs, term="total"):
+        """{(name, name2): xi(z, r)} for several pairs: their spectra from one pass over the profile tensors
+        (get_power_all's) and all of them through ONE transform launch of len(pairs) * nz rows.  Each entry is bit for
+        bit get_xi of that pair."""
+        pairs, (xi,) = self._realspace_all(pairs, rs, term, None)
         return {p: xi[i] for i, p in enumerate(pairs)}
+
+    def get_wp(self, rps, name, name2=None, term="total"):
+        """Projected correlation function w_p(z, r_p), shape (nz, nr), of the spectrum of (name, name2) - term as for
+        get_xi - integrated along the whole line of sight (pi_max -> infinity): W_0 of
+        realspace.projected_from_power, bit for bit projected_from_power(ks, get_power(name, name2), rps).  r_p is
+        comoving, in the inverse units of ks; w_p has the units of P times those of ks squared (a length for a
+        three-dimensional spectrum)."""
+        return self._realspace_pair(rps, name, name2, term, (0,))[0]
+
+    def get_surface_density(self, Rs, name, name2=None, term="total"):
+        """Surface density Sigma(z, R) = rho_m0 W_0(R), shape (nz, nr), of the spectrum of (name, name2), e.g. P_gm -
+        term as for get_xi; W_0 of realspace.projected_from_power.  Comoving units: rho_m0 = rho_matter_z(0) is the
+        comoving matter density, R a comoving transverse distance in the inverse units of ks, Sigma a mass per comoving
+        area with the mean density's contribution left out (the line-of-sight integral of rho_m0 xi).  The physical
+        convention of sigma_2h_profiles (physical radius R_phys = R / (1 + z), mass per
+        physical area, at the angle theta = R_phys / d_A(z) = R / chi(z)) is
+        Sigma_phys(R_phys) = (1 + z)^2 Sigma(R_phys (1 + z))."""
+        w0 = self._realspace_pair(Rs, name, name2, term, (0,))[0]          # (the request is checked first)
+        return self._rho_m0() * w0
+
+    def get_excess_surface_density(self, Rs, name, name2=None, term="total"):
+        """Excess surface density Delta Sigma(z, R) = mean Sigma(< R) - Sigma(R) = rho_m0 W_2(R), shape (nz, nr), of
+        the spectrum of (name, name2); units and the conversion to the physical convention of
+        delta_sigma_2h_profiles as for get_surface_density: Delta Sigma_phys(R_phys) = (1 + z)^2 Delta Sigma(R_phys (1 + z))."""
+        w2 = self._realspace_pair(Rs, name, name2, term, (2,))[0]
+        return self._rho_m0() * w2
+
+    def get_wp_all(self, pairs, rps, term="total"):
+        """{(name, name2): w_p(z, r_p)} for several pairs, spectra and launches as for get_xi_all.  Each entry is bit
+        for bit get_wp of that pair."""
+        pairs, (wp,) = self._realspace_all(pairs, rps, term, (0,))
+        return {p: wp[i] for i, p in enumerate(pairs)}
+
+    def get_surface_density_all(self, pairs, Rs, term="total"):
+        """{(name, name2): (Sigma(z, R), Delta Sigma(z, R))} for several pairs, spectra as for get_xi_all and both
+        statistics from ONE transform launch.  Each entry is bit for bit get_surface_density and
+        get_excess_surface_density of that pair."""
+        pairs, (w0, w2) = self._realspace_all(pairs, Rs, term, (0, 2))
+        rho = self._rho_m0()
+        return {p: (rho * w0[i], rho * w2[i]) for i, p in enumerate(pairs)}
 
     # ------------------------------------------------------------------ cluster lensing (DESIGN.md section 10)
     # The per-halo scalars are formed on the host one lens redshift at a time (a few values per halo), so that a z slice

@@ -643,6 +643,16 @@ int hmg_ksz_limber_cl(hmg_ctx* ctx, int nell, int nchi, int nz, int nk, const do
 int hmg_xi_transform(hmg_ctx* ctx, int rows, int nk, int nr, const double* d_ks, const double* d_P,
                      const double* d_rs, double* d_out);
 
+/* ---- Hankel transforms of tabulated spectra: w_p, Sigma, Delta Sigma ----------------------
+ * hmg_hankel_transform: d_w0 and d_w2 (rows, nr), w0[row, j] = W_0(rs[j]) and w2[row, j] = W_2(rs[j]) of d_P[row, :],
+ *   W_n(R) = 1/(2 pi) int k P~(k) J_n(k R) dk,   n = 0, 2,
+ * P~ the interpolant of P that is linear in k^2 on each panel of [ks[0], ks[nk-1]] and zero outside, the integrals
+ * exact panel by panel.  Either output pointer may be NULL (that order is not computed), not both.  Arguments as for
+ * hmg_xi_transform; fp64, no atomics: bit-identical on repeat, a row's results do not depend on the other rows or radii
+ * of the launch, and an output does not depend on whether the other one was asked for.                             */
+int hmg_hankel_transform(hmg_ctx* ctx, int rows, int nk, int nr, const double* d_ks, const double* d_P,
+                         const double* d_rs, double* d_w0, double* d_w2);
+
 /* ---- z-slab gather over RCCL/xGMI -------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */

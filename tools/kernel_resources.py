@@ -41,6 +41,9 @@ KERNELS = [   # (label, regex on the mangled name)
     ("ksz_nvv_rows_kernel  (N_vv, photo-z / per-row, ksz.hip)", r"19ksz_nvv_rows_kernelE"),
     ("ksz_limber_cl_kernel  (kSZ C_ell, ksz.hip)", r"20ksz_limber_cl_kernelE"),
     ("xi_transform_kernel<256,4>  (correlation function, realspace.hip)", r"19xi_transform_kernelILi256ELi4EE"),
+    ("hankel_transform_kernel<256,4,true,false>  (W_0: w_p, Sigma; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb1ELb0EE"),
+    ("hankel_transform_kernel<256,4,false,true>  (W_2: Delta Sigma; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb0ELb1EE"),
+    ("hankel_transform_kernel<256,4,true,true>  (W_0 and W_2 from one pass; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb1ELb1EE"),
 ]
 
 

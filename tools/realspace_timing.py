@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Device time of the correlation-function transform (hmg_xi_transform) on GPU 0, one launch of
+"""Device time of the correlation-function transform (hmg_xi_transform) and of the Hankel
+transforms (hmg_hankel_transform: W_0 alone, W_2 alone and both from one launch; section 14) on GPU 0, one launch of
   * 6 spectra x nz 32 rows of nk 4096 at 64 radii (the Config-3 grid), and
   * 6 spectra x nz 20 rows of nk 1001 at 64 radii (the README grid).
 Rows are a matter-like spectrum with per-row amplitudes, radii geomspace(0.1, 200, 64).  Inputs are uploaded once; the
@@ -22,15 +23,15 @@ from hmvec_amd import _native as nat  # noqa: E402
 SLOT0 = 100       # event slots clear of HaloModel's (0-3) and bench.py's (40 and up)
 
 
-def timed(ctx, reps, warmup, batch, *args):
+def timed(ctx, reps, warmup, batch, entry, *args):
     for _ in range(warmup):
-        ctx.call("hmg_xi_transform", *args)
+        ctx.call(entry, *args)
     ctx.sync()
     ms = []
     for _ in range(reps):
         ctx.record(SLOT0)
         for _ in range(batch):
-            ctx.call("hmg_xi_transform", *args)
+            ctx.call(entry, *args)
         ctx.record(SLOT0 + 1)
         ctx.sync()
         ms.append(ctx.elapsed_ms(SLOT0, SLOT0 + 1) / batch)
@@ -48,14 +49,19 @@ def main():
     rs = np.geomspace(0.1, 200, 64)
     d_rs = ctx.upload(rs)
     res = {}
-    for label, rows, nk in (("xi_6x32_rows_nk4096_nr64", 6 * 32, 4096), ("xi_6x20_rows_nk1001_nr64", 6 * 20, 1001)):
+    for shape, rows, nk in (("6x32_rows_nk4096_nr64", 6 * 32, 4096), ("6x20_rows_nk1001_nr64", 6 * 20, 1001)):
         ks = np.geomspace(1e-4, 100, nk)
         P = rng.uniform(0.5, 2.0, (rows, 1)) * (2e4 * (ks / 0.02) / (1 + (ks / 0.02) ** 2) ** 1.9)[None, :]
-        d_ks, d_P, out = ctx.upload(ks), ctx.upload(P), ctx.empty((rows, rs.size))
-        res[label] = timed(ctx, a.reps, a.warmup, a.batch, rows, nk, rs.size, d_ks.ptr, d_P.ptr, d_rs.ptr, out.ptr)
-        xi = out.numpy()
-        assert np.all(np.isfinite(xi)) and np.all(xi[:, 0] > 0)
-        res[label]["panel_radius_pairs"] = rows * (nk - 1) * rs.size
+        d_ks, d_P, out, out2 = ctx.upload(ks), ctx.upload(P), ctx.empty((rows, rs.size)), ctx.empty((rows, rs.size))
+        common = (rows, nk, rs.size, d_ks.ptr, d_P.ptr, d_rs.ptr)
+        for label, entry, outs in (("xi", "hmg_xi_transform", (out.ptr,)), ("w0", "hmg_hankel_transform", (out.ptr, None)),
+                                   ("w2", "hmg_hankel_transform", (None, out2.ptr)),
+                                   ("w0_w2", "hmg_hankel_transform", (out.ptr, out2.ptr))):
+            label = f"{label}_{shape}"
+            res[label] = timed(ctx, a.reps, a.warmup, a.batch, entry, *common, *outs)
+            res[label]["panel_radius_pairs"] = rows * (nk - 1) * rs.size
+            got = out.numpy()
+            assert np.all(np.isfinite(got)) and np.all(got[:, 0] > 0) and np.all(np.isfinite(out2.numpy()))
     res["kernel_source_sha16"] = nat.kernel_source_sha16()
     print(json.dumps(res))
     ctx.close()
