@@ -198,6 +198,8 @@ SIGNATURES = {
     "hmg_ksz_limber_cl": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _D, _D, _P],
     "hmg_xi_transform": [_P, _I, _I, _I, _P, _P, _P, _P],
     "hmg_hankel_transform": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "hmg_trispectrum_1h": [_P, _I, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), C.POINTER(Tracer), C.POINTER(Tracer),
+                           _P, _P, _P, _D, _P, _P, _P, _P, _P, _P],
     "hmg_comm_unique_id": [C.c_char * COMM_ID_BYTES],
     "hmg_comm_init": [_P, C.c_char * COMM_ID_BYTES, _I, _I],
     "hmg_comm_allgather": [_P, _P, _P, _Z],
@@ -221,7 +223,7 @@ def kernel_source_sha16():
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
     names = ["hmgrid.hip", "longgrid.hip", "longgrid.hpp", "rowdev.hpp", "sici.hpp", "ldsfft.hpp", "fastmath.hpp", "Makefile",
-             "lensing.hip", "j0.hpp", "j1.hpp", "ksz.hip", "realspace.hip", "j01.hpp"]
+             "lensing.hip", "j0.hpp", "j1.hpp", "ksz.hip", "realspace.hip", "j01.hpp", "trispectrum.hip"]
     names += sorted(os.path.join("kernels", n) for n in os.listdir(os.path.join(csrc, "kernels")) if n.endswith(".hpp"))
     for name in names:          # (runtime.hip / comm.hip / hmctx.hpp hold no device code: not part of the kernel identity)
         with open(os.path.join(csrc, name), "rb") as f:
@@ -407,6 +409,14 @@ class Context:
         a = np.ascontiguousarray(arr, dtype=np.float64)
         d = self.empty(a.shape)          # (a recycled block: its last owner released it, and owners of queued
                                          # stages issue the queue before they release anything - DeviceArray.free)
+        check(self.lib.hmg_memcpy_h2d(self.handle, d.ptr, a.ctypes.data, a.nbytes))
+        return d
+
+    def upload_int32(self, arr):
+        """A host integer array as 32-bit ints on the device: a DeviceArray whose block holds them packed (two per fp64
+        slot; its shape counts slots, not ints)."""
+        a = np.ascontiguousarray(arr, dtype=np.int32)
+        d = self.empty(((a.size + 1) // 2,))
         check(self.lib.hmg_memcpy_h2d(self.handle, d.ptr, a.ctypes.data, a.nbytes))
         return d
 

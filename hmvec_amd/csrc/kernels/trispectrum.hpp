@@ -1,0 +1,199 @@
+// 1-halo trispectrum of two spectra:
+//     T[z,i,j] = sum_m wm[m] nzm[z,m] s_ab[z,m,i] s_cd[z,m,j],
+// s the sampled square term of get_power_1halo.  Included by trispectrum.hip alone (its own translation unit: the
+// headline path's units do not see these kernels).  The tracer logic restates tracer_form / power_prep_kernel of
+// kernels/power.hpp, which is not a stand-alone header.
+#pragma once
+
+namespace hmg {
+
+constexpr int TRI_TILE = 64;        // samples per tile side
+constexpr int TRI_CHUNK = 32;       // mass bins staged through LDS at a time
+constexpr int TRI_THREADS = 256;    // 16 x 16 threads, a 4 x 4 register block each
+constexpr int TRI_MAXT = 4;         // distinct tensors of one pair
+constexpr int TRI_NC = 1 + TRI_MAXT;
+
+struct TriTracer {
+    int kind;
+    int t_prof, t_cprof;            // slots in the pair's tensor list, -1 = none
+    const double *Nc, *Ns, *NcNs, *NsNsm1, *ngal;
+};
+struct TriSide {                    // one spectrum (a, b): its square term is form1 * form2
+    TriTracer a, b;
+    int nt;
+    const double* tens[TRI_MAXT];
+};
+struct TriArgs {
+    TriSide ab, cd;
+    const double *nzm, *ms, *wm;
+    double rho_m0;
+    const int* idx;                 // [nz][n] left node
+    const double *frac, *scale;     // [nz][n]
+    double* T;                      // [nz][n][n]
+    int nm, nk, n;
+};
+
+// c[0..TRI_NC) += the linear form of one tracer's 1-halo weight (c lives in LDS: the slots are run-time indices)
+__device__ __forceinline__ void tri_tracer_form(const TriTracer& T, size_t zm, int z, double mass, double rho_m0,
+                                                double* c) {
+    if (T.kind == HMG_TRACER_MATTER) {
+        c[1 + T.t_prof] += mass / rho_m0;
+    } else if (T.kind == HMG_TRACER_PRESSURE) {
+        c[1 + T.t_prof] += 1.0;
+    } else {
+        const double ng = T.ngal[z], nc = T.Nc[zm], ns = T.Ns[zm];
+        if (T.t_cprof >= 0) c[1 + T.t_cprof] += nc / ng; else c[0] += nc / ng;
+        c[1 + T.t_prof] += ns / ng;
+    }
+}
+
+// the two linear forms x1, x2 of the square term S = x1 * x2 of one spectrum at (z, m) (hmvec/hmvec.py:510-523)
+__device__ __forceinline__ void tri_square_forms(const TriSide& S, size_t zm, int z, double mass, double rho_m0,
+                                                 double* x1, double* x2) {
+    for (int i = 0; i < TRI_NC; ++i) x1[i] = x2[i] = 0.0;
+    if (S.a.kind == HMG_TRACER_HOD && S.b.kind == HMG_TRACER_HOD) {
+        // (2 u_c u_s <NcNs> + <Ns(Ns-1)> u_s^2)/ngal^2 of the FIRST name
+        const double ng = S.a.ngal[z], ng2 = ng * ng;
+        x1[1 + S.a.t_prof] = 1.0;
+        const double cc = 2.0 * S.a.NcNs[zm] / ng2;
+        if (S.a.t_cprof >= 0) x2[1 + S.a.t_cprof] += cc; else x2[0] += cc;
+        x2[1 + S.a.t_prof] += S.a.NsNsm1[zm] / ng2;
+    } else if (S.a.kind == HMG_TRACER_PRESSURE && S.b.kind == HMG_TRACER_PRESSURE) {
+        // pk_a**2 - first name only
+        tri_tracer_form(S.a, zm, z, mass, rho_m0, x1);
+        tri_tracer_form(S.a, zm, z, mass, rho_m0, x2);
+    } else {
+        tri_tracer_form(S.a, zm, z, mass, rho_m0, x1);
+        tri_tracer_form(S.b, zm, z, mass, rho_m0, x2);
+    }
+}
+
+// S(z, m, node) = x1(node) * x2(node) of one spectrum; `at` is the offset of (z, m, node) in its tensors
+__device__ __forceinline__ double tri_square_at(const TriSide& S, const double* x1, const double* x2, size_t at) {
+    double f1 = x1[0], f2 = x2[0];
+#pragma unroll
+    for (int t = 0; t < TRI_MAXT; ++t) {
+        if (t < S.nt) {
+            const double v = S.tens[t][at];
+            f1 = fma(x1[1 + t], v, f1);
+            f2 = fma(x2[1 + t], v, f2);
+        }
+    }
+    return f1 * f2;
+}
+
+// stage the interpolated square term of one spectrum at (z, m0 + ml, sample first + il) for ml < mc into dst[ml][il];
+// the thread's sample il = tid % 64 is the same for all of its elements, so its table entry (id, f) is read once by
+// the caller.  The scale does not depend on m: it multiplies the finished sum (the kernel's last step).
+__device__ __forceinline__ void tri_stage(const TriSide& S, const double* cf /*[TRI_CHUNK][2][TRI_NC]*/, double* dst,
+                                          int z, int m0, int mc, int nm, int nk, bool live, int id, double f) {
+    const int il = threadIdx.x & (TRI_TILE - 1), w = threadIdx.x >> 6;
+#pragma unroll 2
+    for (int ml = w; ml < mc; ml += TRI_THREADS / TRI_TILE) {
+        double s = 0.0;
+        if (live) {
+            const double* x1 = cf + ml * (2 * TRI_NC);
+            const double* x2 = x1 + TRI_NC;
+            const size_t at = ((size_t)z * nm + (m0 + ml)) * (size_t)nk + id;
+            s = tri_square_at(S, x1, x2, at);
+            if (f != 0.0) s = fma(f, tri_square_at(S, x1, x2, at + 1), (1.0 - f) * s);   // node id + 1 is read only here
+        }
+        dst[ml * TRI_TILE + il] = s;
+    }
+}
+
+// grid (tiles of j, tiles of i, nz), TRI_THREADS threads.  Each workgroup walks the whole mass axis itself, in order:
+// no split over workgroups, no atomics - an element depends on its own (z, i, j), the tables and the tensors alone.
+// The weight wm * nzm multiplies the product of the two sides (it is not folded into one of them), and the finished
+// sum is multiplied by scale_i * scale_j as one factor: every step is symmetric in the two sides, so exchanging the
+// two spectra and transposing gives the same bits, and a scale is applied once, not once per mass bin.
+__global__ __launch_bounds__(TRI_THREADS) void trispectrum_1h_kernel(TriArgs A) {
+    __shared__ __align__(16) double sA[TRI_CHUNK * TRI_TILE], sB[TRI_CHUNK * TRI_TILE];
+    __shared__ double cfA[TRI_CHUNK * 2 * TRI_NC], cfB[TRI_CHUNK * 2 * TRI_NC];
+    __shared__ double sW[TRI_CHUNK];
+    const int tid = threadIdx.x;
+    const int z = blockIdx.z, i0 = blockIdx.y * TRI_TILE, j0 = blockIdx.x * TRI_TILE;
+    const int tx = tid & 15, ty = tid >> 4;
+    // this thread's sample of each side in the loader
+    const int il = tid & (TRI_TILE - 1);
+    const bool liveA = i0 + il < A.n, liveB = j0 + il < A.n;
+    int idA = 0, idB = 0;
+    double fA = 0.0, fB = 0.0;
+    if (liveA) { const size_t o = (size_t)z * A.n + i0 + il; idA = A.idx[o]; fA = A.frac[o]; }
+    if (liveB) { const size_t o = (size_t)z * A.n + j0 + il; idB = A.idx[o]; fB = A.frac[o]; }
+
+    double acc[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = 0.0;
+
+    for (int m0 = 0; m0 < A.nm; m0 += TRI_CHUNK) {
+        const int mc = min(TRI_CHUNK, A.nm - m0);
+        __syncthreads();                       // the previous chunk has been consumed
+        if (tid < 2 * TRI_CHUNK) {             // the coefficient rows of the chunk: one thread per (side, m)
+            const int ml = tid & (TRI_CHUNK - 1);
+            if (ml < mc) {
+                const size_t zm = (size_t)z * A.nm + m0 + ml;
+                const double mass = A.ms[m0 + ml];
+                if (tid < TRI_CHUNK) {
+                    tri_square_forms(A.ab, zm, z, mass, A.rho_m0, cfA + ml * (2 * TRI_NC), cfA + ml * (2 * TRI_NC) + TRI_NC);
+                    sW[ml] = A.wm[m0 + ml] * A.nzm[zm];
+                } else {
+                    tri_square_forms(A.cd, zm, z, mass, A.rho_m0, cfB + ml * (2 * TRI_NC), cfB + ml * (2 * TRI_NC) + TRI_NC);
+                }
+            }
+        }
+        __syncthreads();
+        tri_stage(A.ab, cfA, sA, z, m0, mc, A.nm, A.nk, liveA, idA, fA);
+        tri_stage(A.cd, cfB, sB, z, m0, mc, A.nm, A.nk, liveB, idB, fB);
+        __syncthreads();
+#pragma unroll 4
+        for (int ml = 0; ml < mc; ++ml) {
+            const double w = sW[ml];
+            const double2 a01 = *reinterpret_cast<const double2*>(&sA[ml * TRI_TILE + ty * 4]);
+            const double2 a23 = *reinterpret_cast<const double2*>(&sA[ml * TRI_TILE + ty * 4 + 2]);
+            const double2 b01 = *reinterpret_cast<const double2*>(&sB[ml * TRI_TILE + tx * 4]);
+            const double2 b23 = *reinterpret_cast<const double2*>(&sB[ml * TRI_TILE + tx * 4 + 2]);
+            const double a[4] = {a01.x, a01.y, a23.x, a23.y}, b[4] = {b01.x, b01.y, b23.x, b23.y};
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc[r][c] = fma(a[r] * b[c], w, acc[r][c]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = i0 + ty * 4 + r;
+        if (i >= A.n) continue;
+        double* out = A.T + ((size_t)z * A.n + i) * (size_t)A.n;
+        const double sci = A.scale[(size_t)z * A.n + i];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int j = j0 + tx * 4 + c;
+            if (j < A.n) out[j] = acc[r][c] * (sci * A.scale[(size_t)z * A.n + j]);
+        }
+    }
+}
+
+// Tz[i,j] = sum_z g[z] T[z,i,j], z in order; one thread per (i, j)
+__global__ __launch_bounds__(256) void trispectrum_zsum_kernel(int nz, size_t nn, const double* __restrict__ g,
+                                                               const double* __restrict__ T, double* __restrict__ Tz) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nn) return;
+    double s = 0.0;
+    for (int z = 0; z < nz; ++z) s = fma(g[z], T[(size_t)z * nn + e], s);
+    Tz[e] = s;
+}
+
+// raises *bad if a sample's left node is off the grid, its fraction outside [0, 1], or it would read node nk
+__global__ __launch_bounds__(256) void trispectrum_check_kernel(size_t count, int nk, const int* __restrict__ idx,
+                                                                const double* __restrict__ frac, int* __restrict__ bad) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= count) return;
+    const int id = idx[e];
+    const double f = frac[e];
+    if (id < 0 || id >= nk || !(f >= 0.0 && f <= 1.0) || (id == nk - 1 && f != 0.0)) *bad = 1;
+}
+
+}  // namespace hmg

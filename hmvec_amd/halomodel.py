@@ -1183,6 +1183,98 @@ class HaloModel(Cosmology):
         rho = self._rho_m0()
         return {p: (rho * w0[i], rho * w2[i]) for i, p in enumerate(pairs)}
 
+    # ------------------------------------------------------------------ 1-halo trispectrum
+    # T[z,i,j] = sum_m wm nzm s_ab[z,m,i] s_cd[z,m,j]: the mass integral of get_power_1halo with one more free index,
+    # contracted on the device over the resident tensors (hmg_trispectrum_1h); only (nz, n, n) or (n, n) results cross.
+    TRISPECTRUM_MAX_SAMPLES = 1024
+
+    def _trispectrum_tables(self, kindex, idx, frac, scale, damping):
+        """The checked (nz, n) sample tables of a trispectrum request: int32 idx, frac, scale (damping folded in).
+        Everything that can be refused is, here, before any launch."""
+        nz, nk = self._nz, self._nk
+        if idx is None:
+            if frac is not None:
+                raise ValueError("frac needs idx")
+            kindex = np.arange(nk) if kindex is None else np.asarray(kindex)
+            if kindex.ndim != 1 or not np.issubdtype(kindex.dtype, np.integer):
+                raise ValueError("kindex must be a one-dimensional integer array of indices into ks")
+            idx = np.broadcast_to(kindex[None, :], (nz, kindex.size))
+        else:
+            if kindex is not None:
+                raise ValueError("give kindex or the idx / frac tables, not both")
+            idx = np.asarray(idx)
+            if not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError("idx must be an integer array")
+            if idx.ndim == 1:
+                idx = np.broadcast_to(idx[None, :], (nz, idx.size))
+            if idx.ndim != 2 or idx.shape[0] != nz:
+                raise ValueError(f"idx must have shape (n,) or (nz, n) with nz = {nz}, got {idx.shape}")
+        n = idx.shape[1]
+        if n < 1:
+            raise ValueError("kindex / idx is empty: the trispectrum needs at least one sample")
+        if n > self.TRISPECTRUM_MAX_SAMPLES:
+            raise ValueError(f"kindex / idx asks for {n} samples per redshift; at most {self.TRISPECTRUM_MAX_SAMPLES} "
+                             f"are taken (the result has nz * n * n entries): pass a shorter kindex")
+        if idx.min() < 0 or idx.max() > nk - 1:
+            raise ValueError(f"kindex / idx must lie in 0 .. nk - 1 = {nk - 1}, got {idx.min()} .. {idx.max()}")
+        frac = np.zeros((nz, n)) if frac is None else np.broadcast_to(np.asarray(frac, dtype=np.float64), (nz, n))
+        if not np.all((frac >= 0.0) & (frac <= 1.0)):
+            raise ValueError("frac must lie in [0, 1]")
+        if np.any((idx == nk - 1) & (frac != 0.0)):
+            raise ValueError("idx = nk - 1 needs frac = 0 (there is no node to its right)")
+        scale = np.ones((nz, n)) if scale is None else np.broadcast_to(np.asarray(scale, dtype=np.float64), (nz, n))
+        if not np.all(np.isfinite(scale)):
+            raise ValueError("scale must be finite")
+        if damping:
+            ks = self.ks
+            k = np.where(frac == 0.0, ks[idx], (1.0 - frac) * ks[idx] + frac * ks[np.minimum(idx + 1, nk - 1)])
+            scale = scale * (1.0 - np.exp(-(k / self.p["kstar_damping"]) ** 2.0))
+        return (np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(frac, dtype=np.float64),
+                np.ascontiguousarray(scale, dtype=np.float64))
+
+    def trispectrum_device(self, name, name2=None, name3=None, name4=None, kindex=None, damping=True, idx=None,
+                           frac=None, scale=None, zweights=None, per_z=True):
+        """(T, Tz) on the device: T (nz, n, n) the 1-halo trispectrum of the spectra (name, name2) and (name3, name4) -
+        per_z=False: None - and Tz (n, n) = sum_z zweights[z] T[z], in z order, if zweights (nz,) is given, else None.
+
+        Samples: kindex (nodes of ks, the same for every z; default all of them), or tables idx / frac (n,) or (nz, n) -
+        sample i of redshift z is the square term interpolated linearly between the nodes idx and idx + 1 at the
+        fraction frac (default 0; idx = nk - 1 needs frac = 0), times scale (default 1).  damping=True multiplies scale
+        by 1 - exp(-(k / kstar)^2) at the sample's wavenumber, as get_power_1halo damps P_1h.  At most 1024 samples.
+        name3 / name4 default to the first pair; the square terms are get_power_1halo's, first-name-only rules
+        included."""
+        name2 = name if name2 is None else name2
+        name3, name4 = (name if name3 is None else name3), (name2 if name4 is None else name4)
+        recs = self._resolve(name, name2, name3, name4)
+        t_idx, t_frac, t_scale = self._trispectrum_tables(kindex, idx, frac, scale, damping)
+        if zweights is not None:
+            zweights = np.ascontiguousarray(zweights, dtype=np.float64).reshape(-1)
+            if zweights.size != self._nz:
+                raise ValueError(f"zweights must have one entry per redshift ({self._nz}), got {zweights.size}")
+        elif not per_z:
+            raise ValueError("nothing asked for: per_z=False needs zweights")
+        nz, nm, nk, n = self._nz, self._nm, self._nk, t_idx.shape[1]
+        ctx = self._main(needs_aux=True)
+        # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
+        tr = [self._tracer(r, 1) for r in recs]
+        d_idx, d_frac, d_scale = ctx.upload_int32(t_idx), ctx.upload(t_frac), ctx.upload(t_scale)
+        d_g = ctx.upload(zweights) if zweights is not None else None
+        T = ctx.empty((nz, n, n)) if per_z else None
+        Tz = ctx.empty((n, n)) if zweights is not None else None
+        ctx.call("hmg_trispectrum_1h", nz, nm, nk, n, *(C.byref(t) for t in tr), self._d_nzm.ptr, self._d_ms().ptr,
+                 self._d_wm().ptr, self._rho_m0(), d_idx.ptr, d_frac.ptr, d_scale.ptr, nat.ptr(d_g), nat.ptr(T),
+                 nat.ptr(Tz))
+        self._sync_point()
+        return T, Tz          # (the tables go back to the free list: whatever reads them was enqueued before)
+
+    def get_trispectrum_1halo(self, name, name2=None, name3=None, name4=None, kindex=None, damping=True):
+        """1-halo trispectrum T(z; k_i, k_j) = int dm n(z,m) S_ab(z,m,k_i) S_cd(z,m,k_j), shape (nz, n, n), of the spectra
+        (name, name2) and (name3, name4; default: the first pair) at the nodes ks[kindex] (default: all; at most 1024).
+        S is the square term get_power_1halo integrates, so without damping T[z,i,i] of a pair with itself is the mass
+        integral of its square.  damping=True (default) multiplies by D(k_i) D(k_j), D = 1 - exp(-(k/kstar)^2), which
+        makes T consistent with the damped P_1h the model returns; damping=False leaves it out."""
+        return self.trispectrum_device(name, name2, name3, name4, kindex=kindex, damping=damping)[0].numpy()
+
     # ------------------------------------------------------------------ cluster lensing (DESIGN.md section 10)
     # The per-halo scalars are formed on the host one lens redshift at a time (a few values per halo), so that a z slice
     # of a model with several redshifts is the same computation as a model of that redshift alone.  With one redshift

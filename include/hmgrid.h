@@ -653,6 +653,27 @@ int hmg_xi_transform(hmg_ctx* ctx, int rows, int nk, int nr, const double* d_ks,
 int hmg_hankel_transform(hmg_ctx* ctx, int rows, int nk, int nr, const double* d_ks, const double* d_P,
                          const double* d_rs, double* d_w0, double* d_w2);
 
+/* ---- 1-halo trispectrum of two spectra -----------------------------------------------------
+ * hmg_trispectrum_1h: d_T (nz, n, n),
+ *   T[z,i,j] = sum_m wm[m] nzm[z,m] s_ab[z,m,i] s_cd[z,m,j],
+ *   s_xy[z,m,i] = scale[z,i] ((1 - frac[z,i]) S_xy(z, m, k_idx[z,i]) + frac[z,i] S_xy(z, m, k_{idx[z,i]+1})),
+ * (scale does not depend on m: the sum is taken without it and multiplied by scale[z,i] scale[z,j] as one factor),
+ * S_xy the square term hmg_power integrates for the pair (x, y), with the reference's first-name-only rules for two HOD
+ * and two pressure names (hmvec/hmvec.py:510-523).  Node idx + 1 is not read where frac == 0, so idx = nk-1 with
+ * frac = 0 is legal.  d_Tz (n, n) = sum_z zweights[z] T[z], z in order, needs d_zweights; either output may be NULL,
+ * not both (d_T NULL: the per-z matrices live in a temporary block).  n >= 1.  The tables are checked on the device
+ * before any tensor is read through them - an idx outside 0 .. nk-1, a frac outside [0, 1], idx == nk-1 with
+ * frac != 0 are errors - and the host waits for that answer: the call synchronises the current stream once and cannot be
+ * part of a captured step.  Tracers as for hmg_power (hints and bias overrides are not read).  fp64 on the vector
+ * units, every workgroup walks the whole mass axis in order, no atomics: bit-identical on repeat, an element depends
+ * only on its own (z, i, j) sample entries, and T^{ab,cd}[z,i,j] has the bits of T^{cd,ab}[z,j,i].                  */
+int hmg_trispectrum_1h(hmg_ctx* ctx, int nz, int nm, int nk, int n,
+                       const hmg_tracer* h_a, const hmg_tracer* h_b, const hmg_tracer* h_c, const hmg_tracer* h_d,
+                       const double* d_nzm, const double* d_ms, const double* d_wm, double rho_m0,
+                       const int* d_idx /*[nz][n]*/, const double* d_frac, const double* d_scale,
+                       const double* d_zweights /*[nz] or NULL*/,
+                       double* d_T /*[nz][n][n] or NULL*/, double* d_Tz /*[n][n] or NULL*/);
+
 /* ---- z-slab gather over RCCL/xGMI -------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */

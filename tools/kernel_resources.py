@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip and realspace.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip and trispectrum.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -44,13 +44,16 @@ KERNELS = [   # (label, regex on the mangled name)
     ("hankel_transform_kernel<256,4,true,false>  (W_0: w_p, Sigma; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb1ELb0EE"),
     ("hankel_transform_kernel<256,4,false,true>  (W_2: Delta Sigma; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb0ELb1EE"),
     ("hankel_transform_kernel<256,4,true,true>  (W_0 and W_2 from one pass; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb1ELb1EE"),
+    ("trispectrum_1h_kernel  (1-halo trispectrum, 64 x 64 tile, trispectrum.hip)", r"21trispectrum_1h_kernelE"),
+    ("trispectrum_zsum_kernel  (its z sum, trispectrum.hip)", r"23trispectrum_zsum_kernelE"),
+    ("trispectrum_check_kernel  (its table check, trispectrum.hip)", r"24trispectrum_check_kernelE"),
 ]
 
 
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16

@@ -453,6 +453,49 @@ def run_extra_pins(hm):
     return out
 
 
+def run_cov_gaussian(hm):
+    """The Gaussian bandpower covariance of hmvec/cov.py: its free functions, and GaussianCov on three sets of bin edges
+    (even, uneven, non-integer) with three spectra - two with noise on a grid of its own, one without - looked up in
+    both name orders (the other order returns 0) and get_cov for seven name orders."""
+    import hmvec.cov as rcov
+    out = {}
+    ells = np.arange(2.0, 3001.0)
+    ellsn = np.geomspace(2.0, 3000.0, 57)
+    ngal = np.array([0.5, 10.0, 26.0])
+    out["ells"], out["ellsn"], out["ngal"] = ells, ellsn, ngal
+    out["cls_kk"] = 1e-7 * (ells / 100.0) ** -1.2 * (1 + 0.1 * np.sin(ells / 150.0))
+    out["cls_gg"] = 3e-6 * (ells / 100.0) ** -0.8
+    out["cls_kg"] = 4e-7 * (ells / 100.0) ** -1.0
+    out["ncls_kk"] = 2e-9 * (1 + (ellsn / 1500.0) ** 2)
+    out["ncls_gg"] = rcov.shot_noise(26.0) * np.ones_like(ellsn)
+    out["shot_noise"] = rcov.shot_noise(ngal)
+    out["shape_noise_default"] = rcov.lensing_shape_noise(ngal)
+    out["shape_noise_0p26"] = rcov.lensing_shape_noise(ngal, 0.26)
+    holes = out["cls_kk"].copy()
+    holes[5:40] = np.nan                      # NaNs: left out of the numerator's mean, one bin all NaN
+    out["cls_holes"] = holes
+    out["edges_holes"] = np.array([2.0, 5.0, 9.0, 30.0, 60.0, 200.0])
+    out["binned_holes"] = rcov.bin_annuli(ells, holes, out["edges_holes"])
+    out["fsky"] = np.float64(0.4)
+    sets = [np.arange(100.0, 1001.0, 100.0), np.array([50.0, 80.0, 200.0, 230.0, 700.0, 1500.0]),
+            np.array([30.5, 90.25, 400.75, 1200.5])]
+    orders = ["kkkk", "gggg", "kgkg", "kkgg", "ggkk", "gkgk", "kggk"]
+    out["orders"] = np.array(orders)
+    for i, edges in enumerate(sets):
+        gc = rcov.GaussianCov(edges)
+        gc.add_cls("k", "k", ells, out["cls_kk"], ellsn, out["ncls_kk"])
+        gc.add_cls("g", "g", ells, out["cls_gg"], ellsn, out["ncls_gg"])
+        gc.add_cls("k", "g", ells, out["cls_kg"])
+        out[f"e{i}_edges"], out[f"e{i}_ells"], out[f"e{i}_ls"], out[f"e{i}_dls"] = edges, gc.ells, gc.ls, gc.dls
+        for x, y in ("kk", "gg", "kg", "gk"):
+            out[f"e{i}_scls_{x}{y}"] = np.asarray(gc.get_scls(x, y), dtype=np.float64)
+            out[f"e{i}_ncls_{x}{y}"] = np.asarray(gc.get_ncls(x, y), dtype=np.float64)
+            out[f"e{i}_tcls_{x}{y}"] = np.asarray(gc.get_tcls(x, y), dtype=np.float64)
+        for o in orders:
+            out[f"e{i}_cov_{o}"] = np.asarray(gc.get_cov(*o, 0.4), dtype=np.float64)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
@@ -519,6 +562,8 @@ def main():
         save("case_f", run_case_f(hm))
     if want("extra_pins"):
         save("extra_pins", run_extra_pins(hm))
+    if want("cov_gaussian"):
+        save("cov_gaussian", run_cov_gaussian(hm))
     if not args.skip_readme:
         if want("readme_c1"):
             save("readme_c1", run_readme_anchor(hm))
