@@ -20,6 +20,7 @@ import numpy as np
 import scipy.constants as constants
 
 from . import _native as nat
+from . import bispectrum as bispec
 from . import realspace, spectra, stages
 from .cosmology import Cosmology, _is_shared_product, sigma2_kgrid, sigma2_weights
 from .params import battaglia_defaults, default_params
@@ -1274,6 +1275,78 @@ class HaloModel(Cosmology):
         integral of its square.  damping=True (default) multiplies by D(k_i) D(k_j), D = 1 - exp(-(k/kstar)^2), which
         makes T consistent with the damped P_1h the model returns; damping=False leaves it out."""
         return self.trispectrum_device(name, name2, name3, name4, kindex=kindex, damping=damping)[0].numpy()
+
+    # ------------------------------------------------------------------ bispectrum of three tracers (DESIGN.md section 16)
+    # B1h, B2h, B3h at triangles of sample wavenumbers, contracted on the device over the resident tensors
+    # (hmg_bispectrum); only (3, nz, nt) or (3, nt) results cross.  The host side of the contract is bispectrum.py.
+    def bispectrum_device(self, name, name2=None, name3=None, triangles=None, kindex=None, damping=True, idx=None,
+                          frac=None, scale=None, zweights=None, per_z=True):
+        """(B, Bz) on the device: B (3, nz, nt) the 1-halo, 2-halo and 3-halo terms of the bispectrum of the tracers
+        (name, name2, name3) - per_z=False: None - and Bz (3, nt) = sum_z zweights[z] B[:, z], in z order, if zweights
+        (nz,) is given, else None.  Missing names default to the first.
+
+        Samples as for trispectrum_device (kindex, or idx / frac / scale tables; at most 256), except that damping is
+        not folded into scale: the factors D = 1 - exp(-(k / kstar)^2) multiply the 1-halo term and the 1-halo factor of
+        each 2-halo term.  triangles: (nt, 3) integer array of sample indices, the same for every redshift - leg
+        `name` sits at column 0, name2 at 1, name3 at 2; default: all i <= j <= l that close at every redshift; at most
+        2^20.  A triangle must close at every redshift.  At most one of the names may be an HOD."""
+        return self._bispectrum(name, name2, name3, triangles, kindex, damping, idx, frac, scale, zweights, per_z)[:2]
+
+    def _bispectrum(self, name, name2, name3, triangles, kindex, damping, idx, frac, scale, zweights, per_z, want_J=False):
+        """(B, Bz, J) of bispectrum_device; J (3, nz, n), the 2-halo bracket (I + b) - C of each leg at the samples, if
+        want_J, else None.  Every refusal happens here on the host, before any launch."""
+        name2 = name if name2 is None else name2
+        name3 = name if name3 is None else name3
+        triple = (name, name2, name3)
+        recs = self._resolve(*triple)
+        if sum(r.kind1 == "h" for r in recs) >= 2:
+            raise NotImplementedError(
+                f"bispectrum of {triple!r}: two or more HOD names in one triple need the third factorial moments of the "
+                f"HOD for the 1-halo term, which the model does not carry (the product of two galaxy weights would "
+                f"count self-pairs)")
+        for r in recs:
+            if not r.same:
+                raise ValueError(f"bispectrum of {triple!r}: the 1-halo and 2-halo lookups resolve {r.name!r} differently "
+                                 f"(it names both an HOD and a profile)")
+        t_idx, t_frac, t_scale = self._trispectrum_tables(kindex, idx, frac, scale, False)
+        n = t_idx.shape[1]
+        if n > bispec.MAX_SAMPLES:
+            raise ValueError(f"kindex / idx asks for {n} samples per redshift; the bispectrum takes at most "
+                             f"{bispec.MAX_SAMPLES}: pass a shorter kindex")
+        tri = bispec.check_triangles(triangles, bispec.sample_wavenumbers(self.ks, t_idx, t_frac), self.zs)
+        if zweights is not None:
+            zweights = np.ascontiguousarray(zweights, dtype=np.float64).reshape(-1)
+            if zweights.size != self._nz:
+                raise ValueError(f"zweights must have one entry per redshift ({self._nz}), got {zweights.size}")
+        elif not per_z and not want_J:
+            raise ValueError("nothing asked for: per_z=False needs zweights")
+        nz, nm, nk, nt = self._nz, self._nm, self._nk, tri.shape[0]
+        ctx = self._main(needs_aux=True)
+        # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
+        tr = [self._tracer(r, 1) for r in recs]
+        d_idx, d_frac, d_scale = ctx.upload_int32(t_idx), ctx.upload(t_frac), ctx.upload(t_scale)
+        d_tri = ctx.upload_int32(tri)
+        d_g = ctx.upload(zweights) if zweights is not None else None
+        B = ctx.empty((3, nz, nt)) if per_z else None
+        Bz = ctx.empty((3, nt)) if zweights is not None else None
+        J = ctx.empty((3, nz, n)) if want_J else None
+        ctx.call("hmg_bispectrum", nz, nm, nk, n, nt, *(C.byref(t) for t in tr), self._d_nzm.ptr, self._d_bh.ptr,
+                 self._d_ms().ptr, self._d_wm().ptr, self._d_ks().ptr, self._d_Pzk().ptr, self._rho_m0(),
+                 float(self.p["kstar_damping"]) if damping else 0.0, d_idx.ptr, d_frac.ptr, d_scale.ptr, d_tri.ptr,
+                 nat.ptr(d_g), nat.ptr(B), nat.ptr(Bz), nat.ptr(J))
+        self._sync_point()
+        return B, Bz, J       # (the tables go back to the free list: whatever reads them was enqueued before)
+
+    def get_bispectrum(self, name, name2=None, name3=None, triangles=None, kindex=None, term="total", damping=True):
+        """The halo-model bispectrum B(z; k_1, k_2, k_3) of three tracers (missing names: the first), shape (nz, nt), at
+        triangles of the nodes ks[kindex] (default: all nodes; at most 256) - triangles (nt, 3) indexes kindex, leg
+        `name` at column 0; default: all i <= j <= l that close.  term: "1h", "2h", "3h" or "total" (their sum in that
+        order).  Linear halo bias only (no b_2 term); the 3-halo term uses the tree-level matter bispectrum of the
+        model's P_lin.  damping as in get_power_1halo, per leg."""
+        if term not in bispec.TERMS:
+            raise ValueError(f"term must be one of {bispec.TERMS}, got {term!r}")
+        B = self.bispectrum_device(name, name2, name3, triangles=triangles, kindex=kindex, damping=damping)[0]
+        return bispec.pick_term(B.numpy(), term)
 
     # ------------------------------------------------------------------ cluster lensing (DESIGN.md section 10)
     # The per-halo scalars are formed on the host one lens redshift at a time (a few values per halo), so that a z slice

@@ -674,6 +674,37 @@ int hmg_trispectrum_1h(hmg_ctx* ctx, int nz, int nm, int nk, int n,
                        const double* d_zweights /*[nz] or NULL*/,
                        double* d_T /*[nz][n][n] or NULL*/, double* d_Tz /*[n][n] or NULL*/);
 
+/* ---- halo-model bispectrum of three tracers, 1h + 2h + 3h ------------------------------------
+ * hmg_bispectrum: d_B (3, nz, nt) = (B1h, B2h, B3h) of the legs (a, b, c) at nt triangles tri[t] = (s1, s2, s3) of the n
+ * samples per redshift (tables as for hmg_trispectrum_1h; leg a sits at s1, b at s2, c at s3; n <= 256, nt <= 2^20):
+ *   B1h[z,t] = sigma D1 D2 D3 sum_m wm nzm w_a(s1) w_b(s2) w_c(s3)
+ *   B2h[z,t] = sigma [D1 D2 I_ab(s1,s2) J_c(s3) P_3 + D2 D3 I_bc(s2,s3) J_a(s1) P_1 + D1 D3 I_ac(s1,s3) J_b(s2) P_2]
+ *   B3h[z,t] = sigma J_a(s1) J_b(s2) J_c(s3) 2 [F2(k1,k2;k3) P_1 P_2 + F2(k2,k3;k1) P_2 P_3 + F2(k3,k1;k2) P_3 P_1]
+ * w_x[z,m,s] the weight of a single tracer in hmg_power's cross-spectrum case (matter m u / rho_m0, HOD
+ * (u_c Nc + u_s Ns) / ngal, pressure pk) interpolated linearly to the sample, without the scale;
+ * I_xy = sum_m wm nzm bh w_x w_y; J_x = (I_x + b_x) - C_x the bracket of P2h in hmg_power (I_x = sum_m wm nzm bh w_x);
+ * P_s = Pzk at the sample; k_s = ks[idx] where frac == 0, else (1 - f) ks[idx] + f ks[idx+1] (three rounded operations);
+ * D_s = 1 - exp(-(k_s / kstar)^2), or 1 if kstar <= 0; sigma = scale_1 scale_2 scale_3;
+ * F2(p,q;r) = 5/7 + mu/2 (p/q + q/p) + 2/7 mu^2, mu = clamp(((r-p)(r+p) - q^2) / (2 p q), -1, 1), evaluated with the longer
+ * of (p, q) as p (F2 is symmetric in them; mu then stays within a few ulp for squeezed triangles).  Linear halo bias only.
+ * Scales and damping multiply finished sums.  d_Bz (3, nt) = sum_z zweights[z] B[:, z], z in order, needs d_zweights;
+ * d_J (3, nz, n) is J by leg.  Any output may be NULL, not all three (d_B NULL with d_Bz: the per-z terms live in a
+ * temporary block).  At most one of the three tracers may be an HOD (the 1-halo term of two needs third factorial
+ * moments).  The tables and the triangles are checked on the device before any tensor is read through them - the
+ * conditions of hmg_trispectrum_1h, a triangle index outside 0 .. n-1, and a triangle that does not close at some z,
+ * k_max > (k_mid + k_min)(1 + 2^-40), are errors - and the host waits for that answer: the call synchronises the current
+ * stream once and cannot be part of a captured step.  Tracers as for hmg_power (hints and bias overrides are not
+ * read).  fp64 on the vector units, every workgroup walks the whole mass axis in order, no atomics: bit-identical on
+ * repeat, an element depends only on its own (z, t) entries, not on the other triangles or redshifts of the call.       */
+int hmg_bispectrum(hmg_ctx* ctx, int nz, int nm, int nk, int n, int nt,
+                   const hmg_tracer* h_a, const hmg_tracer* h_b, const hmg_tracer* h_c,
+                   const double* d_nzm, const double* d_bh, const double* d_ms, const double* d_wm, const double* d_ks,
+                   const double* d_Pzk, double rho_m0, double kstar /*<= 0: no damping*/,
+                   const int* d_idx /*[nz][n]*/, const double* d_frac, const double* d_scale,
+                   const int* d_tri /*[nt][3]*/, const double* d_zweights /*[nz] or NULL*/,
+                   double* d_B /*[3][nz][nt] or NULL*/, double* d_Bz /*[3][nt] or NULL*/,
+                   double* d_J /*[3][nz][n] or NULL*/);
+
 /* ---- z-slab gather over RCCL/xGMI -------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */
