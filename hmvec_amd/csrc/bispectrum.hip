@@ -78,6 +78,8 @@ int hmg_bispectrum(hmg_ctx* c, int nz, int nm, int nk, int n, int nt, const hmg_
     for (auto t : tr) hods += t->kind == HMG_TRACER_HOD;
     REQUIRE(hods < 2, "two or more HOD tracers in one triple: the 1-halo term needs third factorial moments of the HOD, "
                       "which the model does not carry");
+    for (auto t : tr)       // (an NFW tensor with deferred series tiles is filled first)
+        if (series_ensure_whole(c, t->d_prof) || series_ensure_whole(c, t->d_cprof)) return 1;
     BisArgs A;
     A.nu = 0;
     for (int l = 0; l < 3; ++l) {

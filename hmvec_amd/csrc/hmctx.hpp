@@ -93,7 +93,14 @@ struct PrefixEntry {                      // a tensor some transform wrote with 
     double* cconst = nullptr;
     int rows = 0, nk = 0;
     bool pending = false;                 // the tiles are unwritten right now
+    // the other kind of entry - series deferral of the analytic NFW tensor: the unwritten tiles are those below nser[row],
+    // their values nfw_series_short of the row's series coefficients (acoef), c, r_s, z and the wavenumbers
+    int* nser = nullptr;
+    const double *acoef = nullptr, *cs = nullptr, *rss = nullptr, *zs = nullptr, *ks = nullptr;
+    int nm = 0;
+    bool described() const { return nconst || nser; }
 };
+struct SeriesCounts { int* d = nullptr; int rows = 0; };      // the context's nser array of one NFW tensor
 
 struct hmg_ctx {
     int device = 0;
@@ -162,6 +169,8 @@ struct hmg_ctx {
     std::map<void*, PrefixEntry> prefix;
     std::map<void*, PrefixEntry> prefix_capture;
     std::map<int, std::map<void*, PrefixEntry>> graph_prefix;
+    std::map<void*, SeriesCounts> series_counts;   // per NFW tensor pointer; grown outside captures only
+    std::vector<void*> series_retired;             // outgrown count arrays: a captured step may still write them
     hmg_ctx() { for (auto& b : bracket) b[0] = b[1] = -1; }
 };
 constexpr size_t FREE_CACHE_LIMIT = (size_t)4 << 30;   // bytes kept in the free list before real frees
@@ -179,13 +188,13 @@ int bracket_close(hmg_ctx* c, int stop_slot);
 // fill of every tensor the context knows (hmg_prefix_fill).
 static inline void prefix_note(hmg_ctx* c, void* out, const PrefixEntry& e) {
     auto& m = c->capturing ? c->prefix_capture : c->prefix;
-    if (e.nconst || c->capturing) m[out] = e;
+    if (e.described() || c->capturing) m[out] = e;
     else m.erase(out);
 }
 // a captured step ran: its launches' effects on the state
 static inline void prefix_replayed(hmg_ctx* c, const std::map<void*, PrefixEntry>& fx) {
     for (auto& kv : fx) {
-        if (kv.second.nconst) c->prefix[kv.first] = kv.second;
+        if (kv.second.described()) c->prefix[kv.first] = kv.second;
         else c->prefix.erase(kv.first);
     }
 }
@@ -194,4 +203,10 @@ static inline void prefix_drop_block(hmg_ctx* c, void* p, size_t bytes) {
     auto lo = c->prefix.lower_bound(p), hi = c->prefix.lower_bound((char*)p + bytes);
     c->prefix.erase(lo, hi);
 }
+// Series deferral (hmgrid.hip).  Every native reader of a tensor other than the batched mass integrals calls
+// series_ensure_whole on it first: if p lies in an NFW tensor whose short-series tiles are unwritten they are filled (in
+// a capture: recorded, with the semantics of hmg_prefix_fill).  Every native writer calls series_forget: nothing
+// describes the tensor any more.
+int series_ensure_whole(hmg_ctx* c, const void* p);
+void series_forget(hmg_ctx* c, const void* p);
 static inline dim3 grid1d(size_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }

@@ -230,6 +230,7 @@ int hmg_nfw_analytic(hmg_ctx* c, int nz, int nm, int nk, const double* cs, const
                            (double*)c->scratch[5]);
         HIP_TRY(hipGetLastError());
     }
+    series_forget(c, uk);          // (written whole)
     int stop = -1;
     if (bracket_open(c, HMG_KERNEL_NFW, &stop)) return 1;
     hipLaunchKernelGGL(nfw_kernel, dim3((unsigned)blocks), dim3(threads), 0, c->stream, c->d_sici,
@@ -508,7 +509,7 @@ static int launch_group(hmg_ctx* c, const FusedArgs& A, int rows, const FftRider
             REQUIRE((size_t)rows + R.nchain + nfw_blocks <= 2147483647u, "bad grid");
             return launch_lds(tensor_group_kernel<B, P, M>, dim3((unsigned)(rows + R.nchain + nfw_blocks)), dim3(FUSED_NT),
                               lds, c->stream, C, A, R.nchain, rows, N.T, N.acoef, N.ktile, N.nm, N.nk, N.cs, N.rss, N.zs,
-                              N.ks, N.uk);
+                              N.ks, N.uk, N.nser);
         } else {
             REQUIRE(false, "internal: the tensor group is compiled for compile-time plans only");
         }
@@ -834,7 +835,7 @@ int hmg_prefix_fill(hmg_ctx* c, double* out) {
         // (filling a prefix that is there writes the same values again).
         auto ic = c->prefix_capture.find(out);
         if (ic != c->prefix_capture.end()) {
-            if (!ic->second.nconst || !ic->second.pending) return 0;
+            if (!ic->second.described() || !ic->second.pending) return 0;
             e = ic->second;
         } else {
             auto ig = c->prefix.find(out);
@@ -846,10 +847,55 @@ int hmg_prefix_fill(hmg_ctx* c, double* out) {
         if (it == c->prefix.end() || !it->second.pending) return 0;
         e = it->second;
     }
-    if (hmg_prefix_fill_rows(c, out, e.nconst, e.cconst, e.rows, e.nk)) return 1;
+    if (e.nser) {          // series deferral: the short-series tiles of an analytic NFW tensor
+        hipLaunchKernelGGL(nfw_series_fill_kernel, dim3(e.rows), dim3(256), 0, c->stream, e.nm, e.nk, (const int*)e.nser,
+                           e.acoef, e.cs, e.rss, e.zs, e.ks, out);
+        HIP_TRY(hipGetLastError());
+    } else if (hmg_prefix_fill_rows(c, out, e.nconst, e.cconst, e.rows, e.nk)) return 1;
     e.pending = false;
     prefix_note(c, out, e);
     return 0;
+}
+
+// ---- series deferral of the analytic NFW tensor (hmctx.hpp)
+// the series entry of the tensor that holds p, in the maps a call at this moment goes by; nullptr: none
+static const PrefixEntry* series_entry(hmg_ctx* c, const void* p, void** key) {
+    auto holds = [&](const std::map<void*, PrefixEntry>& m) -> const std::pair<void* const, PrefixEntry>* {
+        auto it = m.upper_bound((void*)p);
+        if (it == m.begin()) return nullptr;
+        --it;
+        const size_t bytes = it->second.nser ? (size_t)it->second.rows * it->second.nk * 8 : 8;
+        return (const char*)p < (const char*)it->first + bytes ? &*it : nullptr;
+    };
+    if (c->capturing)
+        if (auto* kv = holds(c->prefix_capture)) {      // a launch of this capture wrote the tensor: what it left decides
+            *key = kv->first;
+            return kv->second.nser ? &kv->second : nullptr;
+        }
+    auto* kv = holds(c->prefix);
+    if (!kv || !kv->second.nser) return nullptr;
+    *key = kv->first;
+    return &kv->second;
+}
+int series_ensure_whole(hmg_ctx* c, const void* p) {
+    void* key = nullptr;
+    if (!p || !series_entry(c, p, &key)) return 0;
+    return hmg_prefix_fill(c, (double*)key);
+}
+void series_forget(hmg_ctx* c, const void* p) {
+    void* key = nullptr;
+    if (p && series_entry(c, p, &key)) prefix_note(c, key, PrefixEntry{});
+}
+// the context's count array of the NFW tensor at uk; nullptr where one would have to be allocated inside a captured step
+static int* series_counts(hmg_ctx* c, void* uk, int rows) {
+    SeriesCounts& S = c->series_counts[uk];
+    if (S.rows >= rows) return S.d;
+    if (c->capturing) return nullptr;
+    int* d = nullptr;
+    if (hipMalloc((void**)&d, (size_t)rows * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (S.d) c->series_retired.push_back(S.d);
+    S.d = d; S.rows = rows;
+    return d;
 }
 
 int hmg_profile_support_epoch(hmg_ctx* c, long long epoch) {
@@ -934,6 +980,8 @@ static int power_impl(hmg_ctx* c, int nz, int nm, int nk, const hmg_tracer* ta, 
     REQUIRE(nz <= 65535, "nz too large");
     std::vector<const double*> tens;
     PowerPrep Q;
+    for (const hmg_tracer* t : {ta, tb})       // (this kernel reads whole rows)
+        if (series_ensure_whole(c, t->d_prof) || series_ensure_whole(c, t->d_cprof)) return 1;
     if (fill_tracer(ta, tens, &Q.a)) return 1;
     if (fill_tracer(tb, tens, &Q.b)) return 1;
     Q.nt = (int)tens.size();
@@ -982,7 +1030,7 @@ int hmg_power_2halo_terms(hmg_ctx* c, int nz, int nm, int nk, const hmg_tracer* 
     return power_impl(c, nz, nm, nk, ta, tb, nzm, bh, ms, wm, ks, nullptr, rho_m0, 1.0, nullptr, nullptr, I1, I2, C12);
 }
 
-template <int NT, int NTR, int V, bool W16, unsigned CODE = 0>
+template <int NT, int NTR, int V, bool W16, unsigned CODE = 0, bool SER = false>
 static int launch_power_batch(hmg_ctx* c, const BatchArgs& A, int nz) {
     const int per_block = 64 * V;
     dim3 grid((A.nk + per_block - 1) / per_block, nz);
@@ -990,7 +1038,7 @@ static int launch_power_batch(hmg_ctx* c, const BatchArgs& A, int nz) {
     const size_t lds = (size_t)8 * NACC * V * 64 * sizeof(double);
     int stop = -1;
     if (bracket_open(c, HMG_KERNEL_POWER, &stop)) return 1;
-    if (launch_lds(power_batch_kernel<NT, NTR, V, W16, CODE>, grid, dim3(W16 ? 1024 : 512), lds, c->stream, A)) return 1;
+    if (launch_lds(power_batch_kernel<NT, NTR, V, W16, CODE, SER>, grid, dim3(W16 ? 1024 : 512), lds, c->stream, A)) return 1;
     return bracket_close(c, stop);
 }
 
@@ -1004,6 +1052,7 @@ struct PbPlan {
     int ntr = 0, nt = 0, thin = 0;
     unsigned code = 0;
     bool vec2 = false;
+    bool ser = false;        // tensor 0 takes the series slot (pb_series)
 };
 static int pb_plan(hmg_ctx* c, int nz, int nm, int nk, const hmg_power_batch_desc* d, PbPlan* P) {
     REQUIRE(c && d && P, "NULL argument");
@@ -1101,6 +1150,7 @@ static int pb_plan(hmg_ctx* c, int nz, int nm, int nk, const hmg_power_batch_des
         A.ngal[t] = (t < ntr && tr[t].kind == HMG_TRACER_HOD) ? tr[t].d_ngal : nullptr;
         A.bias_const[t] = (t < ntr && tr[t].kind == HMG_TRACER_MATTER) ? 1.0 : 0.0;
     }
+    A.ser_n = nullptr; A.ser_a = A.ser_cs = A.ser_rss = A.ser_zs = nullptr;
     A.nblk = nblk;
     A.coef = coef; A.sidep = sidep; A.ks = d->d_ks; A.Pzk = d->d_Pzk; A.kstar = d->kstar; A.nm = nm; A.nk = nk;
     bool vec2 = (nk % 2 == 0);
@@ -1121,23 +1171,44 @@ static int pb_plan(hmg_ctx* c, int nz, int nm, int nk, const hmg_power_batch_des
     return 0;
 }
 
+// The NFW tensors of the batch that carry a series entry (a launch deferred their short-series tiles): tensor 0 of a
+// batch compiled for its structure takes the series slot - its tiles in the band are evaluated, unwritten or not, in
+// every launch shape (measured: profiles/r08/series_deferral_ab.txt); any other gets its tiles filled before the launch
+// reads them.
+static int pb_series(hmg_ctx* c, int nz, int nm, int nk, PbPlan* P) {
+    for (int i = 0; i < P->nt; ++i) {
+        void* key = nullptr;
+        const PrefixEntry* e = series_entry(c, P->A.tens[i], &key);
+        if (!e) continue;
+        if (i == 0 && P->code && key == (void*)P->A.tens[0] && e->rows == nz * nm && e->nk == nk && e->nm == nm &&
+            e->ks == P->A.ks) {
+            P->ser = true;
+            P->A.ser_n = e->nser; P->A.ser_a = e->acoef; P->A.ser_cs = e->cs; P->A.ser_rss = e->rss; P->A.ser_zs = e->zs;
+        } else if (hmg_prefix_fill(c, (double*)key)) return 1;
+    }
+    return 0;
+}
+
 static int pb_launch_main(hmg_ctx* c, const PbPlan& P, int nz) {
     const BatchArgs& A = P.A;
     const int thin = P.thin, ntr = P.ntr;
     const bool vec2 = P.vec2;
     const unsigned code = P.code;
-#define PB_SHAPES(NT_, NTR_, CODE_)                                                        \
-    if (thin == 3) return launch_power_batch<NT_, NTR_, 2, true, CODE_>(c, A, nz);         \
-    return thin == 1 ? launch_power_batch<NT_, NTR_, 1, true, CODE_>(c, A, nz)             \
-                     : (vec2 ? launch_power_batch<NT_, NTR_, 2, false, CODE_>(c, A, nz)    \
-                             : launch_power_batch<NT_, NTR_, 1, false, CODE_>(c, A, nz));
+#define PB_SHAPES(NT_, NTR_, CODE_, SER_)                                                        \
+    if (thin == 3) return launch_power_batch<NT_, NTR_, 2, true, CODE_, SER_>(c, A, nz);         \
+    return thin == 1 ? launch_power_batch<NT_, NTR_, 1, true, CODE_, SER_>(c, A, nz)             \
+                     : (vec2 ? launch_power_batch<NT_, NTR_, 2, false, CODE_, SER_>(c, A, nz)    \
+                             : launch_power_batch<NT_, NTR_, 1, false, CODE_, SER_>(c, A, nz));
     if (code) {
 #define PB_SPEC(NT_, NTR_, ...)                                                            \
-        if (P.nt == NT_ && ntr == NTR_ && code == pb_code(__VA_ARGS__)) { PB_SHAPES(NT_, NTR_, pb_code(__VA_ARGS__)) }
+        if (P.nt == NT_ && ntr == NTR_ && code == pb_code(__VA_ARGS__)) {                  \
+            if (P.ser) { PB_SHAPES(NT_, NTR_, pb_code(__VA_ARGS__), true) }                \
+            PB_SHAPES(NT_, NTR_, pb_code(__VA_ARGS__), false)                              \
+        }
         PB_SPEC_LIST
 #undef PB_SPEC
     }
-#define PB_V(NT_, NTR_) PB_SHAPES(NT_, NTR_, 0u)
+#define PB_V(NT_, NTR_) PB_SHAPES(NT_, NTR_, 0u, false)
 #define PB_NTR(NT_)                         \
     switch (ntr) {                          \
         case 1: PB_V(NT_, 1)                \
@@ -1161,6 +1232,7 @@ static int pb_launch_main(hmg_ctx* c, const PbPlan& P, int nz) {
 int hmg_power_batch_run(hmg_ctx* c, int nz, int nm, int nk, const hmg_power_batch_desc* d, int flags) {
     PbPlan P;
     if (pb_plan(c, nz, nm, nk, d, &P)) return 1;
+    if (pb_series(c, nz, nm, nk, &P)) return 1;
     if (!(flags & HMG_PB_PREPARED)) {
         hipLaunchKernelGGL(power_batch_prep_kernel, dim3(nz, P.PA.nblk), dim3(64), 0, c->stream, P.PA);
         HIP_TRY(hipGetLastError());
@@ -1318,6 +1390,7 @@ int hmg_group_rows(hmg_ctx* c, int nz, int nm, int nk, int nq, const hmg_massfn_
     if (nfw) {
         REQUIRE(nk > 0, "empty grid");
         if (nfw_setup(c, nz, nm, nk, nfw, &N, &nfw_blocks)) return 1;
+        series_forget(c, nfw->d_uk);         // (this route writes the tensor whole)
         if (bracket_open(c, HMG_KERNEL_NFW, &stop)) return 1;
     }
     if (launch_rows_group(c, nz, nm, C, one ? nz : 0, mf ? &S : nullptr, Rw, nfw ? &N : nullptr, nfw_blocks)) return 1;
@@ -1388,9 +1461,24 @@ int hmg_group_tensors(hmg_ctx* c, int nz, int nm, int nk, int nq, const hmg_mass
     NfwArgs N{};
     size_t nfw_blocks = 0;
     if (nfw && nfw_setup(c, nz, nm, nk, nfw, &N, &nfw_blocks)) return 1;
+    // Series deferral: under hmg_prefix_deferral and on this route (ascending wavenumbers: the promise of the transform's
+    // hint arrays) the NFW rows leave the whole tiles of their short-series band unwritten and the tensor is entered in
+    // the context's books with what describes them.  Every launch shape of the mass integrals substitutes (pb_series), so
+    // there is no shape to decide by: measured at nz = 4, 8, 12, 16 and 32 (profiles/r08/series_deferral_ab.txt).
+    if (nfw && c->prefix_deferral && nfw->d_ks == fft->d_ks)
+        N.nser = series_counts(c, nfw->d_uk, nz * nm);
     bool nfw_done = false;
     if (profile_group_launches(c, nz, nm, nk, fft, C, one, prep, P, nfw ? &N : nullptr, nfw_blocks, &nfw_done)) return 1;
     REQUIRE(!nfw || nfw_done, "internal: the transform did not take the route the tensor group was set up for");
+    if (nfw) {
+        PrefixEntry e{};
+        if (N.nser) {
+            e.rows = nz * nm; e.nk = nk; e.nm = nm; e.pending = true;
+            e.nser = N.nser; e.acoef = N.acoef; e.cs = N.cs; e.rss = N.rss; e.zs = N.zs; e.ks = N.ks;
+        }
+        series_forget(c, nfw->d_uk);
+        prefix_note(c, nfw->d_uk, e);
+    }
     return 0;
 }
 
@@ -1422,7 +1510,9 @@ int hmg_fn2d(hmg_ctx* c, int op, int rows, int cols, int nin, const double* cons
         REQUIRE(in[i], "NULL input");
         REQUIRE(sr[i] >= 0 && sc[i] >= 0, "negative stride");
         A.in[i] = in[i]; A.sr[i] = sr[i]; A.sc[i] = sc[i];
+        if (series_ensure_whole(c, in[i])) return 1;
     }
+    series_forget(c, out);
     for (int i = 0; i < HMG_FN_MAXPAR; ++i) A.par[i] = i < npar ? par[i] : 0.0;
     if (op == HMG_FN_TINKER_FNU || op == HMG_FN_TINKER_FSIGMA) REQUIRE(par[0] == 0.0 || par[2] >= 2.0, "alpha table needs >= 2 rows");
     if (op == HMG_FN_HOD_NSNSM1 || op == HMG_FN_HOD_NCNS) REQUIRE(par[0] == 0.0 || par[0] == 1.0, "corr must be 0 (max) or 1 (min)");
@@ -1442,6 +1532,8 @@ int hmg_mstellar_halo(hmg_ctx* c, int nz, int nm, const double* zs, const double
 int hmg_add(hmg_ctx* c, size_t n, const double* a, const double* b, double* out) {
     REQUIRE(c && a && b && out, "NULL argument");
     if (!n) return 0;
+    if (series_ensure_whole(c, a) || series_ensure_whole(c, b)) return 1;
+    series_forget(c, out);
     hipLaunchKernelGGL(add2_kernel, grid1d(n, 256), dim3(256), 0, c->stream, n, a, b, out);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1450,6 +1542,7 @@ int hmg_add(hmg_ctx* c, size_t n, const double* a, const double* b, double* out)
 int hmg_trapz_rows(hmg_ctx* c, int rows, int cols, const double* y, const double* x, double* out) {
     REQUIRE(c && y && x && out, "NULL argument");
     REQUIRE(rows > 0 && cols > 0, "empty grid");
+    if (series_ensure_whole(c, y)) return 1;
     hipLaunchKernelGGL(trapz_rows_kernel, dim3(rows), dim3(256), 0, c->stream, cols, y, x, out);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -188,7 +188,7 @@ template <int MAXB, int MAXP, int SPECM>
 __global__ __launch_bounds__(512, (fused_occ<MAXB, SPECM>())) void tensor_group_kernel(
     ChainArgs C, FusedArgs A, int nchain, int nprof, const SiciTable* __restrict__ T, const double* __restrict__ acoef,
     int ktile, int nm, int nk, const double* __restrict__ cs, const double* __restrict__ rss,
-    const double* __restrict__ zs, const double* __restrict__ ks, double* __restrict__ uk) {
+    const double* __restrict__ zs, const double* __restrict__ ks, double* __restrict__ uk, int* __restrict__ nser) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     int b = blockIdx.x;
     if (b < nchain) {
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(512, (fused_occ<MAXB, SPECM>())) void tensor_group_
     }
     b -= nchain;
     if (b < nprof) profile_fused_row<512, MAXB, MAXP, SPECM, false, true>(A, row_order(b, A.nm), smem);
-    else nfw_rows(T, acoef, ktile, nm, nk, cs, rss, zs, ks, uk, b - nprof, 512, threadIdx.x);
+    else nfw_rows(T, acoef, ktile, nm, nk, cs, rss, zs, ks, uk, b - nprof, 512, threadIdx.x, nser);      // (nser: series deferral)
 }
 
 }  // namespace hmg

@@ -60,6 +60,45 @@ __global__ void nfw_series_kernel(int rows, const double* __restrict__ cs, doubl
     nfw_series_row(cs[row], acoef + (size_t)row * NFW_ROW);
 }
 
+// The two short forms of the series, for a point with (1+c) x <= NFW_XS2 of a row whose series is on.  The series
+// alternates and its n-th term is below (xc)^(2n) / (2n (2n+1)! m_c): 5 terms are exact to 1e-18 for (1+c) x <= 0.1,
+// 8 terms to 2e-17 for <= 0.8 - about 60 % of a typical grid (k starts four decades below the halo scale) takes one
+// of the two.  a: the row's coefficients a[0..7], wave-uniform.  EVERY evaluation of these points goes through this
+// function - the row kernel, the batched mass integrals that evaluate instead of loading (series deferral, DESIGN.md
+// section 3) and the fill kernel -, so all of them produce the same bits.
+__device__ __forceinline__ double nfw_series_short(const double* __restrict__ a, double x, double xc) {
+    const double z = x * x;
+    double u;
+    if (xc <= NFW_XS1) {
+        u = fma_svs(a[NFW_NT1 - 1], z, a[NFW_NT1 - 2]);
+#pragma unroll
+        for (int n = NFW_NT1 - 3; n >= 0; --n) u = fma_vvs(u, z, a[n]);
+    } else {
+        u = fma_svs(a[NFW_NT2 - 1], z, a[NFW_NT2 - 2]);
+#pragma unroll
+        for (int n = NFW_NT2 - 3; n >= 0; --n) u = fma_vvs(u, z, a[n]);
+    }
+    return u;
+}
+// Number of leading wavenumbers of a row that take a short form: the k with opc * (ks[k] * rs * z1) <= NFW_XS2, the
+// value and the operation order nfw_rows tests.  ks ascending, so the test is monotone in k: a 64-way search, one
+// wavefront, one load and one ballot per level (two levels up to nk = 4096).  Every lane returns the count.
+__device__ __forceinline__ int nfw_series_count(const double* __restrict__ ks, int nk, double rs, double z1, double opc,
+                                                int lane) {
+    int lo = 0, n = nk;          // every k < lo passes; the first that fails, if any, is in [lo, lo + n)
+    while (n > 0) {
+        const int s = (n + 63) >> 6, nchunk = (n + s - 1) / s;      // lane l: the chunk [lo + l s, lo + (l+1) s) of it
+        const int last = min(lo + (lane + 1) * s, lo + n) - 1;
+        const bool pass = lane < nchunk && opc * (ks[lane < nchunk ? last : 0] * rs * z1) <= NFW_XS2;
+        const int np = __builtin_amdgcn_readfirstlane(__popcll(__ballot(pass)));      // chunks that pass whole
+        if (np >= nchunk) { lo += n; n = 0; break; }
+        const int end = min(lo + (np + 1) * s, lo + n);
+        lo += np * s;
+        n = end - lo - 1;        // (the last k of chunk np fails)
+    }
+    return lo;
+}
+
 // Order in which the row workgroups of a launch take the masses of a redshift: heaviest first.  Workgroups are
 // dispatched in index order and the rows of the heavy end of the mass grid are the expensive ones in both tensor
 // producers (NFW: most of their wavenumbers are on the Si/Ci branch; Battaglia: many FFT modes are reachable), so
@@ -82,6 +121,7 @@ struct NfwArgs {
     int ktile, nm, nk;
     const double *cs, *rss, *zs, *ks;
     double* uk;
+    int* nser;       // series deferral: the per-row counts the launch writes (nullptr: the tensor is written whole)
 };
 // blk: index of the (row, k tile) this workgroup owns; nthr: threads that share it (the workgroup size).
 // The pointers must reach this function as __restrict__ KERNEL PARAMETERS (not as fields of a by-value
@@ -92,7 +132,7 @@ __device__ __forceinline__ void nfw_rows(const SiciTable* __restrict__ T, const 
                                          int nm, int nk, const double* __restrict__ cs,
                                          const double* __restrict__ rss, const double* __restrict__ zs,
                                          const double* __restrict__ ks, double* __restrict__ uk, int blk, int nthr,
-                                         int tid) {
+                                         int tid, int* __restrict__ nser = nullptr) {
     // one (z,m) row per workgroup, the whole k axis in one tile: measured against two rows per workgroup
     // (+4 %), half tiles (+40 %) and 128 threads per row (+-0): a workgroup's fixed cost is the latency of
     // its scalar loads (row constants, series coefficients), not instructions
@@ -111,24 +151,23 @@ __device__ __forceinline__ void nfw_rows(const SiciTable* __restrict__ T, const 
     const double ln_opc = a[NFW_NS2 + 0], inv_mc = a[NFW_NS2 + 1], inv_opc2 = a[NFW_NS2 + 2];
     const bool use_series = (a[0] != 0.0);
     double* __restrict__ dst = uk + (size_t)row * nk;
-    for (int k = k_lo + tid; k < k_hi; k += nthr) {
+    // series deferral (nser != nullptr): the count of this row's short-series wavenumbers goes to nser[row] and the whole
+    // HMG_PREFIX_TILE-wide tiles below it stay unwritten - whoever reads them evaluates nfw_series_short instead
+    int k_first = k_lo;
+    if (nser) {
+        const int cnt = use_series ? nfw_series_count(ks, nk, rs, z1, opc, tid & 63) : 0;
+        if (tid == 0 && k_lo == 0) nser[row] = cnt;
+        k_first = max(k_lo, cnt & ~(HMG_PREFIX_TILE - 1));
+    }
+    for (int k = k_first + tid; k < k_hi; k += nthr) {
         const double x = ks[k] * rs * z1;
         const double xc = opc * x;
         if (use_series && xc <= 4.0) {
-            // The series alternates and its n-th term is below (xc)^(2n) / (2n (2n+1)! m_c): 5 terms are
-            // exact to 1e-18 for (1+c) x <= 0.1, 8 terms to 2e-17 for <= 0.8 - about 60 % of a typical
-            // grid (k starts four decades below the halo scale) takes one of the two short forms.
-            const double z = x * x;
             double u;
-            if (xc <= NFW_XS1) {
-                u = fma_svs(a[NFW_NT1 - 1], z, a[NFW_NT1 - 2]);
-#pragma unroll
-                for (int n = NFW_NT1 - 3; n >= 0; --n) u = fma_vvs(u, z, a[n]);
-            } else if (xc <= NFW_XS2) {
-                u = fma_svs(a[NFW_NT2 - 1], z, a[NFW_NT2 - 2]);
-#pragma unroll
-                for (int n = NFW_NT2 - 3; n >= 0; --n) u = fma_vvs(u, z, a[n]);
+            if (xc <= NFW_XS2) {
+                u = nfw_series_short(a, x, xc);
             } else {
+                const double z = x * x;
                 u = fma_svs(a[NFW_NS - 1], z, a[NFW_NS - 2]);
 #pragma unroll
                 for (int n = NFW_NS - 3; n >= 0; --n) u = fma_vvs(u, z, a[n]);
@@ -209,6 +248,25 @@ __global__ __launch_bounds__(256, HMG_NFW_OCC) void nfw_kernel(const SiciTable* 
                                                   const double* __restrict__ zs, const double* __restrict__ ks,
                                                   double* __restrict__ uk) {
     nfw_rows(T, acoef, ktile, nm, nk, cs, rss, zs, ks, uk, blockIdx.x, blockDim.x, threadIdx.x);
+}
+
+// The tiles a deferring launch left unwritten (nfw_rows with nser), for every reader other than the batched mass
+// integrals: one workgroup per row writes nfw_series_short into [0, nser[row] & ~(HMG_PREFIX_TILE-1)).
+__global__ __launch_bounds__(256) void nfw_series_fill_kernel(int nm, int nk, const int* __restrict__ nser,
+                                                              const double* __restrict__ acoef,
+                                                              const double* __restrict__ cs,
+                                                              const double* __restrict__ rss,
+                                                              const double* __restrict__ zs,
+                                                              const double* __restrict__ ks, double* __restrict__ uk) {
+    const int row = blockIdx.x;
+    const int n = min(nk, nser[row] & ~(HMG_PREFIX_TILE - 1));
+    const double rs = rss[row], z1 = 1.0 + zs[row / nm], opc = 1.0 + cs[row];
+    const double* __restrict__ a = acoef + (size_t)row * NFW_ROW;
+    double* __restrict__ dst = uk + (size_t)row * nk;
+    for (int k = threadIdx.x; k < n; k += blockDim.x) {
+        const double x = ks[k] * rs * z1;
+        dst[k] = nfw_series_short(a, x, opc * x);
+    }
 }
 
 }  // namespace hmg

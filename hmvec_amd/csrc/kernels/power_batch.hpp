@@ -215,6 +215,10 @@ struct BatchArgs {
     double* P2h[PB_MAXPAIR];
     double kstar;
     int nm, nk;
+    // series deferral (instantiations with SER): tensor 0 is an analytic NFW tensor whose row r holds nfw_series_short
+    // in its first ser_n[r] wavenumbers, written or not - the rows' counts, series coefficients, c, r_s and the redshifts
+    const int* ser_n;
+    const double *ser_a, *ser_cs, *ser_rss, *ser_zs;
 };
 
 // Summation order over the mass axis (fixed by nm alone, so that a z-slab run and the full grid agree
@@ -233,7 +237,9 @@ __device__ __forceinline__ double lane_value(double v, int l) {
     return __hiloint2double(hi, lo);
 }
 
-template <int NT, int NTR, int V, bool W16, unsigned CODE = 0>
+// SER: k tiles of tensor 0 that lie in a row's short-series band are evaluated (nfw_series_short, the function that wrote
+// or would have written them) instead of loaded; a compile-time property, so that batches without it keep their code.
+template <int NT, int NTR, int V, bool W16, unsigned CODE = 0, bool SER = false>
 __global__ __launch_bounds__(W16 ? 1024 : 512) void power_batch_kernel(BatchArgs A) {
     extern __shared__ double red[];  // [8][NACC*V][64]: parked sums / pair exchange, then the cross-wave reduction
     using vec_t = typename VecT<V>::type;
@@ -266,12 +272,29 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) void power_batch_kernel(BatchArgs
         if (W16) return wv + PB_NV * i;
         return i < L ? wv + PB_NV * i : wv + 8 + PB_NV * (i - L);
     };
-    // constant-prefix hint of mass bin m: how many leading k of the row equal `val`
-    struct Hint { int n[NT]; double val[NT]; };
+    // constant-prefix hint of mass bin m: how many leading k of the row equal `val`; with SER, for tensor 0: how many
+    // take a short series form, and what that form needs of the row (NFW_NT2 coefficients, r_s, 1 + c)
+    struct Hint { int n[NT]; double val[NT]; double a[SER ? NFW_NT2 : 1], rs, opc; };
+    double kser[V], z1ser = 0.0;      // SER: this lane's wavenumbers, 1 + z
+    if constexpr (SER) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) kser[v] = A.ks[kofs + v];
+        z1ser = 1.0 + A.ser_zs[z];
+    }
     auto load_hint = [&](Hint& h, int m) {
         const size_t r = zrow + min(m, A.nm - 1);
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
+            if (SER && i == 0) {
+                const double* __restrict__ ar = A.ser_a + r * (size_t)NFW_ROW;
+                h.n[0] = A.ser_n[r];
+                h.val[0] = 0.0;
+#pragma unroll
+                for (int j = 0; j < NFW_NT2; ++j) h.a[j] = ar[j];
+                h.rs = A.ser_rss[r];
+                h.opc = 1.0 + A.ser_cs[r];
+                continue;
+            }
             h.n[i] = A.nconst[i] ? A.nconst[i][r] : -1;
             h.val[i] = A.nconst[i] ? A.cconst[i][r] : 0.0;
         }
@@ -281,6 +304,19 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) void power_batch_kernel(BatchArgs
         const size_t off = (zrow + min(m, A.nm - 1)) * (size_t)A.nk + kofs;
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
+            if (SER && i == 0) {
+                if (h.n[0] >= kend) {
+                    double u[V];
+#pragma unroll
+                    for (int v = 0; v < V; ++v) {
+                        const double x = kser[v] * h.rs * z1ser;       // nfw_rows' own expressions, in its order
+                        u[v] = nfw_series_short(h.a, x, h.opc * x);
+                    }
+                    if constexpr (V == 2) dst[0] = make_double2(u[0], u[V - 1]);
+                    else dst[0] = u[0];
+                } else dst[0] = vload_nt<V>(A.tens[0] + off);
+                continue;
+            }
             if (h.n[i] >= kend) dst[i] = vsplat<V>(h.val[i]);
             else dst[i] = vload_nt<V>(A.tens[i] + off);
         }

@@ -147,6 +147,8 @@ int hmg_ctx_destroy(hmg_ctx* c) {
         if (kv.second.twNr) (void)hipFree(kv.second.twNr);
     }
     for (auto& kv : c->pass_tw) (void)hipFree(kv.second);
+    for (auto& kv : c->series_counts) (void)hipFree(kv.second.d);
+    for (void* p : c->series_retired) (void)hipFree(p);
     if (c->h_fault) (void)hipHostFree(c->h_fault);
     for (auto& s : c->scratch) if (s) (void)hipFree(s);
     for (auto& kv : c->free_blocks) (void)hipFree(kv.second);
@@ -237,11 +239,13 @@ int hmg_host_free(hmg_ctx* c, void* h) {
 }
 int hmg_memcpy_d2h_async(hmg_ctx* c, void* h_pinned, const void* d, size_t bytes) {
     REQUIRE(c && h_pinned && d, "NULL argument");
+    if (series_ensure_whole(c, d)) return 1;
     HIP_TRY(hipMemcpyAsync(h_pinned, d, bytes, hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
 int hmg_memcpy_h2d_async(hmg_ctx* c, void* d, const void* h_pinned, size_t bytes) {
     REQUIRE(c && h_pinned && d, "NULL argument");
+    series_forget(c, d);
     HIP_TRY(hipMemcpyAsync(d, h_pinned, bytes, hipMemcpyHostToDevice, c->stream));
     return 0;
 }
@@ -266,6 +270,7 @@ static int ensure_pinned(hmg_ctx* c) {
 // pinned 8 MiB buffers (DMA of chunk i+1 overlapped with the host memcpy of chunk i) is 5-8x faster.
 int hmg_memcpy_h2d(hmg_ctx* c, void* d, const void* h, size_t bytes) {
     REQUIRE(c && d && h, "NULL argument");
+    series_forget(c, d);        // (the caller's values replace a tensor with deferred tiles: nothing is substituted for them)
     if (bytes <= hmg_ctx::UP_SLOT_BYTES && !c->capturing && !c->lanes_dirty && c->stream == c->lanes[0]) {
         // the caller's array is copied into a pinned slot now, the DMA out of the slot is stream-ordered: no
         // host wait (a slot is reused only after its own DMA has finished).  Only while everything runs on
@@ -311,6 +316,7 @@ int hmg_memcpy_d2h(hmg_ctx* c, void* h, const void* d, size_t bytes) {
     // the copy runs on the current lane, behind everything enqueued there; only when other lanes
     // have been used can the producer sit elsewhere
     if (c->lanes_dirty && sync_all(c)) return 1;
+    if (series_ensure_whole(c, d)) return 1;
     if (bytes < (256u << 10)) {
         HIP_TRY(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -340,6 +346,8 @@ int hmg_memcpy_d2h(hmg_ctx* c, void* h, const void* d, size_t bytes) {
 }
 int hmg_memcpy_d2d(hmg_ctx* c, void* dst, const void* src, size_t bytes) {
     REQUIRE(c && dst && src, "NULL argument");
+    if (series_ensure_whole(c, src)) return 1;
+    series_forget(c, dst);
     HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
     return 0;
 }

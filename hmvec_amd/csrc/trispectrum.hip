@@ -83,6 +83,8 @@ int hmg_trispectrum_1h(hmg_ctx* c, int nz, int nm, int nk, int n, const hmg_trac
     const int tiles = (n - 1) / TRI_TILE + 1;
     REQUIRE(tiles <= 65535, "n too large");
     REQUIRE(!c->capturing, "hmg_trispectrum_1h waits on the host for its table check and cannot be part of a captured step");
+    for (const hmg_tracer* t : {ta, tb, tc, td})       // (an NFW tensor with deferred series tiles is filled first)
+        if (series_ensure_whole(c, t->d_prof) || series_ensure_whole(c, t->d_cprof)) return 1;
     TriArgs A;
     if (tri_side(ta, tb, &A.ab)) return 1;
     if (tri_side(tc, td, &A.cd)) return 1;

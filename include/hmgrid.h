@@ -306,7 +306,22 @@ int hmg_profile_fft_logx(hmg_ctx* ctx, int nxs, const double* d_xs, double* d_lo
  * Every reader other than the batched mass integrals - the one-pair entry points, a copy to the host, the
  * caller's own kernels - must be preceded by the fill below; a filled tensor is bit-identical to the one a
  * transform without deferral writes.  HMG_PREFIX_TILE is a multiple of every k-tile width of the batched mass
- * integrals (asserted where they are compiled).                                                              */
+ * integrals (asserted where they are compiled).
+ *
+ * Series deferral of the analytic NFW tensor.  The same switch covers the NFW rows of hmg_group_tensors: 61 % of
+ * that tensor at the headline shape are whole tiles of a row's short-series band - the leading wavenumbers with
+ * (1+c) k r_s (1+z) <= 0.8, a 5- or 8-term polynomial of the row's series coefficients.  With deferral ON and on the
+ * tensor-group route (ascending d_ks) the rows leave elements [0, nser[row] & ~(HMG_PREFIX_TILE-1)) UNWRITTEN, nser[row] being the length of the band (an array the context
+ * owns).  hmg_power_batch* finds the tensor in the context's books by its pointer and EVALUATES the k tiles that lie
+ * in the band with the device function the rows use - the same bits, no load; tracers carry nothing new.  Every other
+ * native reader fills first, on its own: hmg_power, hmg_power_2halo_terms, hmg_trispectrum_1h, hmg_bispectrum,
+ * hmg_memcpy_d2h / _d2h_async / _d2d (source), hmg_fn2d / hmg_add / hmg_trapz_rows (inputs), and a batch that cannot
+ * substitute (generic forms, the tensor not in slot 0).  The fill reads the row's c, r_s, z,
+ * wavenumbers and series coefficients through the pointers the deferring launch was given: they must still hold what
+ * that launch read.  hmg_memcpy_h2d / _h2d_async and hmg_memcpy_d2d INTO the tensor, a launch that writes it whole
+ * (hmg_nfw_analytic, hmg_group_rows, hmg_group_tensors without deferral) and hmg_free drop the entry.  A reader
+ * OUTSIDE the library (the caller's own kernel on the raw pointer) calls hmg_prefix_fill first, as for a hinted
+ * tensor; hmg_prefix_pending reports the state.  hmg_nfw_analytic and hmg_group_rows never defer.              */
 #define HMG_PREFIX_TILE 128
 int hmg_prefix_deferral(hmg_ctx* ctx, int on);
 /* Fill the pending prefix of the tensor at d_out on the current lane; nothing is enqueued when none is pending.

@@ -16,8 +16,13 @@ KERNELS = [   # (label, regex on the mangled name)
     ("tensor_group_kernel<2,3,2500>  (nxs = 5000: chain | profile rows | NFW rows, the launch of a pass)", r"tensor_group_kernelILi2ELi3ELi2500E"),
     ("rows_group_kernel  (HMG_NO_TENSOR_GROUP=1, and passes without a profile transform)", r"17rows_group_kernelE"),
     ("profile_group_kernel<2,3,2500>  (nxs = 5000; a second profile of a pass, HMG_NO_TENSOR_GROUP=1)", r"profile_group_kernelILi2ELi3ELi2500E"),
-    ("power_batch_kernel<2,3,2,false,593>  (Config 3, full grid)", r"power_batch_kernelILi2ELi3ELi2ELb0ELj593E"),
-    ("power_batch_kernel<2,3,1,true,593>  (thin slab)", r"power_batch_kernelILi2ELi3ELi1ELb1ELj593E"),
+    ("power_batch_kernel<2,3,2,false,593,true>  (Config 3, full grid: the NFW tensor in the series slot)", r"power_batch_kernelILi2ELi3ELi2ELb0ELj593ELb1E"),
+    ("power_batch_kernel<2,3,1,false,593,true>  (the same for an odd nk)", r"power_batch_kernelILi2ELi3ELi1ELb0ELj593ELb1E"),
+    ("power_batch_kernel<2,3,1,true,593,true>  (thin slab, 64-k tiles, series slot)", r"power_batch_kernelILi2ELi3ELi1ELb1ELj593ELb1E"),
+    ("power_batch_kernel<2,3,2,true,593,true>  (thin slab, 128-k tiles, series slot)", r"power_batch_kernelILi2ELi3ELi2ELb1ELj593ELb1E"),
+    ("power_batch_kernel<2,3,2,false,593>  (Config 3, full grid, tensors written whole)", r"power_batch_kernelILi2ELi3ELi2ELb0ELj593ELb0E"),
+    ("power_batch_kernel<2,3,1,true,593>  (thin slab)", r"power_batch_kernelILi2ELi3ELi1ELb1ELj593ELb0E"),
+    ("nfw_series_fill_kernel  (fill of a deferred short-series band)", r"22nfw_series_fill_kernelE"),
     ("profile_pruned_kernel<512,1000>  (nxs = 30000)", r"profile_pruned_kernelILi512ELi1000E"),
     ("profile_pruned_kernel<512,1250>  (nxs = 40000)", r"profile_pruned_kernelILi512ELi1250E"),
     ("profile_band_kernel<512,1000,1>  (tSZ: nxs = 30000, xmax = 2, <= 255 modes)", r"profile_band_kernelILi512ELi1000ELi1E"),
