@@ -202,6 +202,8 @@ SIGNATURES = {
                            _P, _P, _P, _D, _P, _P, _P, _P, _P, _P],
     "hmg_bispectrum": [_P, _I, _I, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), C.POINTER(Tracer),
                        _P, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P],
+    "hmg_response": [_P, _I, _I, _I, _I, _I, C.POINTER(Tracer), _P, _P, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P],
+    "hmg_ssc": [_P, _I, _I, _I, _P, _P, _P, _P],
     "hmg_comm_unique_id": [C.c_char * COMM_ID_BYTES],
     "hmg_comm_init": [_P, C.c_char * COMM_ID_BYTES, _I, _I],
     "hmg_comm_allgather": [_P, _P, _P, _Z],
@@ -225,7 +227,8 @@ def kernel_source_sha16():
     h = hashlib.sha256()
     csrc = os.path.join(_HERE, "csrc")
     names = ["hmgrid.hip", "longgrid.hip", "longgrid.hpp", "rowdev.hpp", "sici.hpp", "ldsfft.hpp", "fastmath.hpp", "Makefile",
-             "lensing.hip", "j0.hpp", "j1.hpp", "ksz.hip", "realspace.hip", "j01.hpp", "trispectrum.hip", "bispectrum.hip"]
+             "lensing.hip", "j0.hpp", "j1.hpp", "ksz.hip", "realspace.hip", "j01.hpp", "trispectrum.hip", "bispectrum.hip",
+             "response.hip"]
     names += sorted(os.path.join("kernels", n) for n in os.listdir(os.path.join(csrc, "kernels")) if n.endswith(".hpp"))
     for name in names:          # (runtime.hip / comm.hip / hmctx.hpp hold no device code: not part of the kernel identity)
         with open(os.path.join(csrc, name), "rb") as f:

@@ -1,19 +1,23 @@
-"""Covariances of halo-model spectra.
+"""Covariances of halo-model spectra (DESIGN.md sections 15 and 17).
 
-Two parts.  The Gaussian covariance between bandpowers mirrors the reference's ``hmvec/cov.py`` under the same names
+Three parts.  The Gaussian covariance between bandpowers mirrors the reference's ``hmvec/cov.py`` under the same names
 (``bin_annuli``, ``shot_noise``, ``lensing_shape_noise``, ``GaussianCov``): host arithmetic on a few hundred numbers.
 The connected part is what a halo model supplies: ``cl_cov_1halo`` is the Limber projection of the 1-halo trispectrum
-``HaloModel.trispectrum_device`` contracts on the GPU; ``limber_samples`` builds its sample tables on the host.
+``HaloModel.trispectrum_device`` contracts on the GPU; ``limber_samples`` builds its sample tables on the host.  The
+super-sample covariance ``cl_cov_ssc`` is the Limber projection of the products of two responses to a background mode
+(``HaloModel.response_device`` / ``ssc_device``) weighted with the variance of that mode in the survey window,
+``sigma_b_disc``.  The three parts are not summed anywhere: the Limber measures of ``cl_cov_1halo`` and ``cl_cov_ssc``
+differ.
 """
 import warnings
 
 import numpy as np
 from scipy.interpolate import interp1d
 
-from .quadrature import trapz_weights
+from .quadrature import simpson_weights, trapz_weights
 
 __all__ = ["bin_annuli", "default_binning", "shot_noise", "lensing_shape_noise", "GaussianCov", "limber_samples",
-           "cl_cov_1halo"]
+           "cl_cov_1halo", "sigma_b_disc", "cl_cov_ssc"]
 
 
 # ---------------------------------------------------------------------------------------- Gaussian part (hmvec/cov.py)
@@ -163,3 +167,92 @@ def cl_cov_1halo(model, ells, name, name2=None, name3=None, name4=None, W1=1, W2
     _, Tz = model.trispectrum_device(name, name2, name3, name4, damping=damping, idx=idx, frac=frac, zweights=g,
                                      per_z=False)
     return Tz.numpy()
+
+
+# ---------------------------------------------------------------------------------------- super-sample covariance
+def dlnp_table(ks, Pzk):
+    """dlnP[z,k] = d ln P_lin / d ln k on the model's grid: np.gradient(log Pzk, log ks, axis=-1).  The table is
+    uploaded as it is, so the device and a restatement interpolate the same numbers."""
+    return np.gradient(np.log(np.asarray(Pzk, dtype=np.float64)), np.log(np.asarray(ks, dtype=np.float64)), axis=-1)
+
+
+def sigma_b_disc(ks, Pzk, chis, fsky=None, theta_s=None):
+    """The variance of the background density mode in a disc-shaped survey per unit radial length, (nz,), in Mpc:
+
+        sigma_b(z) = 1 / (2 pi) sum_j w_j k_j P[z,j] (2 J1(x) / x)^2,    x = k_j chi(z) theta_s,
+
+    w the Simpson weights of ks (quadrature.simpson_weights, the rule of the sigma^2 integral), P (nz, nq) the linear
+    spectrum on ks, chi in Mpc.  The disc is the cap of area 4 pi fsky, theta_s = arccos(1 - 2 fsky), if fsky is given;
+    exactly one of fsky (in (0, 1]) and theta_s (radians, >= 0) must be.  x == 0 gives a window of 1."""
+    from scipy.special import j1
+    if (fsky is None) == (theta_s is None):
+        raise ValueError("give exactly one of fsky and theta_s")
+    if fsky is not None:
+        fsky = float(fsky)
+        if not (0.0 < fsky <= 1.0):
+            raise ValueError(f"fsky must lie in (0, 1], got {fsky!r}")
+        theta_s = np.arccos(1.0 - 2.0 * fsky)
+    theta_s = float(theta_s)
+    if not (np.isfinite(theta_s) and theta_s >= 0.0):
+        raise ValueError(f"theta_s must be finite and not negative, got {theta_s!r}")
+    ks = np.asarray(ks, dtype=np.float64).reshape(-1)
+    P = np.atleast_2d(np.asarray(Pzk, dtype=np.float64))
+    chis = np.asarray(chis, dtype=np.float64).reshape(-1)
+    if P.shape != (chis.size, ks.size):
+        raise ValueError(f"Pzk must have shape (nz, nq) = {(chis.size, ks.size)}, got {P.shape}")
+    x = ks[None, :] * chis[:, None] * theta_s
+    zero = x == 0.0
+    win = np.where(zero, 1.0, 2.0 * j1(x) / np.where(zero, 1.0, x))
+    return np.sum((simpson_weights(ks) * ks)[None, :] * P * win * win, axis=1) / (2.0 * np.pi)
+
+
+def ssc_limber_tables(model, ells, npairs, windows=None, fsky=None, sigma_b=None):
+    """The host tables of cl_cov_ssc: (idx, frac, g, zscale) - the Limber samples of the multipoles, the z weights
+    g = trapz weight H^3 sigma_b / chi^4 and zscale (npairs, nz) = W1 W2 of each pair.  Everything that can be refused
+    is, here."""
+    ells = np.asarray(ells, dtype=np.float64).reshape(-1)
+    zs = np.asarray(model.zs, dtype=np.float64).reshape(-1)
+    if zs.size < 2:
+        raise ValueError("cl_cov_ssc integrates over the model's redshifts: it needs at least two")
+    chis = np.asarray(model.comoving_radial_distance(zs), dtype=np.float64).reshape(-1)
+    hzs = np.asarray(model.h_of_z(zs), dtype=np.float64).reshape(-1)
+    if sigma_b is None:
+        if fsky is None:
+            raise ValueError("give sigma_b (nz,) or fsky")
+        from .cosmology import sigma2_kgrid
+        kq = sigma2_kgrid(model.p["sigma2_kmin"], model.p["sigma2_kmax"], model.p["sigma2_numks"])
+        sigma_b = sigma_b_disc(kq, model.sPzk, chis, fsky=fsky)
+    else:
+        sigma_b = np.asarray(sigma_b, dtype=np.float64)
+        if sigma_b.shape != zs.shape:
+            raise ValueError(f"sigma_b must have one entry per redshift ({zs.size}), got shape {sigma_b.shape}")
+    if windows is None:
+        windows = [(1, 1)] * npairs
+    if len(windows) != npairs:
+        raise ValueError(f"windows must have one (W1, W2) per pair ({npairs}), got {len(windows)}")
+    zscale = np.empty((npairs, zs.size))
+    for p, (W1, W2) in enumerate(windows):
+        zscale[p] = (np.broadcast_to(np.asarray(W1, dtype=np.float64), zs.shape)
+                     * np.broadcast_to(np.asarray(W2, dtype=np.float64), zs.shape))
+    idx, frac = limber_samples(ells, chis, model.ks, zs=zs)
+    g = trapz_weights(zs) * hzs ** 3 * sigma_b / chis ** 4
+    return idx, frac, g, zscale
+
+
+def cl_cov_ssc(model, ells, pairs, windows=None, fsky=None, sigma_b=None, damping=True):
+    """The super-sample covariance of the Limber spectra C_ell^{p} of the pairs p = (a, b), (np, n_ell, np, n_ell):
+
+        Cov[p,l,q,l'] = trapz_z[ H^3 sigma_b / chi^4  (W_p1 W_p2 R_p(z, (l + 1/2)/chi)) (W_q1 W_q2 R_q(z, (l' + 1/2)/chi)) ]
+
+    on the model's own zs (at least two), H in 1/Mpc and chi in Mpc as in limber_integral; R = dP / d delta_b is
+    HaloModel.response_device's at the Limber samples (limber_samples: a wavenumber outside the model's grid raises
+    ValueError).  windows[p] = (W1, W2), scalars or (nz,) arrays of limber_integral's conventions (default 1).
+    sigma_b (nz,) is the variance of the background mode per unit radial length, in Mpc; None: sigma_b_disc on the
+    model's sigma^2 grid and spectrum at fsky.  The measure is H^3 and not H: with C_ell = int dz H W1 W2 P / chi^2 the
+    kernel per d chi is H W, and <delta_b(z) delta_b(z')> = H delta_D(z - z') sigma_b.  The z sum is taken on the device,
+    in z order.  The result is not to be added to cl_cov_1halo's, whose measure differs."""
+    pairs = list(pairs)
+    idx, frac, g, zscale = ssc_limber_tables(model, ells, len(pairs), windows, fsky, sigma_b)
+    if idx.shape[1] == 0:
+        return np.empty((len(pairs), 0, len(pairs), 0))
+    return model.ssc_device(pairs, g, zscale=zscale, idx=idx, frac=frac, damping=damping).numpy()

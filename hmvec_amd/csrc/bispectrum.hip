@@ -6,26 +6,6 @@
 
 using namespace hmg;
 
-static int bis_leg(const hmg_tracer* t, BisLeg* L) {
-    REQUIRE(t->kind == HMG_TRACER_MATTER || t->kind == HMG_TRACER_HOD || t->kind == HMG_TRACER_PRESSURE,
-            "unknown tracer kind");
-    REQUIRE(t->d_prof, "tracer has no profile tensor");
-    L->kind = t->kind;
-    L->prof = t->d_prof;
-    L->cprof = nullptr;
-    L->Nc = L->Ns = L->ngal = nullptr;
-    if (t->kind == HMG_TRACER_HOD) {
-        REQUIRE(t->d_Nc && t->d_Ns && t->d_ngal, "HOD tracer needs Nc,Ns,ngal");
-        L->cprof = t->d_cprof;
-        L->Nc = t->d_Nc; L->Ns = t->d_Ns; L->ngal = t->d_ngal;
-    }
-    return 0;
-}
-
-static bool bis_same(const BisLeg& x, const BisLeg& y) {
-    return x.kind == y.kind && x.prof == y.prof && x.cprof == y.cprof && x.Nc == y.Nc && x.Ns == y.Ns && x.ngal == y.ngal;
-}
-
 // the launches of one call; d_bad holds the three words of the check
 static int bis_run(hmg_ctx* c, const BisArgs& A, const double* zweights, double* Bz, int* d_bad) {
     // the tables and the triangles are checked on the device before anything reads a tensor through them
@@ -56,6 +36,25 @@ static int bis_run(hmg_ctx* c, const BisArgs& A, const double* zweights, double*
                            zweights, A.B, Bz);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+// the prepass alone, for hmg_response (response.hip): see kernels/leg_form.hpp
+int hmg::bis_legs_launch(hmg_ctx* c, const BisLeg& L, int nz, int nm, int nk, int n, const double* nzm, const double* bh,
+                         const double* ms, const double* wm, const double* ks, const double* Pzk, double rho_m0,
+                         double kstar, const int* idx, const double* frac, double* J, double* Ps, double* Ds, double* Ks) {
+    BisArgs A = {};
+    A.nu = 1;
+    A.uq[0] = A.uq[1] = A.uq[2] = L;
+    A.nzm = nzm; A.bh = bh; A.ms = ms; A.wm = wm; A.ks = ks; A.Pzk = Pzk;
+    A.rho_m0 = rho_m0; A.kstar = kstar;
+    A.idx = idx; A.frac = frac;
+    A.nz = nz; A.nm = nm; A.nk = nk; A.n = n; A.nt = 0; A.chunk = bis_chunk(n);
+    // leg bit 0 also samples P, D and k; bit 1 writes the plane behind A.J and nothing else
+    A.J = Ps ? J : J - (size_t)nz * n;
+    A.Ps = Ps; A.Ds = Ds; A.Ks = Ks;
+    hipLaunchKernelGGL(bispectrum_legs_kernel, dim3(nz), dim3(BIS_THREADS), 0, c->stream, A, L, Ps ? 1 : 2);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

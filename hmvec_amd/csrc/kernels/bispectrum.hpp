@@ -4,28 +4,22 @@
 //     B3h[z,t] = sigma J_a(s1) J_b(s2) J_c(s3) B_tree(k1, k2, k3)
 // w_x the single-tracer weight of get_power_1halo's cross-spectrum case at a sample, I_xy = sum_m wm nzm bh w_x w_y.
 // Included by bispectrum.hip alone (its own translation unit: the headline path's units do not see these kernels).  The
-// tracer weights restate tracer_form / power_prep_kernel of kernels/power.hpp, which is not a stand-alone header.
+// form of one leg's weight is in kernels/leg_form.hpp, shared with response.hip.
 #pragma once
+#include "leg_form.hpp"
 
 namespace hmg {
 
-constexpr int BIS_THREADS = 256;
 constexpr int BIS_TPT = 4;                          // triangles per thread
 constexpr int BIS_BLOCK = BIS_THREADS * BIS_TPT;    // triangles per workgroup
 constexpr int BIS_MAXN = 256;                       // samples per redshift
 constexpr int BIS_MAXCHUNK = 32;                    // mass bins staged through LDS at a time, at most
 constexpr int BIS_ROW = 2048;                       // chunk * n <= BIS_ROW: 3 legs * 2048 * 8 B = 48 KB of staged weights
-constexpr int BIS_PREP_CHUNK = 256;                 // mass bins per step of the leg prepass
 
 // chunk length of the triangle kernel for n samples: 32 up to n = 64, 8 at n = 256 (the kernel's static LDS is
 // 55,040 B whatever n is: two workgroups fit a CU's 160 KB)
 static inline int bis_chunk(int n) { return BIS_ROW / n < BIS_MAXCHUNK ? BIS_ROW / n : BIS_MAXCHUNK; }
 
-struct BisLeg {                     // w(z,m,k) = c0(z,m) + c1(z,m) prof(z,m,k) + c2(z,m) cprof(z,m,k)
-    int kind;
-    const double *prof, *cprof;     // cprof: an HOD's central profile or NULL
-    const double *Nc, *Ns, *ngal;
-};
 struct BisArgs {
     BisLeg uq[3];                   // the distinct legs; slot[l] is leg l's entry (legs of one tracer are staged once)
     int nu, slot[3];
@@ -94,26 +88,6 @@ __device__ __forceinline__ double bis_F2(double p, double q, double r) {
     return fma(2.0 / 7.0 * mu, mu, fma(0.5 * mu, s, 5.0 / 7.0));
 }
 
-// the coefficients of one leg's weight at (z, m), its k -> 0 limit (lowk) and - of an HOD - Nc + Ns
-__device__ __forceinline__ void bis_leg_form(const BisLeg& L, size_t zm, int z, double mass, double rho_m0, double* c,
-                                             double& lowk, double& ngals) {
-    c[0] = c[1] = c[2] = 0.0;
-    ngals = 0.0;
-    if (L.kind == HMG_TRACER_MATTER) {
-        c[1] = mass / rho_m0;
-        lowk = c[1];
-    } else if (L.kind == HMG_TRACER_PRESSURE) {
-        c[1] = 1.0;
-        lowk = 0.0;
-    } else {
-        const double ng = L.ngal[z], nc = L.Nc[zm], ns = L.Ns[zm];
-        if (L.cprof) c[2] = nc / ng; else c[0] = nc / ng;
-        c[1] = ns / ng;
-        lowk = (nc + ns) / ng;
-        ngals = nc + ns;
-    }
-}
-
 __device__ __forceinline__ double bis_leg_node(const BisLeg& L, const double* c, size_t at) {
     double v = fma(c[1], L.prof[at], c[0]);
     if (L.cprof) v = fma(c[2], L.cprof[at], v);
@@ -141,18 +115,6 @@ __device__ __forceinline__ BisLeg bis_pick(const BisArgs& A, int u) {
     return L;
 }
 #undef BIS_PICK
-
-__device__ __forceinline__ double bis_block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int h = BIS_THREADS / 2; h > 0; h >>= 1) {
-        if (tid < h) red[tid] += red[tid + h];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 // Leg prepass, one launch per distinct leg (the leg is an argument of its own: picked from the argument block by a
 // run-time index it would go through scratch); `legs` has bit l set for every leg l of the triple that is this tracer,
@@ -315,11 +277,6 @@ __global__ __launch_bounds__(256) void bispectrum_zsum_kernel(int nz, int nt, co
     double s = 0.0;
     for (int z = 0; z < nz; ++z) s = fma(g[z], src[(size_t)z * nt], s);
     Bz[e] = s;
-}
-
-// a sample's table entry is usable: left node on the grid, fraction in [0, 1], node nk - 1 only with fraction 0
-__device__ __forceinline__ bool bis_sample_ok(int id, double f, int nk) {
-    return id >= 0 && id < nk && f >= 0.0 && f <= 1.0 && !(id == nk - 1 && f != 0.0);
 }
 
 // Raises bad[0] for a bad sample table entry, bad[1] for a triangle index outside 0 .. n-1, bad[2] for a triangle that

@@ -1,28 +1,16 @@
 // 1-halo trispectrum of two spectra:
 //     T[z,i,j] = sum_m wm[m] nzm[z,m] s_ab[z,m,i] s_cd[z,m,j],
-// s the sampled square term of get_power_1halo.  Included by trispectrum.hip alone (its own translation unit: the
-// headline path's units do not see these kernels).  The tracer logic restates tracer_form / power_prep_kernel of
-// kernels/power.hpp, which is not a stand-alone header.
+// s the sampled square term of get_power_1halo (kernels/square_term.hpp, shared with response.hip).  Included by
+// trispectrum.hip alone (its own translation unit: the headline path's units do not see these kernels).
 #pragma once
+#include "square_term.hpp"
 
 namespace hmg {
 
 constexpr int TRI_TILE = 64;        // samples per tile side
 constexpr int TRI_CHUNK = 32;       // mass bins staged through LDS at a time
 constexpr int TRI_THREADS = 256;    // 16 x 16 threads, a 4 x 4 register block each
-constexpr int TRI_MAXT = 4;         // distinct tensors of one pair
-constexpr int TRI_NC = 1 + TRI_MAXT;
 
-struct TriTracer {
-    int kind;
-    int t_prof, t_cprof;            // slots in the pair's tensor list, -1 = none
-    const double *Nc, *Ns, *NcNs, *NsNsm1, *ngal;
-};
-struct TriSide {                    // one spectrum (a, b): its square term is form1 * form2
-    TriTracer a, b;
-    int nt;
-    const double* tens[TRI_MAXT];
-};
 struct TriArgs {
     TriSide ab, cd;
     const double *nzm, *ms, *wm;
@@ -32,55 +20,6 @@ struct TriArgs {
     double* T;                      // [nz][n][n]
     int nm, nk, n;
 };
-
-// c[0..TRI_NC) += the linear form of one tracer's 1-halo weight (c lives in LDS: the slots are run-time indices)
-__device__ __forceinline__ void tri_tracer_form(const TriTracer& T, size_t zm, int z, double mass, double rho_m0,
-                                                double* c) {
-    if (T.kind == HMG_TRACER_MATTER) {
-        c[1 + T.t_prof] += mass / rho_m0;
-    } else if (T.kind == HMG_TRACER_PRESSURE) {
-        c[1 + T.t_prof] += 1.0;
-    } else {
-        const double ng = T.ngal[z], nc = T.Nc[zm], ns = T.Ns[zm];
-        if (T.t_cprof >= 0) c[1 + T.t_cprof] += nc / ng; else c[0] += nc / ng;
-        c[1 + T.t_prof] += ns / ng;
-    }
-}
-
-// the two linear forms x1, x2 of the square term S = x1 * x2 of one spectrum at (z, m) (hmvec/hmvec.py:510-523)
-__device__ __forceinline__ void tri_square_forms(const TriSide& S, size_t zm, int z, double mass, double rho_m0,
-                                                 double* x1, double* x2) {
-    for (int i = 0; i < TRI_NC; ++i) x1[i] = x2[i] = 0.0;
-    if (S.a.kind == HMG_TRACER_HOD && S.b.kind == HMG_TRACER_HOD) {
-        // (2 u_c u_s <NcNs> + <Ns(Ns-1)> u_s^2)/ngal^2 of the FIRST name
-        const double ng = S.a.ngal[z], ng2 = ng * ng;
-        x1[1 + S.a.t_prof] = 1.0;
-        const double cc = 2.0 * S.a.NcNs[zm] / ng2;
-        if (S.a.t_cprof >= 0) x2[1 + S.a.t_cprof] += cc; else x2[0] += cc;
-        x2[1 + S.a.t_prof] += S.a.NsNsm1[zm] / ng2;
-    } else if (S.a.kind == HMG_TRACER_PRESSURE && S.b.kind == HMG_TRACER_PRESSURE) {
-        // pk_a**2 - first name only
-        tri_tracer_form(S.a, zm, z, mass, rho_m0, x1);
-        tri_tracer_form(S.a, zm, z, mass, rho_m0, x2);
-    } else {
-        tri_tracer_form(S.a, zm, z, mass, rho_m0, x1);
-        tri_tracer_form(S.b, zm, z, mass, rho_m0, x2);
-    }
-}
-
-// S(z, m, node) = x1(node) * x2(node) of one spectrum; `at` is the offset of (z, m, node) in its tensors
-__device__ __forceinline__ double tri_square_at(const TriSide& S, const double* x1, const double* x2, size_t at) {
-    double f1 = x1[0], f2 = x2[0];
-#pragma unroll
-    for (int t = 0; t < TRI_MAXT; ++t) {
-        if (t < S.nt) {
-            const double v = S.tens[t][at];
-            f1 = fma(x1[1 + t], v, f1);
-            f2 = fma(x2[1 + t], v, f2);
-        }
-    }
-    return f1 * f2;
-}
 
 // stage the interpolated square term of one spectrum at (z, m0 + ml, sample first + il) for ml < mc into dst[ml][il];
 // the thread's sample il = tid % 64 is the same for all of its elements, so its table entry (id, f) is read once by

@@ -6,43 +6,6 @@
 
 using namespace hmg;
 
-static int tri_slot(TriSide* S, const double* p) {
-    if (!p) return -1;
-    for (int i = 0; i < S->nt; ++i)
-        if (S->tens[i] == p) return i;
-    if (S->nt == TRI_MAXT) return -2;
-    S->tens[S->nt] = p;
-    return S->nt++;
-}
-
-static int tri_tracer(const hmg_tracer* t, bool stream, TriSide* S, TriTracer* out) {
-    REQUIRE(t->kind == HMG_TRACER_MATTER || t->kind == HMG_TRACER_HOD || t->kind == HMG_TRACER_PRESSURE,
-            "unknown tracer kind");
-    REQUIRE(t->d_prof, "tracer has no profile tensor");
-    if (t->kind == HMG_TRACER_HOD)
-        REQUIRE(t->d_Nc && t->d_Ns && t->d_NcNs && t->d_NsNsm1 && t->d_ngal, "HOD tracer needs Nc,Ns,NcNs,NsNsm1,ngal");
-    out->kind = t->kind;
-    out->t_prof = out->t_cprof = -1;
-    if (stream) {
-        out->t_prof = tri_slot(S, t->d_prof);
-        if (t->kind == HMG_TRACER_HOD) out->t_cprof = tri_slot(S, t->d_cprof);
-        REQUIRE(out->t_prof != -2 && out->t_cprof != -2, "bad tensor count");
-    }
-    out->Nc = t->d_Nc; out->Ns = t->d_Ns; out->NcNs = t->d_NcNs; out->NsNsm1 = t->d_NsNsm1; out->ngal = t->d_ngal;
-    return 0;
-}
-
-// one spectrum (a, b): its tracers and the distinct tensors its square term reads - of two HOD or two pressure names
-// the first name's alone (the reference's first-name-only rules)
-static int tri_side(const hmg_tracer* a, const hmg_tracer* b, TriSide* S) {
-    S->nt = 0;
-    for (auto& p : S->tens) p = nullptr;
-    const bool first_only = a->kind == b->kind && (a->kind == HMG_TRACER_HOD || a->kind == HMG_TRACER_PRESSURE);
-    if (tri_tracer(a, true, S, &S->a)) return 1;
-    if (tri_tracer(b, !first_only, S, &S->b)) return 1;
-    return 0;
-}
-
 // the launches of one call; d_bad is a device word of the caller's
 static int tri_run(hmg_ctx* c, TriArgs& A, int nz, int nm, int nk, int n, int tiles, const double* nzm, const double* ms,
                    const double* wm, double rho_m0, const int* idx, const double* frac, const double* scale,

@@ -21,6 +21,7 @@ import scipy.constants as constants
 
 from . import _native as nat
 from . import bispectrum as bispec
+from . import cov as covmod
 from . import realspace, spectra, stages
 from .cosmology import Cosmology, _is_shared_product, sigma2_kgrid, sigma2_weights
 from .params import battaglia_defaults, default_params
@@ -1347,6 +1348,95 @@ class HaloModel(Cosmology):
             raise ValueError(f"term must be one of {bispec.TERMS}, got {term!r}")
         B = self.bispectrum_device(name, name2, name3, triangles=triangles, kindex=kindex, damping=damping)[0]
         return bispec.pick_term(B.numpy(), term)
+
+    # ------------------------------------------------------------------ response and super-sample covariance (section 17)
+    # R_ab = dP_ab / d delta_b at sample wavenumbers for several pairs at once (hmg_response) and the rank-nz contraction
+    # Cov = sum_z g r r of such responses (hmg_ssc); only (np, nz, n) and (np n)^2 results cross.  The host side of the
+    # contract - sigma_b, the Limber tables, the slope table - is cov.py.
+    RESPONSE_MAX_PAIRS = 16
+
+    def _response_request(self, pairs, kindex, idx, frac, scale):
+        """(pairs as names, records, tables) of a response request.  Every refusal happens here on the host, before any
+        launch."""
+        pairs = [(a, a if b is None else b) for a, b in ([p, None] if isinstance(p, str) else p for p in pairs)]
+        if len(pairs) < 1:
+            raise ValueError("pairs is empty: the response needs at least one (name, name2)")
+        if len(pairs) > self.RESPONSE_MAX_PAIRS:
+            raise ValueError(f"{len(pairs)} pairs; at most {self.RESPONSE_MAX_PAIRS} are taken in one call")
+        recs = self._resolve(*[nm_ for p in pairs for nm_ in p])
+        for r in recs:
+            if not r.same:
+                raise ValueError(f"response of {pairs!r}: the 1-halo and 2-halo lookups resolve {r.name!r} differently "
+                                 f"(it names both an HOD and a profile)")
+        tables = self._trispectrum_tables(kindex, idx, frac, scale, False)
+        n = tables[0].shape[1]
+        if n > bispec.MAX_SAMPLES:
+            raise ValueError(f"kindex / idx asks for {n} samples per redshift; the response takes at most "
+                             f"{bispec.MAX_SAMPLES}: pass a shorter kindex")
+        return pairs, recs, tables
+
+    def _response_launch(self, recs, tables, damping, parts):
+        nz, nm, nk, n, npairs = self._nz, self._nm, self._nk, tables[0].shape[1], len(recs) // 2
+        ctx = self._main(needs_aux=True)
+        # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
+        tr = (nat.Tracer * len(recs))(*[self._tracer(r, 1) for r in recs])
+        d_idx, d_frac, d_scale = ctx.upload_int32(tables[0]), ctx.upload(tables[1]), ctx.upload(tables[2])
+        d_dlnP = self._dev("dlnP", lambda: covmod.dlnp_table(self.ks, self.Pzk))
+        R = ctx.empty((npairs, nz, n))
+        P = ctx.empty((3, npairs, nz, n)) if parts else None
+        ctx.call("hmg_response", nz, nm, nk, n, npairs, tr, self._d_nzm.ptr, self._d_bh.ptr, self._d_ms().ptr,
+                 self._d_wm().ptr, self._d_ks().ptr, self._d_Pzk().ptr, d_dlnP.ptr, self._rho_m0(),
+                 float(self.p["kstar_damping"]) if damping else 0.0, d_idx.ptr, d_frac.ptr, d_scale.ptr, R.ptr, nat.ptr(P))
+        self._sync_point()
+        return R, P           # (the tables go back to the free list: whatever reads them was enqueued before)
+
+    def response_device(self, pairs, kindex=None, damping=True, idx=None, frac=None, scale=None, parts=False):
+        """R on the device, (np, nz, n): the response dP_ab / d delta_b of the halo-model spectrum of each pair (a, b) of
+        `pairs` (1 to 16; a lone name or (a, None) is (a, a)) to a long-wavelength density mode,
+
+            R = scale [ (47/21 - n_s/3) P2h + D I1 - (beta_a + beta_b) (P2h + D A1) ],
+
+        A1 the undamped 1-halo integral of get_power_1halo (first-name-only rules included), I1 the same integral weighted
+        with the halo bias, P2h = P_lin J_a J_b the 2-halo term of get_power_2halo, n_s the logarithmic slope of P_lin,
+        D the damping factor of get_power_1halo (damping=False: 1) and beta the mean galaxy bias of an HOD name (0 of a
+        matter or pressure name: a galaxy overdensity is defined against the local mean density).  The growth and
+        dilation factor takes the slope of P_lin only, not of the 2-halo brackets - the usual halo-model approximation.
+        Samples as for bispectrum_device (kindex, or idx / frac / scale tables; at most 256).  parts=True: (R, parts),
+        parts (3, np, nz, n) = (A1, I1, P2h), unscaled and undamped.  Two HOD names in one pair are allowed."""
+        _, recs, tables = self._response_request(pairs, kindex, idx, frac, scale)
+        R, P = self._response_launch(recs, tables, damping, parts)
+        return (R, P) if parts else R
+
+    def get_power_response(self, name, name2=None, kindex=None, damping=True):
+        """dP_ab(z, k) / d delta_b of the pair (name, name2; default name) at the nodes ks[kindex] (default: all, at most
+        256), shape (nz, n); see response_device."""
+        return self.response_device([(name, name2)], kindex=kindex, damping=damping).numpy()[0]
+
+    def ssc_device(self, pairs, zweights, zscale=None, kindex=None, damping=True, idx=None, frac=None, scale=None):
+        """Cov on the device, (np, n, np, n): Cov[p,i,q,j] = sum_z zweights[z] r[p,z,i] r[q,z,j], in z order, of the
+        responses r[p,z,s] = zscale[p][z] R_p[z,s] (response_device's; zscale (np, nz), default 1).  Each term is formed
+        as fma(r r, g, acc) with the weight on neither side: Cov[p,i,q,j] has the bits of Cov[q,j,p,i]."""
+        pairs, recs, tables = self._response_request(pairs, kindex, idx, frac, scale)
+        nz, n, npairs = self._nz, tables[0].shape[1], len(pairs)
+        zweights = np.ascontiguousarray(zweights, dtype=np.float64)
+        if zweights.shape != (nz,):
+            raise ValueError(f"zweights must have one entry per redshift ({nz}), got shape {zweights.shape}")
+        if zscale is not None:
+            zscale = np.ascontiguousarray(zscale, dtype=np.float64)
+            if zscale.shape != (npairs, nz):
+                raise ValueError(f"zscale must have shape (np, nz) = {(npairs, nz)}, got {zscale.shape}")
+        R, _ = self._response_launch(recs, tables, damping, False)
+        return self._ssc_launch(R, zweights, zscale)
+
+    def _ssc_launch(self, R, zweights, zscale):
+        npairs, nz, n = R.shape
+        ctx = self._main()
+        d_g = ctx.upload(zweights)
+        d_zs = ctx.upload(zscale) if zscale is not None else None
+        cov_ = ctx.empty((npairs, n, npairs, n))
+        ctx.call("hmg_ssc", nz, n, npairs, R.ptr, nat.ptr(d_zs), d_g.ptr, cov_.ptr)
+        self._sync_point()
+        return cov_
 
     # ------------------------------------------------------------------ cluster lensing (DESIGN.md section 10)
     # The per-halo scalars are formed on the host one lens redshift at a time (a few values per halo), so that a z slice

@@ -314,7 +314,7 @@ int hmg_profile_fft_logx(hmg_ctx* ctx, int nxs, const double* d_xs, double* d_lo
  * tensor-group route (ascending d_ks) the rows leave elements [0, nser[row] & ~(HMG_PREFIX_TILE-1)) UNWRITTEN, nser[row] being the length of the band (an array the context
  * owns).  hmg_power_batch* finds the tensor in the context's books by its pointer and EVALUATES the k tiles that lie
  * in the band with the device function the rows use - the same bits, no load; tracers carry nothing new.  Every other
- * native reader fills first, on its own: hmg_power, hmg_power_2halo_terms, hmg_trispectrum_1h, hmg_bispectrum,
+ * native reader fills first, on its own: hmg_power, hmg_power_2halo_terms, hmg_trispectrum_1h, hmg_bispectrum, hmg_response,
  * hmg_memcpy_d2h / _d2h_async / _d2d (source), hmg_fn2d / hmg_add / hmg_trapz_rows (inputs), and a batch that cannot
  * substitute (generic forms, the tensor not in slot 0).  The fill reads the row's c, r_s, z,
  * wavenumbers and series coefficients through the pointers the deferring launch was given: they must still hold what
@@ -720,7 +720,31 @@ int hmg_bispectrum(hmg_ctx* ctx, int nz, int nm, int nk, int n, int nt,
                    double* d_B /*[3][nz][nt] or NULL*/, double* d_Bz /*[3][nt] or NULL*/,
                    double* d_J /*[3][nz][n] or NULL*/);
 
-/* ---- z-slab gather over RCCL/xGMI -------------------------------------------------
+/* ---- response to a long-wavelength mode and super-sample covariance -------------------------
+ * hmg_response: d_R (np, nz, n), the response dP_ab / d delta_b of np spectra (a, b) = h_pairs[2p], h_pairs[2p+1] at the
+ * n samples per redshift (tables as for hmg_bispectrum; n <= 256, 1 <= np <= 16):
+ *   R[p,z,s] = scale [ (47/21 - n_s/3) P2h + D_s I1 - (beta_a + beta_b) (P2h + D_s A1) ]
+ *   A1 = sum_m wm nzm S_ab,  I1 = sum_m wm nzm bh S_ab,  S_ab the sampled square term of hmg_trispectrum_1h without the
+ *   scale (first-name-only rules included);  P2h = P_s J_a J_b with J_x, P_s, k_s, D_s of hmg_bispectrum (each leg under
+ *   its own name);  n_s the linear interpolant (frac == 0: the node itself) of d_dlnP (nz, nk), the logarithmic slope of
+ *   P_lin the caller tabulated;  beta_x = sum_m wm nzm bh (Nc + Ns) / ngal of an HOD leg, 0 of a matter or pressure leg.
+ * Scales and damping multiply finished sums.  d_parts (3, np, nz, n) = (A1, I1, P2h), or NULL.  Two HOD tracers in one
+ * pair are allowed.  The tables are checked on the device before any tensor is read through them (the conditions of
+ * hmg_trispectrum_1h) and the host waits for that answer: the call synchronises the current stream once and cannot be
+ * part of a captured step.  Tracers as for hmg_power (hints and bias overrides are not read).  fp64 on the vector units,
+ * one thread walks the whole mass axis in order, no atomics: bit-identical on repeat, an element depends only on its own
+ * (pair, z, sample), not on the other pairs, samples or redshifts of the call.
+ * hmg_ssc: d_cov (np n, np n),  Cov[p n + i, q n + j] = sum_z g[z] r[p,z,i] r[q,z,j],  r[p,z,s] = zscale[p,z] R[p,z,s]
+ * (d_zscale NULL: R itself), z in order, each term fma(r r, g, acc): Cov[a,b] has the bits of Cov[b,a].              */
+int hmg_response(hmg_ctx* ctx, int nz, int nm, int nk, int n, int np, const hmg_tracer* h_pairs /*[np][2]*/,
+                 const double* d_nzm, const double* d_bh, const double* d_ms, const double* d_wm, const double* d_ks,
+                 const double* d_Pzk, const double* d_dlnP /*[nz][nk]*/, double rho_m0, double kstar /*<= 0: no damping*/,
+                 const int* d_idx /*[nz][n]*/, const double* d_frac, const double* d_scale,
+                 double* d_R /*[np][nz][n]*/, double* d_parts /*[3][np][nz][n] or NULL*/);
+int hmg_ssc(hmg_ctx* ctx, int nz, int n, int np, const double* d_R /*[np][nz][n]*/,
+            const double* d_zscale /*[np][nz] or NULL*/, const double* d_g /*[nz]*/, double* d_cov /*[np n][np n]*/);
+
+/* ---- z-slab gather over RCCL/xGMI-------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */
 #define HMG_COMM_ID_BYTES 128

@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip and bispectrum.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip and response.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -56,13 +56,17 @@ KERNELS = [   # (label, regex on the mangled name)
     ("bispectrum_legs_kernel  (its leg prepass: I, C, b, J, P, D, k at the samples, bispectrum.hip)", r"22bispectrum_legs_kernelE"),
     ("bispectrum_zsum_kernel  (its z sum, bispectrum.hip)", r"22bispectrum_zsum_kernelE"),
     ("bispectrum_check_kernel  (its table and triangle check, bispectrum.hip)", r"23bispectrum_check_kernelE"),
+    ("response_pairs_kernel  (response of halo-model spectra to a long mode: A1, I1 and the epilogue, response.hip)", r"21response_pairs_kernelE"),
+    ("response_beta_kernel  (the HOD bias sum of a leg, response.hip)", r"20response_beta_kernelE"),
+    ("ssc_kernel  (super-sample contraction, 64 x 64 tile, response.hip)", r"10ssc_kernelE"),
+    ("response_check_kernel  (its table check, response.hip)", r"21response_check_kernelE"),
 ]
 
 
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
