@@ -1033,7 +1033,10 @@ int hmg_power_2halo_terms(hmg_ctx* c, int nz, int nm, int nk, const hmg_tracer* 
 template <int NT, int NTR, int V, bool W16, unsigned CODE = 0, bool SER = false>
 static int launch_power_batch(hmg_ctx* c, const BatchArgs& A, int nz) {
     const int per_block = 64 * V;
-    dim3 grid((A.nk + per_block - 1) / per_block, nz);
+    // a 1-D grid: the kernel turns the block id into its (k tile, z) itself, in the order of kernels/pb_map.hpp
+    const long nblocks = (long)((A.nk + per_block - 1) / per_block) * nz;
+    REQUIRE(nblocks <= 0x7fffffffL && A.nz == nz, "grid of the batched mass integrals");
+    dim3 grid((unsigned)nblocks);
     constexpr int NACC = NTR + NTR * (NTR + 1) / 2;
     const size_t lds = (size_t)8 * NACC * V * 64 * sizeof(double);
     int stop = -1;
@@ -1152,7 +1155,7 @@ static int pb_plan(hmg_ctx* c, int nz, int nm, int nk, const hmg_power_batch_des
     }
     A.ser_n = nullptr; A.ser_a = A.ser_cs = A.ser_rss = A.ser_zs = nullptr;
     A.nblk = nblk;
-    A.coef = coef; A.sidep = sidep; A.ks = d->d_ks; A.Pzk = d->d_Pzk; A.kstar = d->kstar; A.nm = nm; A.nk = nk;
+    A.coef = coef; A.sidep = sidep; A.ks = d->d_ks; A.Pzk = d->d_Pzk; A.kstar = d->kstar; A.nm = nm; A.nk = nk; A.nz = nz;
     bool vec2 = (nk % 2 == 0);
     for (int i = 0; i < Q.nt; ++i) vec2 = vec2 && (((uintptr_t)tens[i]) % 16 == 0);
     // thin z-slabs: narrower k tiles so that every CU still gets a workgroup, and sixteen wavefronts per

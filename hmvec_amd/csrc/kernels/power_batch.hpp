@@ -2,6 +2,8 @@
 // Part of the ONE translation unit hmgrid.hip (included there in this order; not a stand-alone header).
 #pragma once
 
+#include "pb_map.hpp"
+
 namespace hmg {
 
 // ---------------------------------------------------------------- K6b: all-pairs mass integrals
@@ -215,6 +217,7 @@ struct BatchArgs {
     double* P2h[PB_MAXPAIR];
     double kstar;
     int nm, nk;
+    int nz;                          // the launch is a 1-D grid of ntile nz blocks, ntile = ceil(nk / (64 V)): pb_map.hpp
     // series deferral (instantiations with SER): tensor 0 is an analytic NFW tensor whose row r holds nfw_series_short
     // in its first ser_n[r] wavenumbers, written or not - the rows' counts, series coefficients, c, r_s and the redshifts
     const int* ser_n;
@@ -254,8 +257,10 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) void power_batch_kernel(BatchArgs
     constexpr int NACC = NTR + NPAIR;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int z = blockIdx.y;
-    const int k0 = (blockIdx.x * 64 + lane) * V;
+    // which (k tile, z) this workgroup owns: the block order of pb_map.hpp, chosen for speed and for nothing else
+    int tile, z;
+    pb_map<PB_ORDER>((int)blockIdx.x, (A.nk + 64 * V - 1) / (64 * V), A.nz, tile, z);
+    const int k0 = (tile * 64 + lane) * V;
     const bool live = k0 < A.nk;
     double acc[NACC][V];      // [0, NTR): 2-halo integrals I_t; [NTR, NACC): 1-halo integrals of the pairs
 #pragma unroll
@@ -263,7 +268,7 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) void power_batch_kernel(BatchArgs
 #pragma unroll
         for (int v = 0; v < V; ++v) acc[a][v] = 0.0;
     const size_t zrow = (size_t)z * A.nm;
-    const int kend = min(A.nk, (int)(blockIdx.x + 1) * 64 * V);   // one past the last k of this tile
+    const int kend = min(A.nk, (tile + 1) * 64 * V);   // one past the last k of this tile
     const size_t kofs = live ? (size_t)k0 : 0;   // dead lanes re-read column 0 (their sums are never stored)
     // the bins of this wavefront, in order: position i -> mass bin (>= nm: no such bin)
     const int L = (A.nm + PB_NV - 1) / PB_NV;            // positions per slice
