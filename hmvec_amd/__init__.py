@@ -13,11 +13,12 @@ from .halomodel import HaloModel  # noqa: F401
 from .functions import *  # noqa: F401,F403  (the reference's free functions, GPU-backed)
 from .fft import generic_profile_fft  # noqa: F401  (hmvec/hmvec.py:3 star-imports it into the package)
 from .lensing import delta_sigma_nfw, sigma_nfw  # noqa: F401  (cluster lensing: batched projected NFW profiles)
+from .gasprofiles import projected_gnfw  # noqa: F401  (projected gas and pressure profiles: Sigma_gas, tau, y)
 from .realspace import projected_from_power, xi_from_power  # noqa: F401  (xi(r) and the J0 / J2 transforms of a tabulated spectrum)
 from .cov import (GaussianCov, bin_annuli, cl_cov_1halo, cl_cov_ssc, lensing_shape_noise, limber_samples,  # noqa: F401
                   shot_noise, sigma_b_disc)  # (covariances)
 from .bispectrum import F2, cl_bispectrum, tree_bispectrum  # noqa: F401  (bispectrum of three tracers)
-from . import bispectrum, cosmology, cov, fft, functions, ksz, lensing, params, quadrature, realspace, tinker, utils  # noqa: F401
+from . import bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, params, quadrature, realspace, tinker, utils  # noqa: F401
 from .functions import __all__ as _fn_all
 
 __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "generic_profile_fft", "sigma_nfw",
@@ -25,4 +26,5 @@ __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "ge
            "GaussianCov", "bin_annuli", "shot_noise", "lensing_shape_noise", "cl_cov_1halo", "limber_samples", "cov",
            "cl_cov_ssc", "sigma_b_disc",
            "F2", "tree_bispectrum", "cl_bispectrum", "bispectrum",
+           "projected_gnfw", "gasprofiles",
            "fft", "tinker", "utils", "cosmology", "params"] + list(_fn_all)

@@ -112,6 +112,8 @@ KERNEL_POWER, KERNEL_NFW, KERNEL_PROFILE_FFT = 0, 1, 2
 EVENT_SLOTS = 4096
 NFW_SERIES_STRIDE = 36     # HMG_NFW_SERIES_STRIDE
 ROWSC_STRIDE = 8            # HMG_ROWSC_STRIDE
+GNFW_SIGMA, GNFW_MEAN, GNFW_EXCESS, GNFW_GENERAL = 0, 1, 2, 4
+GNFW_TABLE_DOUBLES = 416    # HMG_GNFW_TABLE_DOUBLES
 
 _I, _D, _P, _Z = C.c_int, C.c_double, C.c_void_p, C.c_size_t
 # name -> argtypes (restype is int for all but hmg_last_error); mirrors include/hmgrid.h
@@ -204,6 +206,9 @@ SIGNATURES = {
                        _P, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P],
     "hmg_response": [_P, _I, _I, _I, _I, _I, C.POINTER(Tracer), _P, _P, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P],
     "hmg_ssc": [_P, _I, _I, _I, _P, _P, _P, _P],
+    "hmg_gnfw_projected": [_P, _I, _I, _I, _I, _P, _P, _P, _D, _P, _P],
+    "hmg_gnfw_projected_smooth": [_P, _I, _I, _I, _I, _P, _P, _P, _D, _P, _P, _P],
+    "hmg_gnfw_quad_table": [_P],
     "hmg_comm_unique_id": [C.c_char * COMM_ID_BYTES],
     "hmg_comm_init": [_P, C.c_char * COMM_ID_BYTES, _I, _I],
     "hmg_comm_allgather": [_P, _P, _P, _Z],
@@ -228,7 +233,7 @@ def kernel_source_sha16():
     csrc = os.path.join(_HERE, "csrc")
     names = ["hmgrid.hip", "longgrid.hip", "longgrid.hpp", "rowdev.hpp", "sici.hpp", "ldsfft.hpp", "fastmath.hpp", "Makefile",
              "lensing.hip", "j0.hpp", "j1.hpp", "ksz.hip", "realspace.hip", "j01.hpp", "trispectrum.hip", "bispectrum.hip",
-             "response.hip"]
+             "response.hip", "gasproj.hip", "i0e.hpp"]
     names += sorted(os.path.join("kernels", n) for n in os.listdir(os.path.join(csrc, "kernels")) if n.endswith(".hpp"))
     for name in names:          # (runtime.hip / comm.hip / hmctx.hpp hold no device code: not part of the kernel identity)
         with open(os.path.join(csrc, name), "rb") as f:

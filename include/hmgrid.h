@@ -744,6 +744,37 @@ int hmg_response(hmg_ctx* ctx, int nz, int nm, int nk, int n, int np, const hmg_
 int hmg_ssc(hmg_ctx* ctx, int nz, int n, int np, const double* d_R /*[np][nz][n]*/,
             const double* d_zscale /*[np][nz] or NULL*/, const double* d_g /*[nz]*/, double* d_cov /*[np n][np n]*/);
 
+/* ---- projected generalised-NFW profiles: gas surface density, optical depth, Compton y --------
+ * Row h is one profile f(x) = x^gamma (1 + x^alpha[h])^(-eta[h]), zero beyond x = xcut[h]; gamma > -1 is one number for
+ * the call.  d_x holds the projected radii in the rows' scaled units: (n, nr) when per_row_x != 0, else one row of nr shared
+ * by every profile.  d_out is (n, nr).  Radii, alpha and xcut must be positive and alpha eta - gamma > 1; the Python layer
+ * checks values, these check shapes, kind and gamma.
+ * hmg_gnfw_projected, by kind:
+ *   HMG_GNFW_SIGMA   F(s) = 2 int_0^sqrt(xcut^2 - s^2) f(sqrt(s^2 + l^2)) dl, exactly 0.0 for s >= xcut;
+ *   HMG_GNFW_MEAN    G(s) = (2/s^2) int_0^s F(s') s' ds', the cylinder mass over pi s^2 (N / (pi s^2) for s >= xcut);
+ *   HMG_GNFW_EXCESS  G(s) - F(s), the bits of the MEAN result minus the bits of the SIGMA result.
+ *   kind | HMG_GNFW_GENERAL evaluates rows with alpha == 1 like any other row (testing; they have a shorter evaluation).
+ *   Gauss-Legendre with 64 nodes in t, l = s sinh t, and in v, r = s v^2; one thread per output.
+ * hmg_gnfw_projected_smooth: kind HMG_GNFW_SIGMA only; F convolved with a circular Gaussian of width d_sigma[h] > 0 in the
+ *   same units, int ds' (s'/sig^2) exp(-(s - s')^2 / 2 sig^2) I0e(s s'/sig^2) F(s'); one wavefront per output.
+ * Both run on the current stream, fp64, fixed summation order, no atomics: bit-identical on repeat, and an output depends
+ * only on its own row and radius.  The first call on a device uploads the node table and so cannot be inside a captured
+ * step.
+ * hmg_gnfw_quad_table: the node table on the host (no device needed), HMG_GNFW_TABLE_DOUBLES doubles: u[64], w[64]
+ *   (Gauss-Legendre on [0, 1]), u^2, 2 ln u, 2 u w (the inner sphere), then for the 32-node rule U, W of the smoothing
+ *   sin^2(pi U / 2), cos^2(pi U / 2), W (pi/2) sin(pi U).                                                            */
+#define HMG_GNFW_SIGMA 0
+#define HMG_GNFW_MEAN 1
+#define HMG_GNFW_EXCESS 2
+#define HMG_GNFW_GENERAL 4
+#define HMG_GNFW_TABLE_DOUBLES 416
+int hmg_gnfw_projected(hmg_ctx* ctx, int n, int nr, int per_row_x, int kind, const double* d_alpha, const double* d_eta,
+                       const double* d_xcut, double gamma, const double* d_x, double* d_out);
+int hmg_gnfw_projected_smooth(hmg_ctx* ctx, int n, int nr, int per_row_x, int kind, const double* d_alpha,
+                              const double* d_eta, const double* d_xcut, double gamma, const double* d_x,
+                              const double* d_sigma, double* d_out);
+int hmg_gnfw_quad_table(double* h_table /*[HMG_GNFW_TABLE_DOUBLES]*/);
+
 /* ---- z-slab gather over RCCL/xGMI-------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */

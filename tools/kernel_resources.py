@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip and response.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip, response.hip and gasproj.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -60,13 +60,15 @@ KERNELS = [   # (label, regex on the mangled name)
     ("response_beta_kernel  (the HOD bias sum of a leg, response.hip)", r"20response_beta_kernelE"),
     ("ssc_kernel  (super-sample contraction, 64 x 64 tile, response.hip)", r"10ssc_kernelE"),
     ("response_check_kernel  (its table check, response.hip)", r"21response_check_kernelE"),
+    ("gnfw_projected_kernel  (projected gas / pressure profile: Sigma, mean, excess; gasproj.hip)", r"21gnfw_projected_kernelE"),
+    ("gnfw_smooth_kernel<4>  (the projection through a Gaussian beam, gasproj.hip)", r"18gnfw_smooth_kernelILi4EE"),
 ]
 
 
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response", "gasproj")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
