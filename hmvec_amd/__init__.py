@@ -18,7 +18,8 @@ from .realspace import projected_from_power, xi_from_power  # noqa: F401  (xi(r)
 from .cov import (GaussianCov, bin_annuli, cl_cov_1halo, cl_cov_ssc, lensing_shape_noise, limber_samples,  # noqa: F401
                   shot_noise, sigma_b_disc)  # (covariances)
 from .bispectrum import F2, cl_bispectrum, tree_bispectrum  # noqa: F401  (bispectrum of three tracers)
-from . import bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, params, quadrature, realspace, tinker, utils  # noqa: F401
+from .rsd import legendre_weights, mu_rule, virial_dispersion  # noqa: F401  (redshift-space wedges and multipoles)
+from . import bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, params, quadrature, realspace, rsd, tinker, utils  # noqa: F401
 from .functions import __all__ as _fn_all
 
 __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "generic_profile_fft", "sigma_nfw",
@@ -27,4 +28,5 @@ __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "ge
            "cl_cov_ssc", "sigma_b_disc",
            "F2", "tree_bispectrum", "cl_bispectrum", "bispectrum",
            "projected_gnfw", "gasprofiles",
+           "virial_dispersion", "mu_rule", "legendre_weights", "rsd",
            "fft", "tinker", "utils", "cosmology", "params"] + list(_fn_all)

@@ -775,6 +775,42 @@ int hmg_gnfw_projected_smooth(hmg_ctx* ctx, int n, int nr, int per_row_x, int ki
                               const double* d_sigma, double* d_out);
 int hmg_gnfw_quad_table(double* h_table /*[HMG_GNFW_TABLE_DOUBLES]*/);
 
+/* ---- redshift-space spectra of the dispersion halo model --------------------------------------
+ * One pair of tracers (a, b), matter or HOD (a pressure tracer is an error), at n nodes d_kindex (n) of the k grid,
+ * 1 <= n <= nk, the same for every redshift, and nmu values of mu, 1 <= nmu <= 32.  A species of a leg at (z, m, k) is a
+ * pair (value, alpha): (m/rho_m0 u, alpha_m) of a matter name; (Nc/ngal (u_c or 1), alpha_c) and (Ns/ngal u_s, alpha_s)
+ * of an HOD.  With x = k sigma_s[z,m] (d_sigma (nz, nm) >= 0, comoving Mpc) the weight of a leg is
+ *   w^s(mu) = sum_species value exp(-alpha^2 x^2 mu^2 / 2).
+ * hmg_rsd_wedges: d_out (2, nz, n, nmu) = (P1h, P2h),
+ *   P1h = damp[s] sum_m wm nzm S^s,  S^s = w^s_a w^s_b, or of two HOD tracers the first one's
+ *         2<NcNs>/ngal^2 u_c u_s exp(-(alpha_c^2 + alpha_s^2) x^2 mu^2 / 2) + <Ns(Ns-1)>/ngal^2 u_s^2 exp(-alpha_s^2 x^2 mu^2);
+ *   P2h = P_lin (J^s_a + f mu^2 K^s_a) (J^s_b + f mu^2 K^s_b),  J^s = (I^s + b) - C,  K^s = (V^s + 1) - C0,
+ *         I^s = sum_m wm nzm bh w^s,  V^s = sum_m wm nzm w^s,  C, C0 the same two sums of the k -> 0 weight without a
+ *         Gaussian, b = 1 of a matter tracer and the HOD bias sum of an HOD - operation by operation in this order.
+ *   d_damp (n) is the factor of the 1-halo term (the caller's damping, or ones), d_f (nz) the growth rate.
+ *   d_parts (4, nz, n, nmu) = (I^s_a, V^s_a, I^s_b, V^s_b), or NULL.
+ * hmg_rsd_multipoles: d_out (2, nz, n, 3), the multipoles l = 0, 2, 4 of the two terms.  The 1-halo ones are exact in mu:
+ *   Q_n = sum_m wm nzm sum_terms value M_n(t),  M_n(t) = int_0^1 mu^2n exp(-t mu^2) dmu (csrc/gauss_moments.hpp), t the
+ *   exponent's factor of mu^2;  P_0 = Q_0, P_2 = 5/2 (3 Q_1 - Q_0), P_4 = 9/8 ((35 Q_2 - 30 Q_1) + 3 Q_0), times d_damp.
+ *   d_Q (3, nz, n) = Q_n, or NULL.  The 2-halo ones are the rule sum_q d_wl[l][q] P2h(mu_q), q ascending, over the nmu nodes
+ *   d_mus with the weights d_wl (3, nmu) = (2l + 1) w_q L_l(mu_q) the caller tabulated.
+ * The table is checked on the device before any tensor is read through it and the host waits for that answer: a call
+ * synchronises the current stream once and cannot be part of a captured step.  Tracers as for hmg_power (hints and bias
+ * overrides are not read).  fp64 on the vector units, one thread walks the whole mass axis in order, no atomics:
+ * bit-identical on repeat, an element depends only on its own (z, sample, mu), not on the rest of the call.            */
+int hmg_rsd_wedges(hmg_ctx* ctx, int nz, int nm, int nk, int n, int nmu, const hmg_tracer* h_a, const hmg_tracer* h_b,
+                   const double* d_nzm, const double* d_bh, const double* d_ms, const double* d_wm, const double* d_ks,
+                   const double* d_Pzk, double rho_m0, const int* d_kindex /*[n]*/, const double* d_damp /*[n]*/,
+                   const double* d_mus /*[nmu]*/, const double* d_sigma /*[nz][nm]*/, const double* d_f /*[nz]*/,
+                   double alpha_m, double alpha_c, double alpha_s, double* d_out /*[2][nz][n][nmu]*/,
+                   double* d_parts /*[4][nz][n][nmu] or NULL*/);
+int hmg_rsd_multipoles(hmg_ctx* ctx, int nz, int nm, int nk, int n, int nmu, const hmg_tracer* h_a, const hmg_tracer* h_b,
+                       const double* d_nzm, const double* d_bh, const double* d_ms, const double* d_wm, const double* d_ks,
+                       const double* d_Pzk, double rho_m0, const int* d_kindex /*[n]*/, const double* d_damp /*[n]*/,
+                       const double* d_mus /*[nmu]*/, const double* d_wl /*[3][nmu]*/, const double* d_sigma /*[nz][nm]*/,
+                       const double* d_f /*[nz]*/, double alpha_m, double alpha_c, double alpha_s,
+                       double* d_out /*[2][nz][n][3]*/, double* d_Q /*[3][nz][n] or NULL*/);
+
 /* ---- z-slab gather over RCCL/xGMI-------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */

@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip, response.hip and gasproj.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip and rsd.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -62,13 +62,19 @@ KERNELS = [   # (label, regex on the mangled name)
     ("response_check_kernel  (its table check, response.hip)", r"21response_check_kernelE"),
     ("gnfw_projected_kernel  (projected gas / pressure profile: Sigma, mean, excess; gasproj.hip)", r"21gnfw_projected_kernelE"),
     ("gnfw_smooth_kernel<4>  (the projection through a Gaussian beam, gasproj.hip)", r"18gnfw_smooth_kernelILi4EE"),
+    ("rsd_wedge_kernel<true>  (redshift-space wedges P1h, P2h, 8 nodes of mu per thread, rsd.hip)", r"16rsd_wedge_kernelILb1EE"),
+    ("rsd_wedge_kernel<false>  (the 2-halo wedge alone, for the multipoles, rsd.hip)", r"16rsd_wedge_kernelILb0EE"),
+    ("rsd_multipole_kernel  (1-halo multipoles from the Gaussian moments, rsd.hip)", r"20rsd_multipole_kernelE"),
+    ("rsd_contract_kernel  (2-halo multipoles: the rule's sum over mu, rsd.hip)", r"19rsd_contract_kernelE"),
+    ("rsd_legs_kernel  (C, C0, b of a leg, rsd.hip)", r"15rsd_legs_kernelE"),
+    ("rsd_check_kernel  (its table check, rsd.hip)", r"16rsd_check_kernelE"),
 ]
 
 
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response", "gasproj")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response", "gasproj", "rsd")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
