@@ -6,58 +6,6 @@
 
 using namespace hmg;
 
-// the launches of one call; d_bad holds the three words of the check
-static int bis_run(hmg_ctx* c, const BisArgs& A, const double* zweights, double* Bz, int* d_bad) {
-    // the tables and the triangles are checked on the device before anything reads a tensor through them
-    const size_t count = (size_t)A.nz * (size_t)(A.n > A.nt ? A.n : A.nt);
-    int bad[3] = {0, 0, 0};
-    HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(bad), c->stream));
-    hipLaunchKernelGGL(bispectrum_check_kernel, grid1d(count, 256), dim3(256), 0, c->stream, A.nz, A.nk, A.n, A.nt, A.idx,
-                       A.frac, A.tri, A.ks, d_bad);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    REQUIRE(!bad[0], "a sample's left node is outside 0 .. nk-1, its fraction outside [0, 1], or it is node nk-1 with a "
-                     "non-zero fraction");
-    REQUIRE(!bad[1], "a triangle names a sample outside 0 .. n-1");
-    REQUIRE(!bad[2], "a triangle does not close at some redshift: k_max > (k_mid + k_min)(1 + 2^-40)");
-    for (int u = 0; u < A.nu; ++u) {            // one prepass per distinct leg; it writes J for every leg it serves
-        int legs = 0;
-        for (int l = 0; l < 3; ++l) legs |= (A.slot[l] == u) << l;
-        hipLaunchKernelGGL(bispectrum_legs_kernel, dim3(A.nz), dim3(BIS_THREADS), 0, c->stream, A, A.uq[u], legs);
-        HIP_TRY(hipGetLastError());
-    }
-    if (A.B) {
-        hipLaunchKernelGGL(bispectrum_kernel, dim3((A.nt - 1) / BIS_BLOCK + 1, A.nz), dim3(BIS_THREADS), 0, c->stream, A);
-        HIP_TRY(hipGetLastError());
-    }
-    if (Bz) {
-        hipLaunchKernelGGL(bispectrum_zsum_kernel, grid1d((size_t)3 * A.nt, 256), dim3(256), 0, c->stream, A.nz, A.nt,
-                           zweights, A.B, Bz);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-// the prepass alone, for hmg_response (response.hip): see kernels/leg_form.hpp
-int hmg::bis_legs_launch(hmg_ctx* c, const BisLeg& L, int nz, int nm, int nk, int n, const double* nzm, const double* bh,
-                         const double* ms, const double* wm, const double* ks, const double* Pzk, double rho_m0,
-                         double kstar, const int* idx, const double* frac, double* J, double* Ps, double* Ds, double* Ks) {
-    BisArgs A = {};
-    A.nu = 1;
-    A.uq[0] = A.uq[1] = A.uq[2] = L;
-    A.nzm = nzm; A.bh = bh; A.ms = ms; A.wm = wm; A.ks = ks; A.Pzk = Pzk;
-    A.rho_m0 = rho_m0; A.kstar = kstar;
-    A.idx = idx; A.frac = frac;
-    A.nz = nz; A.nm = nm; A.nk = nk; A.n = n; A.nt = 0; A.chunk = bis_chunk(n);
-    // leg bit 0 also samples P, D and k; bit 1 writes the plane behind A.J and nothing else
-    A.J = Ps ? J : J - (size_t)nz * n;
-    A.Ps = Ps; A.Ds = Ds; A.Ks = Ks;
-    hipLaunchKernelGGL(bispectrum_legs_kernel, dim3(nz), dim3(BIS_THREADS), 0, c->stream, A, L, Ps ? 1 : 2);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 int hmg_bispectrum(hmg_ctx* c, int nz, int nm, int nk, int n, int nt, const hmg_tracer* ta, const hmg_tracer* tb,
                    const hmg_tracer* tc, const double* nzm, const double* bh, const double* ms, const double* wm,
                    const double* ks, const double* Pzk, double rho_m0, double kstar, const int* idx, const double* frac,
@@ -77,8 +25,7 @@ int hmg_bispectrum(hmg_ctx* c, int nz, int nm, int nk, int n, int nt, const hmg_
     for (auto t : tr) hods += t->kind == HMG_TRACER_HOD;
     REQUIRE(hods < 2, "two or more HOD tracers in one triple: the 1-halo term needs third factorial moments of the HOD, "
                       "which the model does not carry");
-    for (auto t : tr)       // (an NFW tensor with deferred series tiles is filled first)
-        if (series_ensure_whole(c, t->d_prof) || series_ensure_whole(c, t->d_cprof)) return 1;
+    if (tracers_ensure_whole(c, tr, 3)) return 1;
     BisArgs A;
     A.nu = 0;
     for (int l = 0; l < 3; ++l) {
@@ -90,23 +37,42 @@ int hmg_bispectrum(hmg_ctx* c, int nz, int nm, int nk, int n, int nt, const hmg_
         A.slot[l] = u;
     }
     for (int u = A.nu; u < 3; ++u) A.uq[u] = A.uq[0];
-    // The words of the check, the sampled P, D and k, and whichever of J and the per-z terms the caller did not ask for
-    // are one ordinary block of the context's allocator (no scratch arena grows here: a captured step may have an
-    // arena's address baked in).  It goes back to the free list before this returns; whatever reuses it is enqueued
-    // behind the kernels below.
+    A.g = {nz, nm, nk, nzm, bh, ms, wm, ks, Pzk, rho_m0};
+    A.s = {idx, frac, scale, n};
+    A.tri = tri; A.nt = nt; A.chunk = bis_chunk(n);
+    // the block: the words of the check, the sampled P, D and k, and whichever of J and the per-z terms the caller did
+    // not ask for
     const size_t zn = (size_t)nz * n, znt = (size_t)nz * nt;
     const bool need_b = B || Bz;
-    void* blk = nullptr;
-    if (hmg_malloc(c, 64 + 8 * (3 * zn + (J ? 0 : 3 * zn) + (need_b && !B ? 3 * znt : 0)), &blk)) return 1;
-    double* w = (double*)((char*)blk + 64);
-    A.Ps = w; A.Ds = w + zn; A.Ks = w + 2 * zn;
-    w += 3 * zn;
-    if (J) A.J = J; else { A.J = w; w += 3 * zn; }
-    A.B = B ? B : need_b ? w : nullptr;
-    A.nzm = nzm; A.bh = bh; A.ms = ms; A.wm = wm; A.ks = ks; A.Pzk = Pzk;
-    A.rho_m0 = rho_m0; A.kstar = kstar;
-    A.idx = idx; A.frac = frac; A.scale = scale; A.tri = tri;
-    A.nz = nz; A.nm = nm; A.nk = nk; A.n = n; A.nt = nt; A.chunk = bis_chunk(n);
-    const int rc = bis_run(c, A, zweights, Bz, (int*)blk);
-    return hmg_free(c, blk) || rc;
+    return with_block(c, 64 + 8 * (3 * zn + (J ? 0 : 3 * zn) + (need_b && !B ? 3 * znt : 0)), [&](void* blk) {
+        double* w = (double*)((char*)blk + 64);
+        A.Ps = w; A.Ds = w + zn; A.Ks = w + 2 * zn;
+        w += 3 * zn;
+        if (J) A.J = J; else { A.J = w; w += 3 * zn; }
+        A.B = B ? B : need_b ? w : nullptr;
+        // the tables and the triangles are checked on the device before anything reads a tensor through them
+        const size_t count = (size_t)nz * (size_t)(n > nt ? n : nt);
+        int* d_bad = (int*)blk;
+        int bad[3] = {0, 0, 0};
+        if (check_words(c, d_bad, bad, 3, [&] {
+                hipLaunchKernelGGL(bispectrum_check_kernel, grid1d(count, 256), dim3(256), 0, c->stream, nz, nk, n, nt, idx,
+                                   frac, tri, ks, d_bad);
+            }))
+            return 1;
+        REQUIRE(!bad[0], BAD_SAMPLE_TABLE);
+        REQUIRE(!bad[1], "a triangle names a sample outside 0 .. n-1");
+        REQUIRE(!bad[2], "a triangle does not close at some redshift: k_max > (k_mid + k_min)(1 + 2^-40)");
+        for (int u = 0; u < A.nu; ++u) {            // one prepass per distinct leg; it writes J for every leg it serves
+            LegOut out = {};
+            for (int l = 0; l < 3; ++l)
+                if (A.slot[l] == u) out.J[l] = A.J + l * zn;
+            if (A.slot[0] == u) { out.Ps = A.Ps; out.Ds = A.Ds; out.Ks = A.Ks; }
+            if (leg_prepass_launch(c, A.g, A.uq[u], idx, frac, n, kstar, out)) return 1;
+        }
+        if (A.B) {
+            hipLaunchKernelGGL(bispectrum_kernel, dim3((nt - 1) / BIS_BLOCK + 1, nz), dim3(BIS_THREADS), 0, c->stream, A);
+            HIP_TRY(hipGetLastError());
+        }
+        return Bz ? zsum_launch(c, nz, (size_t)3 * nt, nt, zweights, A.B, Bz) : 0;
+    });
 }

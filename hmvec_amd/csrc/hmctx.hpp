@@ -1,6 +1,6 @@
 // Internal header of libhmgrid: the context, the error plumbing and the host helpers shared by its translation units -
-// runtime.hip (contexts, memory, events, lanes, captured steps), comm.hip (RCCL) and hmgrid.hip (kernels + their launch
-// entry points).  Not part of the C ABI (include/hmgrid.h).
+// runtime.hip (contexts, memory, events, lanes, captured steps), comm.hip (RCCL) and the units that hold kernels and
+// their launch entry points (the Makefile lists them).  Not part of the C ABI (include/hmgrid.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -210,3 +210,36 @@ static inline void prefix_drop_block(hmg_ctx* c, void* p, size_t bytes) {
 int series_ensure_whole(hmg_ctx* c, const void* p);
 void series_forget(hmg_ctx* c, const void* p);
 static inline dim3 grid1d(size_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
+// every tensor of the tracers a call reads, whole (an NFW tensor with deferred series tiles is filled first)
+static inline int tracers_ensure_whole(hmg_ctx* c, const hmg_tracer* t, int count) {      // (a contiguous array)
+    for (int i = 0; i < count; ++i)
+        if (series_ensure_whole(c, t[i].d_prof) || series_ensure_whole(c, t[i].d_cprof)) return 1;
+    return 0;
+}
+static inline int tracers_ensure_whole(hmg_ctx* c, const hmg_tracer* const* t, int count) {
+    for (int i = 0; i < count; ++i)
+        if (tracers_ensure_whole(c, t[i], 1)) return 1;
+    return 0;
+}
+// The temporaries of one call that cannot be part of a captured step - the words of its table check, what its prepasses
+// leave for its main kernel, outputs the caller did not ask for - are ONE ordinary block of the context's allocator, live
+// while f(block) enqueues the call (no scratch arena grows here: a captured step may have an arena's address baked in).
+// It goes back to the free list before the call returns; whatever reuses it is enqueued behind the kernels of f.
+template <class F>
+static inline int with_block(hmg_ctx* c, size_t bytes, F f) {
+    void* blk = nullptr;
+    if (hmg_malloc(c, bytes, &blk)) return 1;
+    const int rc = f(blk);
+    return hmg_free(c, blk) || rc;
+}
+// A device-side check and its answer: zero `words` ints at d_bad, run `launch` (it enqueues the kernel that raises them),
+// copy them to `bad` and wait for the stream.
+template <class F>
+static inline int check_words(hmg_ctx* c, int* d_bad, int* bad, int words, F launch) {
+    HIP_TRY(hipMemsetAsync(d_bad, 0, words * sizeof(int), c->stream));
+    launch();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(bad, d_bad, words * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}

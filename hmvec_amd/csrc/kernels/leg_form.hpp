@@ -1,9 +1,10 @@
 // One leg of a halo-model spectrum: the weight w(z,m,k) of a single tracer in get_power_1halo's cross-spectrum case as a
 // linear form in its tensors, its k -> 0 limit and the HOD bias term - the pieces of the 2-halo bracket J that the units
-// which form it share: bispectrum.hip and response.hip (section 17).  Device functions and host
-// helpers only, no kernel.  The tracer weights restate tracer_form / power_prep_kernel of kernels/power.hpp, which is
-// not a stand-alone header.
+// which form it share: sampled.hip (the leg prepass and the leg sums), bispectrum.hip,
+// response.hip (section 17) and rsd.hip (section 19).  Device functions and host helpers only, no kernel.  The tracer
+// weights restate tracer_form / power_prep_kernel of kernels/power.hpp, which is not a stand-alone header.
 #pragma once
+#include "sampled.hpp"
 
 namespace hmg {
 
@@ -48,9 +49,17 @@ __device__ __forceinline__ double bis_block_sum(double v, double* red) {
     return red[0];
 }
 
-// a sample's table entry is usable: left node on the grid, fraction in [0, 1], node nk - 1 only with fraction 0
-__device__ __forceinline__ bool bis_sample_ok(int id, double f, int nk) {
-    return id >= 0 && id < nk && f >= 0.0 && f <= 1.0 && !(id == nk - 1 && f != 0.0);
+__device__ __forceinline__ double bis_leg_node(const BisLeg& L, const double* c, size_t at) {
+    double v = fma(c[1], L.prof[at], c[0]);
+    if (L.cprof) v = fma(c[2], L.cprof[at], v);
+    return v;
+}
+
+// the weight interpolated to a sample; `at` is the offset of (z, m, left node).  Node id + 1 is read only where f != 0.
+__device__ __forceinline__ double bis_leg_at(const BisLeg& L, const double* c, size_t at, double f) {
+    double v = bis_leg_node(L, c, at);
+    if (f != 0.0) v = fma(f, bis_leg_node(L, c, at + 1), (1.0 - f) * v);
+    return v;
 }
 
 // ---- host side: a leg from its hmg_tracer
@@ -73,13 +82,5 @@ static inline int bis_leg(const hmg_tracer* t, BisLeg* L) {
 static inline bool bis_same(const BisLeg& x, const BisLeg& y) {
     return x.kind == y.kind && x.prof == y.prof && x.cprof == y.cprof && x.Nc == y.Nc && x.Ns == y.Ns && x.ngal == y.ngal;
 }
-
-// The leg prepass of section 16 (bispectrum_legs_kernel) for one leg, enqueued on the context's stream by the unit that
-// owns the kernel (bispectrum.hip): J (nz, n) = (I + b) - C at the samples and, if Ps, P_lin, the damping factor and
-// the wavenumber at the samples (kstar <= 0: D = 1).  When Ps is NULL the zn doubles before J must belong to the
-// caller's block (the kernel addresses J as the second plane of an array).
-int bis_legs_launch(hmg_ctx* c, const BisLeg& L, int nz, int nm, int nk, int n, const double* nzm, const double* bh,
-                    const double* ms, const double* wm, const double* ks, const double* Pzk, double rho_m0, double kstar,
-                    const int* idx, const double* frac, double* J, double* Ps, double* Ds, double* Ks);
 
 }  // namespace hmg

@@ -4,8 +4,8 @@
 //     A1 = sum_m wm nzm S_ab,   I1 = sum_m wm nzm bh S_ab,   P2h = P_s J_a J_b
 //     Cov[p,i,q,j]   = sum_z g[z] r[p,z,i] r[q,z,j],   r[p,z,s] = zscale[p][z] R_p[z,s]
 // S_ab the sampled square term of get_power_1halo (kernels/square_term.hpp, the code the trispectrum integrates), J, P,
-// D from the leg prepass of the bispectrum (bispectrum.hip), the form of a leg from kernels/leg_form.hpp.  Included by
-// response.hip alone (its own translation unit: the other units do not see these kernels).
+// D from the leg prepass and beta from the leg sums (both sampled.hip's), the form of a leg from kernels/leg_form.hpp.
+// Included by response.hip alone (its own translation unit: the other units do not see these kernels).
 #pragma once
 #include "leg_form.hpp"
 #include "square_term.hpp"
@@ -25,41 +25,16 @@ struct RespPair {                   // one spectrum of the request, read from de
 };
 struct RespArgs {
     const RespPair* pairs;          // [np]
-    const double *nzm, *bh, *ms, *wm, *dlnP;
-    double rho_m0;
-    const int* idx;                 // [nz][n] left node
-    const double *frac, *scale;     // [nz][n]
+    HaloGrid g;                     // (ks, Pzk are read by the leg prepass alone)
+    SampleTable s;
+    const double* dlnP;             // [nz][nk]
     const double *J;                // [nu][nz][n] by distinct leg
     const double *beta;             // [nu][nz]
     const double *Ps, *Ds;          // [nz][n]
     double* R;                      // [np][nz][n]
     double* parts;                  // [3][np][nz][n] = (A1, I1, P2h), or NULL
-    int nz, nm, nk, n, np;
+    int np;
 };
-
-// beta[z] = sum_m wm nzm bh (Nc + Ns) / ngal of an HOD leg: the bias sum b of the leg prepass by itself, formed as
-// bispectrum_legs_kernel forms it (per-thread strided partial sums over steps of BIS_PREP_CHUNK, then the block sum)
-// - the same bits.  A kernel of its own: the prepass keeps J = (I + b) - C and not b.  grid nz, BIS_THREADS threads.
-__global__ __launch_bounds__(BIS_THREADS) void response_beta_kernel(BisLeg L, int nm, const double* __restrict__ nzm,
-                                                                    const double* __restrict__ bh,
-                                                                    const double* __restrict__ ms,
-                                                                    const double* __restrict__ wm, double rho_m0,
-                                                                    double* __restrict__ beta) {
-    __shared__ double red[BIS_THREADS];
-    const int tid = threadIdx.x, z = blockIdx.x;
-    double accB = 0.0;
-    for (int m0 = 0; m0 < nm; m0 += BIS_PREP_CHUNK) {
-        if (tid < min(BIS_PREP_CHUNK, nm - m0)) {
-            const size_t zm = (size_t)z * nm + m0 + tid;
-            const double wnb = wm[m0 + tid] * nzm[zm] * bh[zm];
-            double c[3], lowk, ngals;
-            bis_leg_form(L, zm, z, ms[m0 + tid], rho_m0, c, lowk, ngals);
-            accB = fma(wnb, ngals, accB);
-        }
-    }
-    const double Bs = bis_block_sum(accB, red);
-    if (tid == 0) beta[z] = L.kind == HMG_TRACER_HOD ? Bs / L.ngal[z] : 0.0;
-}
 
 // grid (np, nz), RESP_THREADS threads: thread s owns sample s of pair blockIdx.x at redshift blockIdx.y and walks the
 // whole mass axis in order with two accumulators - no split over workgroups, no atomics: a result depends on its own
@@ -71,29 +46,29 @@ __global__ __launch_bounds__(RESP_THREADS) void response_pairs_kernel(RespArgs A
     __shared__ double cf[RESP_CHUNK * 2 * TRI_NC], sW[RESP_CHUNK], sWb[RESP_CHUNK];
     const int tid = threadIdx.x, p = blockIdx.x, z = blockIdx.y;
     const TriSide S = A.pairs[p].S;
-    const bool live = tid < A.n;
-    const size_t o = (size_t)z * A.n + tid;
+    const bool live = tid < A.s.n;
+    const size_t o = (size_t)z * A.s.n + tid;
     int id = 0;
     double f = 0.0;
-    if (live) { id = A.idx[o]; f = A.frac[o]; }
+    if (live) { id = A.s.idx[o]; f = A.s.frac[o]; }
     double a1 = 0.0, i1 = 0.0;
-    for (int m0 = 0; m0 < A.nm; m0 += RESP_CHUNK) {
-        const int mc = min(RESP_CHUNK, A.nm - m0);
+    for (int m0 = 0; m0 < A.g.nm; m0 += RESP_CHUNK) {
+        const int mc = min(RESP_CHUNK, A.g.nm - m0);
         __syncthreads();                       // the previous chunk has been consumed
         if (tid < mc) {
-            const size_t zm = (size_t)z * A.nm + m0 + tid;
-            tri_square_forms(S, zm, z, A.ms[m0 + tid], A.rho_m0, cf + tid * (2 * TRI_NC), cf + tid * (2 * TRI_NC) + TRI_NC);
-            const double wn = A.wm[m0 + tid] * A.nzm[zm];
+            const size_t zm = (size_t)z * A.g.nm + m0 + tid;
+            tri_square_forms(S, zm, z, A.g.ms[m0 + tid], A.g.rho_m0, cf + tid * (2 * TRI_NC), cf + tid * (2 * TRI_NC) + TRI_NC);
+            const double wn = A.g.wm[m0 + tid] * A.g.nzm[zm];
             sW[tid] = wn;
-            sWb[tid] = wn * A.bh[zm];
+            sWb[tid] = wn * A.g.bh[zm];
         }
         __syncthreads();
         if (live) {
-            const size_t at0 = ((size_t)z * A.nm + m0) * (size_t)A.nk + id;
+            const size_t at0 = ((size_t)z * A.g.nm + m0) * (size_t)A.g.nk + id;
             for (int ml = 0; ml < mc; ++ml) {
                 const double* x1 = cf + ml * (2 * TRI_NC);
                 const double* x2 = x1 + TRI_NC;
-                const size_t at = at0 + (size_t)ml * A.nk;
+                const size_t at = at0 + (size_t)ml * A.g.nk;
                 double s = tri_square_at(S, x1, x2, at);
                 if (f != 0.0) s = fma(f, tri_square_at(S, x1, x2, at + 1), (1.0 - f) * s);   // node id + 1 is read only here
                 a1 = fma(s, sW[ml], a1);
@@ -105,18 +80,18 @@ __global__ __launch_bounds__(RESP_THREADS) void response_pairs_kernel(RespArgs A
     {   // the epilogue, every operation rounded by itself in the order of the definition
 #pragma clang fp contract(off)
     const int la = A.pairs[p].la, lb = A.pairs[p].lb;
-    const size_t zn = (size_t)A.nz * A.n;
-    const double* dl = A.dlnP + (size_t)z * A.nk;
+    const size_t zn = (size_t)A.g.nz * A.s.n;
+    const double* dl = A.dlnP + (size_t)z * A.g.nk;
     double ns = dl[id];
     if (f != 0.0) ns = fma(f, dl[id + 1], (1.0 - f) * ns);
     const double p2h = A.Ps[o] * A.J[la * zn + o] * A.J[lb * zn + o];
     const double D = A.Ds[o];
-    const double bsum = A.beta[(size_t)la * A.nz + z] + A.beta[(size_t)lb * A.nz + z];
+    const double bsum = A.beta[(size_t)la * A.g.nz + z] + A.beta[(size_t)lb * A.g.nz + z];
     const double growth = (47.0 / 21.0 - ns / 3.0) * p2h;
     const double halo = D * i1;
     const double mean = bsum * (p2h + D * a1);
     const size_t e = (size_t)p * zn + o;
-    A.R[e] = A.scale[o] * ((growth + halo) - mean);
+    A.R[e] = A.s.scale[o] * ((growth + halo) - mean);
     if (A.parts) {
         const size_t plane = (size_t)A.np * zn;
         A.parts[e] = a1;
@@ -194,14 +169,6 @@ __global__ __launch_bounds__(SSC_THREADS) void ssc_kernel(int nz, int n, int N, 
             if (b < N) out[b] = acc[r][c];
         }
     }
-}
-
-// raises *bad (a plain store) if a sample's table entry is not usable; one thread per (z, sample)
-__global__ __launch_bounds__(256) void response_check_kernel(size_t count, int nk, const int* __restrict__ idx,
-                                                             const double* __restrict__ frac, int* __restrict__ bad) {
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= count) return;
-    if (!bis_sample_ok(idx[e], frac[e], nk)) *bad = 1;
 }
 
 }  // namespace hmg

@@ -9,7 +9,7 @@
 //     P2h[z,s,q]  = P_lin (J^s_a + f mu^2 K^s_a) (J^s_b + f mu^2 K^s_b)
 //     Q_n[z,s]    = sum_m wm nzm sum_terms v M_n((h_i + h_j) x^2),  M_n of gauss_moments.hpp; the 1-halo multipoles are
 //                   P_0 = Q_0, P_2 = 5/2 (3 Q_1 - Q_0), P_4 = 9/8 (35 Q_2 - 30 Q_1 + 3 Q_0), times damp[s]
-// The form of a leg is kernels/leg_form.hpp's (shared with bispectrum.hip and response.hip: device functions only).
+// The form of a leg is kernels/leg_form.hpp's (device functions only); C, C0, b of a leg are the leg sums of sampled.hip.
 // Included by rsd.hip alone (its own translation unit: the other units do not see these kernels).
 #pragma once
 #include "../gauss_moments.hpp"
@@ -28,10 +28,9 @@ struct RsdArgs {
     const double *NcNs, *NsNsm1;    // of leg a (two HOD names: the first name's square term)
     int same, hh;                   // leg b is leg a; both are HODs
     double ha0, ha1, hb0, hb1;      // alpha^2 / 2 of the two slots of each leg
-    const double *nzm, *bh, *ms, *wm, *ks, *Pzk;
+    HaloGrid g;
     const double *sigma;            // [nz][nm]
     const double *f;                // [nz]
-    double rho_m0;
     const int* kidx;                // [n] node of each sample
     const double* damp;             // [n] the factor of the 1-halo term
     const double* mus;              // [nmu]
@@ -40,54 +39,21 @@ struct RsdArgs {
     double* out;                    // wedges [2][nz][n][nmu]; multipoles [2][nz][n][3]
     double* parts;                  // wedges [4][nz][n][nmu] = (I_a, V_a, I_b, V_b); multipoles [3][nz][n] = Q_n; or NULL
     double* w2h;                    // multipoles: the 2-halo wedge [nz][n][nmu]
-    int nz, nm, nk, n, nmu;
+    int n, nmu;
 };
-
-// C = sum_m wm nzm bh lowk, C0 = sum_m wm nzm lowk and b (1 of a matter name, sum_m wm nzm bh (Nc + Ns) / ngal of an HOD)
-// of one leg: they depend neither on k nor on mu.  Per-thread strided partial sums over steps of BIS_PREP_CHUNK, then the
-// block sum - the order in which the leg prepass of section 16 forms C and b.  grid nz, BIS_THREADS threads.
-__global__ __launch_bounds__(BIS_THREADS) void rsd_legs_kernel(BisLeg L, int nz, int nm, const double* __restrict__ nzm,
-                                                               const double* __restrict__ bh,
-                                                               const double* __restrict__ ms,
-                                                               const double* __restrict__ wm, double rho_m0,
-                                                               double* __restrict__ out) {
-    __shared__ double red[BIS_THREADS];
-    const int tid = threadIdx.x, z = blockIdx.x;
-    double accC = 0.0, accC0 = 0.0, accB = 0.0;
-    for (int m0 = 0; m0 < nm; m0 += BIS_PREP_CHUNK) {
-        if (tid < min(BIS_PREP_CHUNK, nm - m0)) {
-            const size_t zm = (size_t)z * nm + m0 + tid;
-            const double wn = wm[m0 + tid] * nzm[zm];
-            const double wnb = wn * bh[zm];
-            double c[3], lowk, ngals;
-            bis_leg_form(L, zm, z, ms[m0 + tid], rho_m0, c, lowk, ngals);
-            accC = fma(wnb, lowk, accC);
-            accC0 = fma(wn, lowk, accC0);
-            accB = fma(wnb, ngals, accB);
-        }
-    }
-    const double C = bis_block_sum(accC, red);
-    const double C0 = bis_block_sum(accC0, red);
-    const double Bs = bis_block_sum(accB, red);
-    if (tid == 0) {
-        out[z] = C;
-        out[nz + z] = C0;
-        out[2 * nz + z] = L.kind == HMG_TRACER_HOD ? Bs / L.ngal[z] : 1.0;
-    }
-}
 
 // one thread per bin of the chunk: the coefficients of the slots, the weights and the dispersion into LDS
 __device__ __forceinline__ void rsd_stage(const RsdArgs& A, int z, int m, double* c) {
-    const size_t zm = (size_t)z * A.nm + m;
+    const size_t zm = (size_t)z * A.g.nm + m;
     double ca[3], cb[3], lowk, ngals;
-    bis_leg_form(A.a, zm, z, A.ms[m], A.rho_m0, ca, lowk, ngals);
+    bis_leg_form(A.a, zm, z, A.g.ms[m], A.g.rho_m0, ca, lowk, ngals);
     c[0] = ca[0] + ca[2];                      // (one of the two is zero)
     c[1] = ca[1];
     if (A.same) {
         c[2] = c[0];
         c[3] = c[1];
     } else {
-        bis_leg_form(A.b, zm, z, A.ms[m], A.rho_m0, cb, lowk, ngals);
+        bis_leg_form(A.b, zm, z, A.g.ms[m], A.g.rho_m0, cb, lowk, ngals);
         c[2] = cb[0] + cb[2];
         c[3] = cb[1];
     }
@@ -97,9 +63,9 @@ __device__ __forceinline__ void rsd_stage(const RsdArgs& A, int z, int m, double
         c[4] = 2.0 * A.NcNs[zm] / ng2;
         c[5] = A.NsNsm1[zm] / ng2;
     }
-    const double wn = A.wm[m] * A.nzm[zm];
+    const double wn = A.g.wm[m] * A.g.nzm[zm];
     c[6] = wn;
-    c[7] = wn * A.bh[zm];
+    c[7] = wn * A.g.bh[zm];
     c[8] = A.sigma[zm];
 }
 
@@ -130,7 +96,7 @@ __global__ __launch_bounds__(RSD_THREADS) void rsd_wedge_kernel(RsdArgs A) {
     const int nq = min(RSD_MU, A.nmu - q0);
     const bool live = s < A.n;
     const int id = live ? A.kidx[s] : 0;
-    const double k = A.ks[id];
+    const double k = A.g.ks[id];
     const bool useA0 = A.a.kind == HMG_TRACER_HOD, useB0 = A.b.kind == HMG_TRACER_HOD;
     double mu2[RSD_MU], s1[RSD_MU], Ia[RSD_MU], Va[RSD_MU], Ib[RSD_MU], Vb[RSD_MU];
 #pragma unroll
@@ -139,17 +105,17 @@ __global__ __launch_bounds__(RSD_THREADS) void rsd_wedge_kernel(RsdArgs A) {
         mu2[q] = mu * mu;
         s1[q] = Ia[q] = Va[q] = Ib[q] = Vb[q] = 0.0;
     }
-    for (int m0 = 0; m0 < A.nm; m0 += RSD_CHUNK) {
-        const int mc = min(RSD_CHUNK, A.nm - m0);
+    for (int m0 = 0; m0 < A.g.nm; m0 += RSD_CHUNK) {
+        const int mc = min(RSD_CHUNK, A.g.nm - m0);
         __syncthreads();                       // the previous chunk has been consumed
         if (tid < mc) rsd_stage(A, z, m0 + tid, cf + tid * RSD_NCF);
         __syncthreads();
         if (!live) continue;
-        const size_t at0 = ((size_t)z * A.nm + m0) * (size_t)A.nk + id;
+        const size_t at0 = ((size_t)z * A.g.nm + m0) * (size_t)A.g.nk + id;
         for (int ml = 0; ml < mc; ++ml) {
             const double* c = cf + ml * RSD_NCF;
             double ua0, ua1, ub0, ub1;
-            rsd_load(A, at0 + (size_t)ml * A.nk, ua0, ua1, ub0, ub1);
+            rsd_load(A, at0 + (size_t)ml * A.g.nk, ua0, ua1, ub0, ub1);
             const double pa0 = c[0] * ua0, pa1 = c[1] * ua1, pb0 = c[2] * ub0, pb1 = c[3] * ub1;
             const double t0 = c[4] * ua0 * ua1, t1 = c[5] * ua1 * ua1;
             const double wn = c[6], wnb = c[7];
@@ -186,10 +152,10 @@ __global__ __launch_bounds__(RSD_THREADS) void rsd_wedge_kernel(RsdArgs A) {
     if (!live) return;
     {   // the epilogue, every operation rounded by itself in the order of the definition
 #pragma clang fp contract(off)
-    const double Ca = A.legs_a[z], C0a = A.legs_a[A.nz + z], ba = A.legs_a[2 * A.nz + z];
-    const double Cb = A.legs_b[z], C0b = A.legs_b[A.nz + z], bb = A.legs_b[2 * A.nz + z];
-    const double P = A.Pzk[(size_t)z * A.nk + id], f = A.f[z];
-    const size_t plane = (size_t)A.nz * A.n * A.nmu;
+    const double Ca = A.legs_a[z], C0a = A.legs_a[A.g.nz + z], ba = A.legs_a[2 * A.g.nz + z];
+    const double Cb = A.legs_b[z], C0b = A.legs_b[A.g.nz + z], bb = A.legs_b[2 * A.g.nz + z];
+    const double P = A.g.Pzk[(size_t)z * A.g.nk + id], f = A.f[z];
+    const size_t plane = (size_t)A.g.nz * A.n * A.nmu;
     const size_t o = ((size_t)z * A.n + s) * A.nmu + q0;
     const double damp = ONEH ? A.damp[s] : 0.0;
 #pragma unroll
@@ -235,22 +201,22 @@ __global__ __launch_bounds__(RSD_THREADS) void rsd_multipole_kernel(RsdArgs A) {
     const int tid = threadIdx.x, s = blockIdx.x * RSD_THREADS + tid, z = blockIdx.y;
     const bool live = s < A.n;
     const int id = live ? A.kidx[s] : 0;
-    const double k = A.ks[id];
+    const double k = A.g.ks[id];
     const bool useA0 = A.a.kind == HMG_TRACER_HOD, useB0 = A.b.kind == HMG_TRACER_HOD;
     const double h00 = A.ha0 + A.hb0, h01 = A.ha0 + A.hb1, h10 = A.ha1 + A.hb0, h11 = A.ha1 + A.hb1;
     const bool mixed_alike = useA0 && useB0 && h01 == h10;
     double Q0 = 0.0, Q1 = 0.0, Q2 = 0.0;
-    for (int m0 = 0; m0 < A.nm; m0 += RSD_CHUNK) {
-        const int mc = min(RSD_CHUNK, A.nm - m0);
+    for (int m0 = 0; m0 < A.g.nm; m0 += RSD_CHUNK) {
+        const int mc = min(RSD_CHUNK, A.g.nm - m0);
         __syncthreads();                       // the previous chunk has been consumed
         if (tid < mc) rsd_stage(A, z, m0 + tid, cf + tid * RSD_NCF);
         __syncthreads();
         if (!live) continue;
-        const size_t at0 = ((size_t)z * A.nm + m0) * (size_t)A.nk + id;
+        const size_t at0 = ((size_t)z * A.g.nm + m0) * (size_t)A.g.nk + id;
         for (int ml = 0; ml < mc; ++ml) {
             const double* c = cf + ml * RSD_NCF;
             double ua0, ua1, ub0, ub1;
-            rsd_load(A, at0 + (size_t)ml * A.nk, ua0, ua1, ub0, ub1);
+            rsd_load(A, at0 + (size_t)ml * A.g.nk, ua0, ua1, ub0, ub1);
             const double wn = c[6];
             const double x = k * c[8], x2 = x * x;
             if (A.hh) {
@@ -272,7 +238,7 @@ __global__ __launch_bounds__(RSD_THREADS) void rsd_multipole_kernel(RsdArgs A) {
     if (!live) return;
     {   // the epilogue, every operation rounded by itself in the order of the definition
 #pragma clang fp contract(off)
-    const size_t zn = (size_t)A.nz * A.n, o = (size_t)z * A.n + s;
+    const size_t zn = (size_t)A.g.nz * A.n, o = (size_t)z * A.n + s;
     const double damp = A.damp[s];
     const double p2 = 2.5 * (3.0 * Q1 - Q0);
     const double p4 = 1.125 * ((35.0 * Q2 - 30.0 * Q1) + 3.0 * Q0);
@@ -290,7 +256,7 @@ __global__ __launch_bounds__(RSD_THREADS) void rsd_multipole_kernel(RsdArgs A) {
 // Two-halo multipoles: the rule's sum over the nodes of mu, ascending, of the 2-halo wedge with the weights
 // (2l + 1) w_q L_l(mu_q) the host tabulated.  One thread per (z, sample).
 __global__ __launch_bounds__(256) void rsd_contract_kernel(RsdArgs A) {
-    const size_t zn = (size_t)A.nz * A.n;
+    const size_t zn = (size_t)A.g.nz * A.n;
     const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= zn) return;
     const double* w = A.w2h + e * A.nmu;

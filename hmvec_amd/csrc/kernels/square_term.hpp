@@ -4,6 +4,7 @@
 // only, no kernel: each unit instantiates its own.  The tracer logic restates tracer_form / power_prep_kernel of
 // kernels/power.hpp, which is not a stand-alone header.
 #pragma once
+#include "sampled.hpp"
 
 namespace hmg {
 

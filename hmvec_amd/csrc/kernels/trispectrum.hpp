@@ -13,12 +13,9 @@ constexpr int TRI_THREADS = 256;    // 16 x 16 threads, a 4 x 4 register block e
 
 struct TriArgs {
     TriSide ab, cd;
-    const double *nzm, *ms, *wm;
-    double rho_m0;
-    const int* idx;                 // [nz][n] left node
-    const double *frac, *scale;     // [nz][n]
+    HaloGrid g;                     // (bh, ks, Pzk are not read)
+    SampleTable s;
     double* T;                      // [nz][n][n]
-    int nm, nk, n;
 };
 
 // stage the interpolated square term of one spectrum at (z, m0 + ml, sample first + il) for ml < mc into dst[ml][il];
@@ -55,11 +52,11 @@ __global__ __launch_bounds__(TRI_THREADS) void trispectrum_1h_kernel(TriArgs A) 
     const int tx = tid & 15, ty = tid >> 4;
     // this thread's sample of each side in the loader
     const int il = tid & (TRI_TILE - 1);
-    const bool liveA = i0 + il < A.n, liveB = j0 + il < A.n;
+    const bool liveA = i0 + il < A.s.n, liveB = j0 + il < A.s.n;
     int idA = 0, idB = 0;
     double fA = 0.0, fB = 0.0;
-    if (liveA) { const size_t o = (size_t)z * A.n + i0 + il; idA = A.idx[o]; fA = A.frac[o]; }
-    if (liveB) { const size_t o = (size_t)z * A.n + j0 + il; idB = A.idx[o]; fB = A.frac[o]; }
+    if (liveA) { const size_t o = (size_t)z * A.s.n + i0 + il; idA = A.s.idx[o]; fA = A.s.frac[o]; }
+    if (liveB) { const size_t o = (size_t)z * A.s.n + j0 + il; idB = A.s.idx[o]; fB = A.s.frac[o]; }
 
     double acc[4][4];
 #pragma unroll
@@ -67,25 +64,25 @@ __global__ __launch_bounds__(TRI_THREADS) void trispectrum_1h_kernel(TriArgs A) 
 #pragma unroll
         for (int c = 0; c < 4; ++c) acc[r][c] = 0.0;
 
-    for (int m0 = 0; m0 < A.nm; m0 += TRI_CHUNK) {
-        const int mc = min(TRI_CHUNK, A.nm - m0);
+    for (int m0 = 0; m0 < A.g.nm; m0 += TRI_CHUNK) {
+        const int mc = min(TRI_CHUNK, A.g.nm - m0);
         __syncthreads();                       // the previous chunk has been consumed
         if (tid < 2 * TRI_CHUNK) {             // the coefficient rows of the chunk: one thread per (side, m)
             const int ml = tid & (TRI_CHUNK - 1);
             if (ml < mc) {
-                const size_t zm = (size_t)z * A.nm + m0 + ml;
-                const double mass = A.ms[m0 + ml];
+                const size_t zm = (size_t)z * A.g.nm + m0 + ml;
+                const double mass = A.g.ms[m0 + ml];
                 if (tid < TRI_CHUNK) {
-                    tri_square_forms(A.ab, zm, z, mass, A.rho_m0, cfA + ml * (2 * TRI_NC), cfA + ml * (2 * TRI_NC) + TRI_NC);
-                    sW[ml] = A.wm[m0 + ml] * A.nzm[zm];
+                    tri_square_forms(A.ab, zm, z, mass, A.g.rho_m0, cfA + ml * (2 * TRI_NC), cfA + ml * (2 * TRI_NC) + TRI_NC);
+                    sW[ml] = A.g.wm[m0 + ml] * A.g.nzm[zm];
                 } else {
-                    tri_square_forms(A.cd, zm, z, mass, A.rho_m0, cfB + ml * (2 * TRI_NC), cfB + ml * (2 * TRI_NC) + TRI_NC);
+                    tri_square_forms(A.cd, zm, z, mass, A.g.rho_m0, cfB + ml * (2 * TRI_NC), cfB + ml * (2 * TRI_NC) + TRI_NC);
                 }
             }
         }
         __syncthreads();
-        tri_stage(A.ab, cfA, sA, z, m0, mc, A.nm, A.nk, liveA, idA, fA);
-        tri_stage(A.cd, cfB, sB, z, m0, mc, A.nm, A.nk, liveB, idB, fB);
+        tri_stage(A.ab, cfA, sA, z, m0, mc, A.g.nm, A.g.nk, liveA, idA, fA);
+        tri_stage(A.cd, cfB, sB, z, m0, mc, A.g.nm, A.g.nk, liveB, idB, fB);
         __syncthreads();
 #pragma unroll 4
         for (int ml = 0; ml < mc; ++ml) {
@@ -104,35 +101,15 @@ __global__ __launch_bounds__(TRI_THREADS) void trispectrum_1h_kernel(TriArgs A) 
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int i = i0 + ty * 4 + r;
-        if (i >= A.n) continue;
-        double* out = A.T + ((size_t)z * A.n + i) * (size_t)A.n;
-        const double sci = A.scale[(size_t)z * A.n + i];
+        if (i >= A.s.n) continue;
+        double* out = A.T + ((size_t)z * A.s.n + i) * (size_t)A.s.n;
+        const double sci = A.s.scale[(size_t)z * A.s.n + i];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int j = j0 + tx * 4 + c;
-            if (j < A.n) out[j] = acc[r][c] * (sci * A.scale[(size_t)z * A.n + j]);
+            if (j < A.s.n) out[j] = acc[r][c] * (sci * A.s.scale[(size_t)z * A.s.n + j]);
         }
     }
-}
-
-// Tz[i,j] = sum_z g[z] T[z,i,j], z in order; one thread per (i, j)
-__global__ __launch_bounds__(256) void trispectrum_zsum_kernel(int nz, size_t nn, const double* __restrict__ g,
-                                                               const double* __restrict__ T, double* __restrict__ Tz) {
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nn) return;
-    double s = 0.0;
-    for (int z = 0; z < nz; ++z) s = fma(g[z], T[(size_t)z * nn + e], s);
-    Tz[e] = s;
-}
-
-// raises *bad if a sample's left node is off the grid, its fraction outside [0, 1], or it would read node nk
-__global__ __launch_bounds__(256) void trispectrum_check_kernel(size_t count, int nk, const int* __restrict__ idx,
-                                                                const double* __restrict__ frac, int* __restrict__ bad) {
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= count) return;
-    const int id = idx[e];
-    const double f = frac[e];
-    if (id < 0 || id >= nk || !(f >= 0.0 && f <= 1.0) || (id == nk - 1 && f != 0.0)) *bad = 1;
 }
 
 }  // namespace hmg

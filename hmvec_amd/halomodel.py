@@ -157,6 +157,14 @@ class HodEntry(MutableMapping):
         return len(set(self.dev) | set(self._vals))
 
 
+def _same_lookups(recs, what):
+    """Refuse a request of `what` that names something the 1-halo and 2-halo lookups resolve differently."""
+    for r in recs:
+        if not r.same:
+            raise ValueError(f"{what}: the 1-halo and 2-halo lookups resolve {r.name!r} differently (it names both an HOD "
+                             f"and a profile)")
+
+
 def _R_from_M(M, rho, delta):
     """hmvec/hmvec.py:627-628 for the handful of grid radii the constructor needs (host input
     preparation; the public, device-backed R_from_M lives in functions.py)."""
@@ -1197,9 +1205,10 @@ class HaloModel(Cosmology):
     # contracted on the device over the resident tensors (hmg_trispectrum_1h); only (nz, n, n) or (n, n) results cross.
     TRISPECTRUM_MAX_SAMPLES = 1024
 
-    def _trispectrum_tables(self, kindex, idx, frac, scale, damping):
-        """The checked (nz, n) sample tables of a trispectrum request: int32 idx, frac, scale (damping folded in).
-        Everything that can be refused is, here, before any launch."""
+    def _sample_tables(self, kindex, idx, frac, scale, damping, max_samples, what):
+        """The checked (nz, n) sample tables of a request of `what` ("the trispectrum", ...), which takes at most
+        max_samples per redshift: int32 idx, frac, scale (damping=True: folded in).  Everything that can be refused is,
+        here, before any launch."""
         nz, nk = self._nz, self._nk
         if idx is None:
             if frac is not None:
@@ -1220,10 +1229,10 @@ class HaloModel(Cosmology):
                 raise ValueError(f"idx must have shape (n,) or (nz, n) with nz = {nz}, got {idx.shape}")
         n = idx.shape[1]
         if n < 1:
-            raise ValueError("kindex / idx is empty: the trispectrum needs at least one sample")
-        if n > self.TRISPECTRUM_MAX_SAMPLES:
-            raise ValueError(f"kindex / idx asks for {n} samples per redshift; at most {self.TRISPECTRUM_MAX_SAMPLES} "
-                             f"are taken (the result has nz * n * n entries): pass a shorter kindex")
+            raise ValueError(f"kindex / idx is empty: {what} needs at least one sample")
+        if n > max_samples:
+            raise ValueError(f"kindex / idx asks for {n} samples per redshift; {what} takes at most {max_samples}: pass "
+                             f"a shorter kindex")
         if idx.min() < 0 or idx.max() > nk - 1:
             raise ValueError(f"kindex / idx must lie in 0 .. nk - 1 = {nk - 1}, got {idx.min()} .. {idx.max()}")
         frac = np.zeros((nz, n)) if frac is None else np.broadcast_to(np.asarray(frac, dtype=np.float64), (nz, n))
@@ -1241,6 +1250,31 @@ class HaloModel(Cosmology):
         return (np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(frac, dtype=np.float64),
                 np.ascontiguousarray(scale, dtype=np.float64))
 
+    def _trispectrum_tables(self, kindex, idx, frac, scale, damping):
+        """_sample_tables of a trispectrum request (the result has nz * n * n entries: at most 1024 samples)."""
+        return self._sample_tables(kindex, idx, frac, scale, damping, self.TRISPECTRUM_MAX_SAMPLES, "the trispectrum")
+
+    # what the requests of sections 15, 16, 17 and 19 share
+    def _zweights(self, zweights):
+        zweights = np.ascontiguousarray(zweights, dtype=np.float64).reshape(-1)
+        if zweights.size != self._nz:
+            raise ValueError(f"zweights must have one entry per redshift ({self._nz}), got {zweights.size}")
+        return zweights
+
+    @staticmethod
+    def _upload_tables(ctx, tables):
+        """(d_idx, d_frac, d_scale).  They may go back to the free list as soon as the call that reads them is enqueued:
+        whatever reuses them is enqueued behind it."""
+        return ctx.upload_int32(tables[0]), ctx.upload(tables[1]), ctx.upload(tables[2])
+
+    def _grid_ptrs(self, bias=True):
+        """The model block of a native call in the order of its arguments: nzm, bh, ms, wm, ks, Pzk, rho_m0 (bias=False,
+        the trispectrum: nzm, ms, wm, rho_m0)."""
+        if not bias:
+            return self._d_nzm.ptr, self._d_ms().ptr, self._d_wm().ptr, self._rho_m0()
+        return (self._d_nzm.ptr, self._d_bh.ptr, self._d_ms().ptr, self._d_wm().ptr, self._d_ks().ptr, self._d_Pzk().ptr,
+                self._rho_m0())
+
     def trispectrum_device(self, name, name2=None, name3=None, name4=None, kindex=None, damping=True, idx=None,
                            frac=None, scale=None, zweights=None, per_z=True):
         """(T, Tz) on the device: T (nz, n, n) the 1-halo trispectrum of the spectra (name, name2) and (name3, name4) -
@@ -1255,26 +1289,23 @@ class HaloModel(Cosmology):
         name2 = name if name2 is None else name2
         name3, name4 = (name if name3 is None else name3), (name2 if name4 is None else name4)
         recs = self._resolve(name, name2, name3, name4)
-        t_idx, t_frac, t_scale = self._trispectrum_tables(kindex, idx, frac, scale, damping)
+        tables = self._trispectrum_tables(kindex, idx, frac, scale, damping)
         if zweights is not None:
-            zweights = np.ascontiguousarray(zweights, dtype=np.float64).reshape(-1)
-            if zweights.size != self._nz:
-                raise ValueError(f"zweights must have one entry per redshift ({self._nz}), got {zweights.size}")
+            zweights = self._zweights(zweights)
         elif not per_z:
             raise ValueError("nothing asked for: per_z=False needs zweights")
-        nz, nm, nk, n = self._nz, self._nm, self._nk, t_idx.shape[1]
+        nz, nm, nk, n = self._nz, self._nm, self._nk, tables[0].shape[1]
         ctx = self._main(needs_aux=True)
         # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
         tr = [self._tracer(r, 1) for r in recs]
-        d_idx, d_frac, d_scale = ctx.upload_int32(t_idx), ctx.upload(t_frac), ctx.upload(t_scale)
+        d_idx, d_frac, d_scale = self._upload_tables(ctx, tables)
         d_g = ctx.upload(zweights) if zweights is not None else None
         T = ctx.empty((nz, n, n)) if per_z else None
         Tz = ctx.empty((n, n)) if zweights is not None else None
-        ctx.call("hmg_trispectrum_1h", nz, nm, nk, n, *(C.byref(t) for t in tr), self._d_nzm.ptr, self._d_ms().ptr,
-                 self._d_wm().ptr, self._rho_m0(), d_idx.ptr, d_frac.ptr, d_scale.ptr, nat.ptr(d_g), nat.ptr(T),
-                 nat.ptr(Tz))
+        ctx.call("hmg_trispectrum_1h", nz, nm, nk, n, *(C.byref(t) for t in tr), *self._grid_ptrs(bias=False), d_idx.ptr,
+                 d_frac.ptr, d_scale.ptr, nat.ptr(d_g), nat.ptr(T), nat.ptr(Tz))
         self._sync_point()
-        return T, Tz          # (the tables go back to the free list: whatever reads them was enqueued before)
+        return T, Tz
 
     def get_trispectrum_1halo(self, name, name2=None, name3=None, name4=None, kindex=None, damping=True):
         """1-halo trispectrum T(z; k_i, k_j) = int dm n(z,m) S_ab(z,m,k_i) S_cd(z,m,k_j), shape (nz, n, n), of the spectra
@@ -1312,38 +1343,29 @@ class HaloModel(Cosmology):
                 f"bispectrum of {triple!r}: two or more HOD names in one triple need the third factorial moments of the "
                 f"HOD for the 1-halo term, which the model does not carry (the product of two galaxy weights would "
                 f"count self-pairs)")
-        for r in recs:
-            if not r.same:
-                raise ValueError(f"bispectrum of {triple!r}: the 1-halo and 2-halo lookups resolve {r.name!r} differently "
-                                 f"(it names both an HOD and a profile)")
-        t_idx, t_frac, t_scale = self._trispectrum_tables(kindex, idx, frac, scale, False)
-        n = t_idx.shape[1]
-        if n > bispec.MAX_SAMPLES:
-            raise ValueError(f"kindex / idx asks for {n} samples per redshift; the bispectrum takes at most "
-                             f"{bispec.MAX_SAMPLES}: pass a shorter kindex")
-        tri = bispec.check_triangles(triangles, bispec.sample_wavenumbers(self.ks, t_idx, t_frac), self.zs)
+        _same_lookups(recs, f"bispectrum of {triple!r}")
+        tables = self._sample_tables(kindex, idx, frac, scale, False, bispec.MAX_SAMPLES, "the bispectrum")
+        n = tables[0].shape[1]
+        tri = bispec.check_triangles(triangles, bispec.sample_wavenumbers(self.ks, tables[0], tables[1]), self.zs)
         if zweights is not None:
-            zweights = np.ascontiguousarray(zweights, dtype=np.float64).reshape(-1)
-            if zweights.size != self._nz:
-                raise ValueError(f"zweights must have one entry per redshift ({self._nz}), got {zweights.size}")
+            zweights = self._zweights(zweights)
         elif not per_z and not want_J:
             raise ValueError("nothing asked for: per_z=False needs zweights")
         nz, nm, nk, nt = self._nz, self._nm, self._nk, tri.shape[0]
         ctx = self._main(needs_aux=True)
         # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
         tr = [self._tracer(r, 1) for r in recs]
-        d_idx, d_frac, d_scale = ctx.upload_int32(t_idx), ctx.upload(t_frac), ctx.upload(t_scale)
+        d_idx, d_frac, d_scale = self._upload_tables(ctx, tables)
         d_tri = ctx.upload_int32(tri)
         d_g = ctx.upload(zweights) if zweights is not None else None
         B = ctx.empty((3, nz, nt)) if per_z else None
         Bz = ctx.empty((3, nt)) if zweights is not None else None
         J = ctx.empty((3, nz, n)) if want_J else None
-        ctx.call("hmg_bispectrum", nz, nm, nk, n, nt, *(C.byref(t) for t in tr), self._d_nzm.ptr, self._d_bh.ptr,
-                 self._d_ms().ptr, self._d_wm().ptr, self._d_ks().ptr, self._d_Pzk().ptr, self._rho_m0(),
+        ctx.call("hmg_bispectrum", nz, nm, nk, n, nt, *(C.byref(t) for t in tr), *self._grid_ptrs(),
                  float(self.p["kstar_damping"]) if damping else 0.0, d_idx.ptr, d_frac.ptr, d_scale.ptr, d_tri.ptr,
                  nat.ptr(d_g), nat.ptr(B), nat.ptr(Bz), nat.ptr(J))
         self._sync_point()
-        return B, Bz, J       # (the tables go back to the free list: whatever reads them was enqueued before)
+        return B, Bz, J
 
     def get_bispectrum(self, name, name2=None, name3=None, triangles=None, kindex=None, term="total", damping=True):
         """The halo-model bispectrum B(z; k_1, k_2, k_3) of three tracers (missing names: the first), shape (nz, nt), at
@@ -1371,31 +1393,23 @@ class HaloModel(Cosmology):
         if len(pairs) > self.RESPONSE_MAX_PAIRS:
             raise ValueError(f"{len(pairs)} pairs; at most {self.RESPONSE_MAX_PAIRS} are taken in one call")
         recs = self._resolve(*[nm_ for p in pairs for nm_ in p])
-        for r in recs:
-            if not r.same:
-                raise ValueError(f"response of {pairs!r}: the 1-halo and 2-halo lookups resolve {r.name!r} differently "
-                                 f"(it names both an HOD and a profile)")
-        tables = self._trispectrum_tables(kindex, idx, frac, scale, False)
-        n = tables[0].shape[1]
-        if n > bispec.MAX_SAMPLES:
-            raise ValueError(f"kindex / idx asks for {n} samples per redshift; the response takes at most "
-                             f"{bispec.MAX_SAMPLES}: pass a shorter kindex")
-        return pairs, recs, tables
+        _same_lookups(recs, f"response of {pairs!r}")
+        return pairs, recs, self._sample_tables(kindex, idx, frac, scale, False, bispec.MAX_SAMPLES, "the response")
 
     def _response_launch(self, recs, tables, damping, parts):
         nz, nm, nk, n, npairs = self._nz, self._nm, self._nk, tables[0].shape[1], len(recs) // 2
         ctx = self._main(needs_aux=True)
         # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
         tr = (nat.Tracer * len(recs))(*[self._tracer(r, 1) for r in recs])
-        d_idx, d_frac, d_scale = ctx.upload_int32(tables[0]), ctx.upload(tables[1]), ctx.upload(tables[2])
+        d_idx, d_frac, d_scale = self._upload_tables(ctx, tables)
         d_dlnP = self._dev("dlnP", lambda: covmod.dlnp_table(self.ks, self.Pzk))
         R = ctx.empty((npairs, nz, n))
         P = ctx.empty((3, npairs, nz, n)) if parts else None
-        ctx.call("hmg_response", nz, nm, nk, n, npairs, tr, self._d_nzm.ptr, self._d_bh.ptr, self._d_ms().ptr,
-                 self._d_wm().ptr, self._d_ks().ptr, self._d_Pzk().ptr, d_dlnP.ptr, self._rho_m0(),
+        grid = self._grid_ptrs()
+        ctx.call("hmg_response", nz, nm, nk, n, npairs, tr, *grid[:6], d_dlnP.ptr, grid[6],
                  float(self.p["kstar_damping"]) if damping else 0.0, d_idx.ptr, d_frac.ptr, d_scale.ptr, R.ptr, nat.ptr(P))
         self._sync_point()
-        return R, P           # (the tables go back to the free list: whatever reads them was enqueued before)
+        return R, P
 
     def response_device(self, pairs, kindex=None, damping=True, idx=None, frac=None, scale=None, parts=False):
         """R on the device, (np, nz, n): the response dP_ab / d delta_b of the halo-model spectrum of each pair (a, b) of
@@ -1458,9 +1472,7 @@ class HaloModel(Cosmology):
             if r.kind1 == "p" or r.kind2 == "p":
                 raise ValueError(f"redshift-space spectrum of {pair!r}: {r.name!r} is a pressure profile, which has no "
                                  f"line-of-sight velocity in this model")
-            if not r.same:
-                raise ValueError(f"redshift-space spectrum of {pair!r}: the 1-halo and 2-halo lookups resolve {r.name!r} "
-                                 f"differently (it names both an HOD and a profile)")
+        _same_lookups(recs, f"redshift-space spectrum of {pair!r}")
         nz, nm, nk = self._nz, self._nm, self._nk
         kindex = rsdmod.check_kindex(kindex, nk)
         sigma_s = rsdmod.check_sigma(rsdmod.virial_dispersion(self) if sigma_s is None else sigma_s, nz, nm)
@@ -1479,8 +1491,7 @@ class HaloModel(Cosmology):
         extra = () if wl is None else (ctx.upload(np.ascontiguousarray(wl, dtype=np.float64)),)
         out = ctx.empty((2, nz, n, out_last))
         parts = ctx.empty(parts_shape(nz, n)) if parts_shape else None
-        ctx.call(entry, nz, nm, nk, n, nmu, C.byref(ta), C.byref(tb), self._d_nzm.ptr, self._d_bh.ptr, self._d_ms().ptr,
-                 self._d_wm().ptr, self._d_ks().ptr, self._d_Pzk().ptr, self._rho_m0(), d_k.ptr, d_damp.ptr, d_mus.ptr,
+        ctx.call(entry, nz, nm, nk, n, nmu, C.byref(ta), C.byref(tb), *self._grid_ptrs(), d_k.ptr, d_damp.ptr, d_mus.ptr,
                  *(e.ptr for e in extra), d_sig.ptr, d_f.ptr, *alphas, out.ptr, nat.ptr(parts))
         self._sync_point()
         return out, parts      # (the tables go back to the free list: whatever reads them was enqueued before)

@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip and rsd.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -50,31 +50,28 @@ KERNELS = [   # (label, regex on the mangled name)
     ("hankel_transform_kernel<256,4,false,true>  (W_2: Delta Sigma; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb0ELb1EE"),
     ("hankel_transform_kernel<256,4,true,true>  (W_0 and W_2 from one pass; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb1ELb1EE"),
     ("trispectrum_1h_kernel  (1-halo trispectrum, 64 x 64 tile, trispectrum.hip)", r"21trispectrum_1h_kernelE"),
-    ("trispectrum_zsum_kernel  (its z sum, trispectrum.hip)", r"23trispectrum_zsum_kernelE"),
-    ("trispectrum_check_kernel  (its table check, trispectrum.hip)", r"24trispectrum_check_kernelE"),
     ("bispectrum_kernel  (bispectrum of three tracers, 1024 triangles per workgroup, bispectrum.hip)", r"17bispectrum_kernelE"),
-    ("bispectrum_legs_kernel  (its leg prepass: I, C, b, J, P, D, k at the samples, bispectrum.hip)", r"22bispectrum_legs_kernelE"),
-    ("bispectrum_zsum_kernel  (its z sum, bispectrum.hip)", r"22bispectrum_zsum_kernelE"),
     ("bispectrum_check_kernel  (its table and triangle check, bispectrum.hip)", r"23bispectrum_check_kernelE"),
     ("response_pairs_kernel  (response of halo-model spectra to a long mode: A1, I1 and the epilogue, response.hip)", r"21response_pairs_kernelE"),
-    ("response_beta_kernel  (the HOD bias sum of a leg, response.hip)", r"20response_beta_kernelE"),
     ("ssc_kernel  (super-sample contraction, 64 x 64 tile, response.hip)", r"10ssc_kernelE"),
-    ("response_check_kernel  (its table check, response.hip)", r"21response_check_kernelE"),
     ("gnfw_projected_kernel  (projected gas / pressure profile: Sigma, mean, excess; gasproj.hip)", r"21gnfw_projected_kernelE"),
     ("gnfw_smooth_kernel<4>  (the projection through a Gaussian beam, gasproj.hip)", r"18gnfw_smooth_kernelILi4EE"),
     ("rsd_wedge_kernel<true>  (redshift-space wedges P1h, P2h, 8 nodes of mu per thread, rsd.hip)", r"16rsd_wedge_kernelILb1EE"),
     ("rsd_wedge_kernel<false>  (the 2-halo wedge alone, for the multipoles, rsd.hip)", r"16rsd_wedge_kernelILb0EE"),
     ("rsd_multipole_kernel  (1-halo multipoles from the Gaussian moments, rsd.hip)", r"20rsd_multipole_kernelE"),
     ("rsd_contract_kernel  (2-halo multipoles: the rule's sum over mu, rsd.hip)", r"19rsd_contract_kernelE"),
-    ("rsd_legs_kernel  (C, C0, b of a leg, rsd.hip)", r"15rsd_legs_kernelE"),
     ("rsd_check_kernel  (its table check, rsd.hip)", r"16rsd_check_kernelE"),
+    ("leg_prepass_kernel  (leg prepass of the bispectrum and the response: I, C, b, J, P, D, k at the samples, sampled.hip)", r"18leg_prepass_kernelE"),
+    ("leg_sums_kernel  (C, C0, b of a leg, for the response and the redshift-space spectra, sampled.hip)", r"15leg_sums_kernelE"),
+    ("zsum_kernel  (the z sum of the trispectrum and the bispectrum, sampled.hip)", r"11zsum_kernelE"),
+    ("sample_check_kernel  (the table check of the trispectrum and the response, sampled.hip)", r"19sample_check_kernelE"),
 ]
 
 
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response", "gasproj", "rsd")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
