@@ -19,7 +19,8 @@ from .cov import (GaussianCov, bin_annuli, cl_cov_1halo, cl_cov_ssc, lensing_sha
                   shot_noise, sigma_b_disc)  # (covariances)
 from .bispectrum import F2, cl_bispectrum, tree_bispectrum  # noqa: F401  (bispectrum of three tracers)
 from .rsd import legendre_weights, mu_rule, virial_dispersion  # noqa: F401  (redshift-space wedges and multipoles)
-from . import bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, params, quadrature, realspace, rsd, tinker, utils  # noqa: F401
+from .onepoint import char_exponent, cumulants, lambda_grid, pdf_from_exponent, ring_rule  # noqa: F401  (one-point PDF of a sum of halo profiles)
+from . import bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils  # noqa: F401
 from .functions import __all__ as _fn_all
 
 __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "generic_profile_fft", "sigma_nfw",
@@ -29,4 +30,5 @@ __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "ge
            "F2", "tree_bispectrum", "cl_bispectrum", "bispectrum",
            "projected_gnfw", "gasprofiles",
            "virial_dispersion", "mu_rule", "legendre_weights", "rsd",
+           "char_exponent", "cumulants", "pdf_from_exponent", "lambda_grid", "ring_rule", "onepoint",
            "fft", "tinker", "utils", "cosmology", "params"] + list(_fn_all)

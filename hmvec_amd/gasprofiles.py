@@ -42,6 +42,52 @@ def projected_gnfw(x, alpha, gamma, eta, xcut, kind="sigma", smooth=None, *, ctx
     smooth: None, or a non-negative scalar or length-N array of Gaussian widths in the same units (kind "sigma" only):
     F convolved with a circular Gaussian of that width; rows with width 0 take the unsmoothed route, bit for bit.
     Requires alpha > 0, gamma > -1, alpha eta - gamma > 1, xcut > 0.  Returns an (N, nR) float64 array."""
+    n, nr, per_row, x, alpha, gamma, eta, xcut, sig = _checked(x, alpha, gamma, eta, xcut, kind, smooth)
+    if n == 0 or nr == 0:
+        return np.empty((n, nr))
+    ctx = _context(ctx)
+    out, plain = None, None
+    if sig is None or not np.all(sig > 0):
+        out = _launch(ctx, n, nr, per_row, x, alpha, gamma, eta, xcut, kind, sig, True)
+        if sig is None:
+            return out.numpy()
+        plain = out.numpy()
+    res = _launch(ctx, n, nr, per_row, x, alpha, gamma, eta, xcut, kind, sig, False, out).numpy()
+    if plain is not None:
+        res = np.where((sig > 0)[:, None], res, plain)
+    return res
+
+
+def projected_gnfw_device(x, alpha, gamma, eta, xcut, smooth=None, *, ctx):
+    """projected_gnfw(kind="sigma") left on the device: the (N, nR) DeviceArray of the context, for a caller that
+    contracts the profiles there (HaloModel.get_y_char_exponent).  Same checks; smooth must be None or positive in every
+    row (no mixing of the two routes, which the host function does with a copy of each)."""
+    n, nr, per_row, x, alpha, gamma, eta, xcut, sig = _checked(x, alpha, gamma, eta, xcut, "sigma", smooth)
+    if n == 0 or nr == 0:
+        raise ValueError("no rows or no radii")
+    if sig is not None and not np.all(sig > 0):
+        raise ValueError("smooth must be positive in every row, or None")
+    return _launch(ctx, n, nr, per_row, x, alpha, gamma, eta, xcut, "sigma", sig, sig is None)
+
+
+def _launch(ctx, n, nr, per_row, x, alpha, gamma, eta, xcut, kind, sig, plain, out=None):
+    """One launch: the unsmoothed kernel (plain) or the smoothed one with the widths sig, where a row without a width gets
+    one (the quadrature needs a positive width; the caller takes that row's unsmoothed values)."""
+    flag = nat.GNFW_GENERAL if _force_general else 0
+    d_al, d_et, d_xc, d_x = (_dev(ctx, a) for a in (alpha, eta, xcut, x))
+    out = ctx.empty((n, nr)) if out is None else out
+    if plain:
+        ctx.call("hmg_gnfw_projected", n, nr, per_row, _KINDS[kind] | flag, d_al.ptr, d_et.ptr, d_xc.ptr, gamma, d_x.ptr,
+                 out.ptr)
+    else:
+        d_sig = _dev(ctx, np.where(sig > 0, sig, 1.0))
+        ctx.call("hmg_gnfw_projected_smooth", n, nr, per_row, _KINDS[kind] | flag, d_al.ptr, d_et.ptr, d_xc.ptr, gamma,
+                 d_x.ptr, d_sig.ptr, out.ptr)
+    return out
+
+
+def _checked(x, alpha, gamma, eta, xcut, kind, smooth):
+    """The checks of projected_gnfw: (n, nr, per_row, x, alpha, gamma, eta, xcut, sig), sig None or the widths per row."""
     if kind not in _KINDS:
         raise ValueError(f"kind must be one of {sorted(_KINDS)}, got {kind!r}")
     sizes = [np.size(a) for a in (alpha, eta, xcut)]
@@ -75,27 +121,7 @@ def projected_gnfw(x, alpha, gamma, eta, xcut, kind="sigma", smooth=None, *, ctx
     if sig is not None and kind != "sigma":
         raise NotImplementedError("smoothing is implemented for kind='sigma' only: the disc average of a convolved "
                                   "profile needs a further level of quadrature")
-    nr = x.shape[-1]
-    if n == 0 or nr == 0:
-        return np.empty((n, nr))
-    ctx = _context(ctx)
-    flag = nat.GNFW_GENERAL if _force_general else 0
-    d_al, d_et, d_xc, d_x = (_dev(ctx, a) for a in (alpha, eta, xcut, x))
-    out = ctx.empty((n, nr))
-    if sig is None or not np.all(sig > 0):
-        ctx.call("hmg_gnfw_projected", n, nr, per_row, _KINDS[kind] | flag, d_al.ptr, d_et.ptr, d_xc.ptr, gamma, d_x.ptr,
-                 out.ptr)
-    if sig is None:
-        return out.numpy()
-    plain = out.numpy() if not np.all(sig > 0) else None
-    # rows without a width: the quadrature needs a positive one, so give them one and take the unsmoothed values
-    d_sig = _dev(ctx, np.where(sig > 0, sig, 1.0))
-    ctx.call("hmg_gnfw_projected_smooth", n, nr, per_row, _KINDS[kind] | flag, d_al.ptr, d_et.ptr, d_xc.ptr, gamma,
-             d_x.ptr, d_sig.ptr, out.ptr)
-    res = out.numpy()
-    if plain is not None:
-        res = np.where((sig > 0)[:, None], res, plain)
-    return res
+    return n, x.shape[-1], per_row, x, alpha, gamma, eta, xcut, sig
 
 
 def quadrature_table():

@@ -53,6 +53,13 @@ def simpson_weights(x):
     return w
 
 
+def gauss_legendre_unit(n):
+    """(x, w): the n-node Gauss-Legendre rule on [0, 1] - numpy.polynomial.legendre.leggauss mapped from [-1, 1], the
+    mapping of rsd.mu_rule - nodes ascending."""
+    x, w = np.polynomial.legendre.leggauss(int(n))
+    return 0.5 * (x + 1.0), 0.5 * w
+
+
 def gradient_is_uniform(x):
     """np.gradient switches to its uniform-spacing stencil when every diff is bit-equal."""
     d = np.diff(np.asarray(x, dtype=np.float64))

@@ -811,6 +811,30 @@ int hmg_rsd_multipoles(hmg_ctx* ctx, int nz, int nm, int nk, int n, int nmu, con
                        const double* d_f /*[nz]*/, double alpha_m, double alpha_c, double alpha_s,
                        double* d_out /*[2][nz][n][3]*/, double* d_Q /*[3][nz][n] or NULL*/);
 
+/* ---- one-point statistics of a field that is a sum of halo profiles on the sky ----------------
+ * A sample is ring t of a halo (z, m): its signal s = d_signal[z][m][t], or d_amp[z][m] d_signal[z][m][t] (one rounded
+ * product) where d_amp is not NULL, and its weight W = ((d_zw[z] d_wm[m]) d_nzm[z][m]) d_area[z][m][t], rounded in this
+ * order.  Both entry points sum over the samples of the mass window m_lo <= m < m_hi (0 <= m_lo < m_hi <= nm) and every t.
+ * hmg_onepoint_exponent: the exponent of the characteristic function of Poisson-placed halos on the uniform grid
+ *   lambda_j = j dlambda, j < nlambda (dlambda finite and positive):
+ *     A[z][j] = sum W (exp(i lambda_j s) - 1),  Re = sum W (-2 sin^2(lambda_j s / 2)),  Im = sum W sin(lambda_j s),
+ *   the row z already multiplied by d_zw[z].  d_rows (nz, 2, nlambda): plane 0 of a row is the real part, plane 1 the
+ *   imaginary part.  d_total (2, nlambda) = sum_z d_rows[z], z ascending, or NULL.  A[z][0] is exactly 0 (written, not summed).
+ * hmg_onepoint_moments: d_rows (nz, 4), d_rows[z][p - 1] = sum W s^p, p = 1 .. 4 - the cumulants of the same field;
+ *   d_total (4) their sum over z, or NULL.
+ * fp64 on the vector units, sines and cosines by sici.hpp's reduction below 2^30 rad and the library's beyond, no atomics.
+ * The order of every addition depends on (m_hi - m_lo, nt) alone: bit-identical on repeat, and a row has the bits of the
+ * call with that redshift alone.  Launch-only on the current stream (the exponent takes one temporary block from the
+ * context's allocator when the window holds more than 4096 samples).                                                   */
+int hmg_onepoint_exponent(hmg_ctx* ctx, int nz, int nm, int nt, const double* d_signal /*[nz][nm][nt]*/,
+                          const double* d_area /*[nz][nm][nt]*/, const double* d_amp /*[nz][nm] or NULL*/,
+                          const double* d_nzm /*[nz][nm]*/, const double* d_wm /*[nm]*/, const double* d_zw /*[nz]*/,
+                          int m_lo, int m_hi, int nlambda, double dlambda, double* d_rows /*[nz][2][nlambda]*/,
+                          double* d_total /*[2][nlambda] or NULL*/);
+int hmg_onepoint_moments(hmg_ctx* ctx, int nz, int nm, int nt, const double* d_signal, const double* d_area,
+                         const double* d_amp, const double* d_nzm, const double* d_wm, const double* d_zw, int m_lo,
+                         int m_hi, double* d_rows /*[nz][4]*/, double* d_total /*[4] or NULL*/);
+
 /* ---- z-slab gather over RCCL/xGMI-------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */

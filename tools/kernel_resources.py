@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -61,6 +61,9 @@ KERNELS = [   # (label, regex on the mangled name)
     ("rsd_multipole_kernel  (1-halo multipoles from the Gaussian moments, rsd.hip)", r"20rsd_multipole_kernelE"),
     ("rsd_contract_kernel  (2-halo multipoles: the rule's sum over mu, rsd.hip)", r"19rsd_contract_kernelE"),
     ("rsd_check_kernel  (its table check, rsd.hip)", r"16rsd_check_kernelE"),
+    ("onepoint_exponent_kernel  (exponent of the one-point characteristic function, one lambda per lane, onepoint.hip)", r"24onepoint_exponent_kernelE"),
+    ("onepoint_moments_kernel  (cumulants of the one-point PDF, onepoint.hip)", r"23onepoint_moments_kernelE"),
+    ("onepoint_finish_kernel  (the sum over slices and over z, onepoint.hip)", r"22onepoint_finish_kernelE"),
     ("leg_prepass_kernel  (leg prepass of the bispectrum and the response: I, C, b, J, P, D, k at the samples, sampled.hip)", r"18leg_prepass_kernelE"),
     ("leg_sums_kernel  (C, C0, b of a leg, for the response and the redshift-space spectra, sampled.hip)", r"15leg_sums_kernelE"),
     ("zsum_kernel  (the z sum of the trispectrum and the bispectrum, sampled.hip)", r"11zsum_kernelE"),
@@ -71,7 +74,7 @@ KERNELS = [   # (label, regex on the mangled name)
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "sampled")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
