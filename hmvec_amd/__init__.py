@@ -20,6 +20,8 @@ from .cov import (GaussianCov, bin_annuli, cl_cov_1halo, cl_cov_ssc, lensing_sha
 from .bispectrum import F2, cl_bispectrum, tree_bispectrum  # noqa: F401  (bispectrum of three tracers)
 from .rsd import legendre_weights, mu_rule, virial_dispersion  # noqa: F401  (redshift-space wedges and multipoles)
 from .onepoint import char_exponent, cumulants, lambda_grid, pdf_from_exponent, ring_rule  # noqa: F401  (one-point PDF of a sum of halo profiles)
+from .hod_ensemble import central_differences, hod_sets, stencil  # noqa: F401  (HOD parameter ensembles: P_gg, P_gm of many sets)
+from . import hod_ensemble  # noqa: F401
 from . import bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils  # noqa: F401
 from .functions import __all__ as _fn_all
 
@@ -31,4 +33,5 @@ __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "ge
            "projected_gnfw", "gasprofiles",
            "virial_dispersion", "mu_rule", "legendre_weights", "rsd",
            "char_exponent", "cumulants", "pdf_from_exponent", "lambda_grid", "ring_rule", "onepoint",
+           "hod_sets", "stencil", "central_differences", "hod_ensemble",
            "fft", "tinker", "utils", "cosmology", "params"] + list(_fn_all)

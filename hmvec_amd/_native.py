@@ -215,6 +215,8 @@ SIGNATURES = {
                            _P, _P, _P, _P, _D, _D, _D, _P, _P],
     "hmg_onepoint_exponent": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _P, _P],
     "hmg_onepoint_moments": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
+    "hmg_hod_ensemble": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "hmg_hod_ensemble_power": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P],
     "hmg_comm_unique_id": [C.c_char * COMM_ID_BYTES],
     "hmg_comm_init": [_P, C.c_char * COMM_ID_BYTES, _I, _I],
     "hmg_comm_allgather": [_P, _P, _P, _Z],
@@ -239,7 +241,8 @@ def kernel_source_sha16():
     csrc = os.path.join(_HERE, "csrc")
     names = ["hmgrid.hip", "longgrid.hip", "longgrid.hpp", "rowdev.hpp", "sici.hpp", "ldsfft.hpp", "fastmath.hpp", "Makefile",
              "lensing.hip", "j0.hpp", "j1.hpp", "ksz.hip", "realspace.hip", "j01.hpp", "trispectrum.hip", "bispectrum.hip",
-             "response.hip", "gasproj.hip", "i0e.hpp", "rsd.hip", "gauss_moments.hpp", "onepoint.hip"]
+             "response.hip", "gasproj.hip", "i0e.hpp", "rsd.hip", "gauss_moments.hpp", "onepoint.hip",
+             "hodens.hip"]
     names += sorted(os.path.join("kernels", n) for n in os.listdir(os.path.join(csrc, "kernels")) if n.endswith(".hpp"))
     for name in names:          # (runtime.hip / comm.hip / hmctx.hpp hold no device code: not part of the kernel identity)
         with open(os.path.join(csrc, name), "rb") as f:

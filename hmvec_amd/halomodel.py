@@ -25,6 +25,7 @@ from . import cov as covmod
 from . import realspace, spectra, stages
 from . import rsd as rsdmod
 from . import onepoint
+from . import hod_ensemble as hodens
 from .cosmology import Cosmology, _is_shared_product, sigma2_kgrid, sigma2_weights
 from .params import battaglia_defaults, default_params
 from .quadrature import gradient_is_uniform, simpson_weights, trapz_weights
@@ -1962,6 +1963,139 @@ class HaloModel(Cosmology):
         get_y_char_exponent (without noise), kappa_p = sum zw wm n a y^p; (4,), or with per_z=True (nz, 4)."""
         req = self._y_request(truncate, fwhm, family, param_override, ntheta, mmin, mmax, zweights)
         return self._onepoint_launch(req, None, bool(per_z))
+
+    # ------------------------------------------------------------------ HOD parameter ensembles (DESIGN.md section 21)
+    # P_gg and P_gm of S parameter sets in one pass over the tensors (hmg_hod_ensemble, hmg_hod_ensemble_power).  The host
+    # side of the contract - the table of sets, the stencil, the checks - is hod_ensemble.py.  Nothing is registered in
+    # hods and the model's version does not change: cached spectra stay valid.
+    def _hodens_request(self, sets, mthresh, ngal, corr):
+        """(sets (S, 6), corr flag, log10 thresholds (S, nz) or None, n_gal targets (S, nz) or None): every refusal of the
+        HOD half of a request, on the host."""
+        sets = hodens.as_sets(sets)
+        if (mthresh is None) == (ngal is None):
+            raise ValueError("give exactly one of mthresh and ngal")
+        S, nz = sets.shape[0], self._nz
+        flag = hodens.check_corr(corr)
+        if ngal is not None:
+            return sets, flag, None, hodens.per_set(ngal, S, nz, "ngal")
+        return sets, flag, np.log10(hodens.per_set(mthresh, S, nz, "mthresh")), None
+
+    def _hodens_occ(self, ctx, d_par, flag, l10, S, occ=None, coef=None):
+        """One hmg_hod_ensemble launch at the thresholds l10 (S, nz): (d_lthr, d_ngal, d_bg)."""
+        nz, nm = self._nz, self._nm
+        d_thr, d_ngal, d_bg = ctx.upload(np.ascontiguousarray(l10)), ctx.empty((S, nz)), ctx.empty((S, nz))
+        ctx.call("hmg_hod_ensemble", S, nz, nm, flag, d_par.ptr, d_thr.ptr, self._d_zs().ptr, self._d_ms().ptr,
+                 self._d_nzm.ptr, self._d_bh.ptr, self._d_wm().ptr, d_ngal.ptr, d_bg.ptr, nat.ptr(occ), nat.ptr(coef))
+        return d_thr, d_ngal, d_bg
+
+    def _hodens_bisect(self, ctx, d_par, target):
+        """log10 mthresh (S, nz) by one batched bisection, and its number of launches.  The rules are those of
+        utils.vectorized_bisection_search with the stop test per set: a set stops updating once all of its redshifts meet
+        hod_bisection_search_rtol - the thresholds add_hod(ngal=target[s]) finds for that set alone - while the others go
+        on; the number of launches is the largest iteration count."""
+        p = self.p
+        S = target.shape[0]
+        lo = np.zeros_like(target) + p["hod_bisection_search_min_log10mthresh"]
+        hi = np.zeros_like(target) + p["hod_bisection_search_max_log10mthresh"]
+        out = np.zeros_like(target)
+        active = np.ones(S, dtype=bool)
+        n_iter, warned = 0, False
+        while active.any():
+            mid = np.where(active[:, None], (lo + hi) / 2.0, out)
+            got = self._hodens_occ(ctx, d_par, 0, mid, S)[1].numpy()
+            miss = (got - target) / target
+            out[active] = mid[active]
+            hodens.bisection_step(lo, hi, mid, miss, active)
+            active &= np.any(np.abs(miss) > p["hod_bisection_search_rtol"], axis=1)
+            n_iter += 1
+            if n_iter > p["hod_bisection_search_warn_iter"] and not warned:
+                print("WARNING: Bisection search has done more than ", p["hod_bisection_search_warn_iter"],
+                      " loops. Still searching...")
+                warned = True
+        return out, n_iter
+
+    def _hodens_thresholds(self, ctx, d_par, l10, target):
+        """The log10 thresholds of a request as add_hod forms them, and the bisection's launches."""
+        if l10 is not None:
+            return l10, 0
+        lm, n_iter = self._hodens_bisect(ctx, d_par, target)
+        return np.log10(10 ** (lm * self.p["hod_A_log10mthresh"])), n_iter
+
+    def _hodens_tensor(self, name, what):
+        if name in self.pk_profiles and name not in self.uk_profiles:
+            raise ValueError(f"{what} {name!r} is a pressure profile: an HOD ensemble takes matter profiles")
+        if name not in self.uk_profiles:
+            raise ValueError(f"{what} {name!r} is not a matter profile of this model")
+        return name
+
+    def hod_ensemble_device(self, sets, mthresh=None, ngal=None, corr="max", satellite_profile_name="nfw", matter_name=None,
+                            kindex=None, damping=True, parts=False):
+        """P_gg and P_gm of S HOD parameter sets at once, on the device: a hod_ensemble.HodEnsembleResult with power
+        (4, S, nz, n) = (P1h_gg, P2h_gg, P1h_gm, P2h_gm), ngal, bg and log10mthresh (S, nz) and parts (3, S, nz, n) =
+        (G, X, I) or None.  sets: (S, 6) as hod_ensemble.hod_sets makes them; exactly one of mthresh and ngal, each (nz,),
+        shared by the sets, or (S, nz) - ngal runs one batched bisection whose thresholds are those add_hod(ngal=...)
+        finds for each set alone.  Plane by plane the result is get_power_1halo / get_power_2halo of (g_s, g_s) and
+        (g_s, matter_name) for g_s = add_hod(mthresh=..., corr=corr, satellite_profile_name=..., param_override=set s)
+        without a central profile; matter_name defaults to the satellite profile.  kindex: the nodes of the k grid
+        (default: all); damping as in get_power_1halo.  Nothing is registered in hods; cached spectra stay valid."""
+        sets, flag, l10, target = self._hodens_request(sets, mthresh, ngal, corr)
+        sat = self._hodens_tensor(satellite_profile_name, "satellite_profile_name")
+        mat = sat if matter_name is None else self._hodens_tensor(matter_name, "matter_name")
+        nz, nm, nk = self._nz, self._nm, self._nk
+        kindex = hodens.check_kindex(kindex, nk)
+        S, n = sets.shape[0], nk if kindex is None else kindex.size
+        nodes = self.ks if kindex is None else self.ks[kindex]
+        damp = bispec.damping(nodes, self.p["kstar_damping"]) if damping else np.ones(n)
+        ctx = self._main(needs_aux=True)
+        shape = (nz, nm, nk)
+        # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
+        d_us = self.uk_profiles.dev(sat, fill=True)
+        d_um = d_us if mat == sat else self.uk_profiles.dev(mat, fill=True)
+        for nm_, d_ in ((sat, d_us), (mat, d_um)):
+            if d_.shape != shape:
+                raise ValueError(f"profile {nm_!r} has shape {d_.shape}, the model's grid is {shape}")
+        d_par = ctx.upload(sets)
+        l10, n_iter = self._hodens_thresholds(ctx, d_par, l10, target)
+        coef = ctx.empty((hodens.coef_block_size(S, nz, nm),))
+        d_thr, d_ngal, d_bg = self._hodens_occ(ctx, d_par, flag, l10, S, coef=coef)
+        d_k = None if kindex is None else ctx.upload_int32(kindex)
+        d_damp = ctx.upload(np.ascontiguousarray(damp, dtype=np.float64))
+        out = ctx.empty((4, S, nz, n))
+        P = ctx.empty((3, S, nz, n)) if parts else None
+        ctx.call("hmg_hod_ensemble_power", S, nz, nm, nk, n, d_us.ptr, d_um.ptr, coef.ptr, d_ngal.ptr, d_bg.ptr,
+                 *self._grid_ptrs(), nat.ptr(d_k), d_damp.ptr, out.ptr, nat.ptr(P))
+        self._sync_point()
+        return hodens.HodEnsembleResult(out, d_ngal, d_bg, d_thr, P, n_iter)
+
+    def get_power_hod_ensemble(self, sets, mthresh=None, ngal=None, corr="max", satellite_profile_name="nfw",
+                               matter_name=None, kindex=None, damping=True, parts=False):
+        """hod_ensemble_device on the host: a dict of gg_1h, gg_2h, gg, gm_1h, gm_2h, gm, each (S, nz, n), and ngal, bg,
+        log10mthresh (S, nz); with parts=True also G, X, I (S, nz, n)."""
+        r = self.hod_ensemble_device(sets, mthresh=mthresh, ngal=ngal, corr=corr,
+                                     satellite_profile_name=satellite_profile_name, matter_name=matter_name, kindex=kindex,
+                                     damping=damping, parts=parts)
+        power = r.power.numpy()
+        out = dict(zip(hodens.POWER_KEYS, power))
+        out["gg"], out["gm"] = power[0] + power[1], power[2] + power[3]
+        out["ngal"], out["bg"], out["log10mthresh"] = r.ngal.numpy(), r.bg.numpy(), r.log10mthresh.numpy()
+        if parts:
+            out.update(zip(("G", "X", "I"), r.parts.numpy()))
+        return out
+
+    def hod_ensemble_occupations(self, sets, mthresh=None, ngal=None, corr="max"):
+        """{Nc, Ns, NsNsm1, NcNs (S, nz, nm), ngal, bg (S, nz)}: the occupation numbers and sums of every set, each the
+        bits add_hod gives for that set alone."""
+        sets, flag, l10, target = self._hodens_request(sets, mthresh, ngal, corr)
+        S = sets.shape[0]
+        ctx = self._main(needs_aux=True)
+        d_par = ctx.upload(sets)
+        l10, _ = self._hodens_thresholds(ctx, d_par, l10, target)
+        occ = ctx.empty((4, S, self._nz, self._nm))
+        _, d_ngal, d_bg = self._hodens_occ(ctx, d_par, flag, l10, S, occ=occ)
+        self._sync_point()
+        out = dict(zip(("Nc", "Ns", "NsNsm1", "NcNs"), occ.numpy()))
+        out["ngal"], out["bg"] = d_ngal.numpy(), d_bg.numpy()
+        return out
 
 
 _X_H = 0.76      # hydrogen mass fraction of the Battaglia profiles (hmvec/hmvec.py:922)

@@ -835,6 +835,40 @@ int hmg_onepoint_moments(hmg_ctx* ctx, int nz, int nm, int nt, const double* d_s
                          const double* d_amp, const double* d_nzm, const double* d_wm, const double* d_zw, int m_lo,
                          int m_hi, double* d_rows /*[nz][4]*/, double* d_total /*[4] or NULL*/);
 
+/* ---- HOD parameter ensembles: P_gg and P_gm of S parameter sets at once -----------------------
+ * Set s is d_par[s] = (sig_log_mstellar, alphasat, Bsat, betasat, Bcut, betacut); corr (0 = max, 1 = min) holds for the
+ * whole call; d_lthr (S, nz) are the thresholds log10 M*_thr.  Centrals sit at the halo centre (u_c = 1).
+ * hmg_hod_ensemble: the occupations and sums of hmg_hod for every set.  log10 M*(z, m), the SHMR inversion, is evaluated
+ *   once per (z, m) and shared by the sets; a point runs hmg_hod's operations in hmg_hod's order and the sums keep its tile
+ *   order per set, so every number has the bits hmg_hod gives for that set alone.  d_ngal, d_bg (S, nz).  d_occ
+ *   (4, S, nz, nm) = (Nc, Ns, NsNsm1, NcNs), or NULL.  d_coef, or NULL, is the block the second call reads, of
+ *   4 nz nm Spad + S nz doubles with Spad = S rounded up to a multiple of 8:
+ *     coef[nz][nm][Spad][4] = (Nc, Ns, 2 NcNs, NsNsm1), zeros in the sets S .. Spad-1;  then
+ *     craw[S][nz] = sum_m ((wm nzm) bh) (Nc + Ns), in the tile order of the n_gal sum.
+ *   With both NULL nothing of size S nz nm is written (the mode of a bisection on n_gal).  Launch-only.
+ * hmg_hod_ensemble_power: d_out (4, S, nz, n) = (P1h_gg, P2h_gg, P1h_gm, P2h_gm) at n columns, the nodes d_kindex (n) of the
+ *   k grid (any order, repeats allowed) or, with d_kindex NULL, the whole grid (n = nk).  d_us is the satellite tensor,
+ *   d_um the matter tensor of the cross spectrum (the same pointer: the tensor is loaded once).  With w = wm nzm:
+ *     G = sum_m (2 NcNs) (w u_s) + NsNsm1 ((w u_s) u_s),   X = sum_m (Ns u_s + Nc) ((w m/rho_m0) u_m),
+ *     I = sum_m (Ns u_s + Nc) (w bh),   I_m = sum_m ((w bh) m/rho_m0) u_m,   one FMA chain each, m ascending;  then
+ *     G / ngal^2, X / ngal, I / ngal, C = craw / ngal, J_g = (I + bg) - C, J_m = (I_m + 1) - C_m,
+ *     P1h_gg = damp G, P2h_gg = (Pzk J_g) J_g, P1h_gm = damp X, P2h_gm = (Pzk J_g) J_m
+ *   - every 1/ngal on the finished sums.  d_damp (n) is the factor of the 1-halo terms (the caller's damping, or ones).
+ *   d_parts (3, S, nz, n) = (G, X, I) after their divisions, or NULL.  A given d_kindex is checked on the device before any
+ *   tensor is read through it and the host waits for that answer: the call then synchronises the current stream once and
+ *   cannot be part of a captured step.  fp64 on the vector units, no atomics: bit-identical on repeat, an element depends
+ *   only on its own (set, z, node), not on which other sets, nodes or redshifts the call holds.                          */
+int hmg_hod_ensemble(hmg_ctx* ctx, int S, int nz, int nm, int corr, const double* d_par /*[S][6]*/,
+                     const double* d_lthr /*[S][nz]*/, const double* d_zs, const double* d_ms, const double* d_nzm,
+                     const double* d_bh, const double* d_wm, double* d_ngal /*[S][nz]*/, double* d_bg /*[S][nz]*/,
+                     double* d_occ /*[4][S][nz][nm] or NULL*/, double* d_coef /*the coefficient block or NULL*/);
+int hmg_hod_ensemble_power(hmg_ctx* ctx, int S, int nz, int nm, int nk, int n, const double* d_us, const double* d_um,
+                           const double* d_coef, const double* d_ngal, const double* d_bg, const double* d_nzm,
+                           const double* d_bh, const double* d_ms, const double* d_wm, const double* d_ks,
+                           const double* d_Pzk, double rho_m0, const int* d_kindex /*[n] or NULL*/,
+                           const double* d_damp /*[n]*/, double* d_out /*[4][S][nz][n]*/,
+                           double* d_parts /*[3][S][nz][n] or NULL*/);
+
 /* ---- z-slab gather over RCCL/xGMI-------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */

@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -64,6 +64,14 @@ KERNELS = [   # (label, regex on the mangled name)
     ("onepoint_exponent_kernel  (exponent of the one-point characteristic function, one lambda per lane, onepoint.hip)", r"24onepoint_exponent_kernelE"),
     ("onepoint_moments_kernel  (cumulants of the one-point PDF, onepoint.hip)", r"23onepoint_moments_kernelE"),
     ("onepoint_finish_kernel  (the sum over slices and over z, onepoint.hip)", r"22onepoint_finish_kernelE"),
+    ("hodens_power_kernel<8,true>  (HOD ensemble contraction, 8 sets per thread, one tensor for both legs, hodens.hip)", r"19hodens_power_kernelILi8ELb1EE"),
+    ("hodens_power_kernel<8,false>  (the same with a matter tensor of its own, hodens.hip)", r"19hodens_power_kernelILi8ELb0EE"),
+    ("hodens_power_kernel<2,true>  (fewer than 256 columns: 2 sets per thread, hodens.hip)", r"19hodens_power_kernelILi2ELb1EE"),
+    ("hodens_power_kernel<2,false>  (the same with a matter tensor of its own, hodens.hip)", r"19hodens_power_kernelILi2ELb0EE"),
+    ("hodens_occ_kernel  (occupations, n_gal, b_g and the coefficient block of an HOD ensemble, hodens.hip)", r"17hodens_occ_kernelE"),
+    ("hodens_lmstar_kernel  (the SHMR inversion, once per (z, m), hodens.hip)", r"20hodens_lmstar_kernelE"),
+    ("hodens_side_kernel  (the side data of the mass bins, hodens.hip)", r"18hodens_side_kernelE"),
+    ("hodens_check_kernel  (the check of a node list, hodens.hip)", r"19hodens_check_kernelE"),
     ("leg_prepass_kernel  (leg prepass of the bispectrum and the response: I, C, b, J, P, D, k at the samples, sampled.hip)", r"18leg_prepass_kernelE"),
     ("leg_sums_kernel  (C, C0, b of a leg, for the response and the redshift-space spectra, sampled.hip)", r"15leg_sums_kernelE"),
     ("zsum_kernel  (the z sum of the trispectrum and the bispectrum, sampled.hip)", r"11zsum_kernelE"),
@@ -74,7 +82,7 @@ KERNELS = [   # (label, regex on the mangled name)
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "sampled")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
