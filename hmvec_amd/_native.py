@@ -200,6 +200,8 @@ SIGNATURES = {
     "hmg_ksz_limber_cl": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _D, _D, _P],
     "hmg_xi_transform": [_P, _I, _I, _I, _P, _P, _P, _P],
     "hmg_hankel_transform": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "hmg_angular_transform": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "hmg_angular_zsum": [_P, _I, _I, _I, _I, _P, _P, _P],
     "hmg_trispectrum_1h": [_P, _I, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), C.POINTER(Tracer), C.POINTER(Tracer),
                            _P, _P, _P, _D, _P, _P, _P, _P, _P, _P],
     "hmg_bispectrum": [_P, _I, _I, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), C.POINTER(Tracer),
@@ -242,7 +244,7 @@ def kernel_source_sha16():
     names = ["hmgrid.hip", "longgrid.hip", "longgrid.hpp", "rowdev.hpp", "sici.hpp", "ldsfft.hpp", "fastmath.hpp", "Makefile",
              "lensing.hip", "j0.hpp", "j1.hpp", "ksz.hip", "realspace.hip", "j01.hpp", "trispectrum.hip", "bispectrum.hip",
              "response.hip", "gasproj.hip", "i0e.hpp", "rsd.hip", "gauss_moments.hpp", "onepoint.hip",
-             "hodens.hip"]
+             "hodens.hip", "angular.hip"]
     names += sorted(os.path.join("kernels", n) for n in os.listdir(os.path.join(csrc, "kernels")) if n.endswith(".hpp"))
     for name in names:          # (runtime.hip / comm.hip / hmctx.hpp hold no device code: not part of the kernel identity)
         with open(os.path.join(csrc, name), "rb") as f:

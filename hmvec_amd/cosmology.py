@@ -463,6 +463,18 @@ class Cosmology(object):
             integral = _trapz(integrand, zs, axis=-1)
         return 1.5 * self.omm0 * H0 ** 2.0 * (1.0 + ezs) * chis / H * integral
 
+    def angular_weights(self, zs, W1, W2):
+        """The z weights of an angular correlation function (angular.angular_from_power):
+        trapz_weights(zs) h_of_z(zs) W1 W2 - the measure of limber_integral without its 1/chi^2, which the change of
+        variable k = l/chi cancels.  W1, W2: the two windows on zs, each a scalar, (nz,) or (nw, nz) (one row per
+        tomographic bin pair).  Returns (nz,) or (nw, nz)."""
+        zs = np.asarray(zs, dtype=np.float64).reshape(-1)
+        W1, W2 = np.asarray(W1, dtype=np.float64), np.asarray(W2, dtype=np.float64)
+        for W in (W1, W2):
+            if W.ndim > 2 or (W.ndim and W.shape[-1] != zs.size):
+                raise ValueError(f"a window must be a scalar, ({zs.size},) or (nw, {zs.size}), got {W.shape}")
+        return trapz_weights(zs) * self.h_of_z(zs) * W1 * W2
+
     def C_kk(self, ells, zs, ks, Pmm, lzs1=None, ldndz1=None, lzs2=None, ldndz2=None, lwindow1=None,
              lwindow2=None):
         """hmvec/cosmology.py:563-568."""

@@ -123,9 +123,7 @@ constexpr int HK_SERIES_N = 10;
 
 // g(x) = x^2 J2(x) and H2(x) given J0(x) and J1(x); the closed forms without a division: x^2 J2 = x (2 J1 - x J0)
 template <bool W0, bool W2>
-__device__ __forceinline__ void hankel_node(double x, double& g, double& h2) {
-    double j0, j1;
-    bessel_j01(x, j0, j1);
+__device__ __forceinline__ void hankel_node_j(double x, double j0, double j1, double& g, double& h2) {
     const double y = 0.25 * x * x;
     const bool series = x < HK_SERIES_X;
     const double gc = x * fma(-x, j0, 2.0 * j1);
@@ -137,6 +135,14 @@ __device__ __forceinline__ void hankel_node(double x, double& g, double& h2) {
     }
     g = series ? 2.0 * y * y * sg : gc;
     h2 = series ? y * y * y * (1.0 / 3.0) * sh : fma(x, fma(-2.0, j1, x), -gc);
+}
+
+// the same at a node whose J0 and J1 the caller does not need (the angular kernel of kernels/angular.hpp does)
+template <bool W0, bool W2>
+__device__ __forceinline__ void hankel_node(double x, double& g, double& h2) {
+    double j0, j1;
+    bessel_j01(x, j0, j1);
+    hankel_node_j<W0, W2>(x, j0, j1, g, h2);
 }
 
 // H1(x) given J0(x) and J1(x): the end terms of W_2

@@ -22,11 +22,11 @@ import scipy.constants as constants
 from . import _native as nat
 from . import bispectrum as bispec
 from . import cov as covmod
-from . import realspace, spectra, stages
+from . import angular, realspace, spectra, stages
 from . import rsd as rsdmod
 from . import onepoint
 from . import hod_ensemble as hodens
-from .cosmology import Cosmology, _is_shared_product, sigma2_kgrid, sigma2_weights
+from .cosmology import Cosmology, _is_shared_product, _trapz, sigma2_kgrid, sigma2_weights
 from .params import battaglia_defaults, default_params
 from .quadrature import gradient_is_uniform, simpson_weights, trapz_weights
 from .functions import FN_BG_INTEGRAND, FN_ST_FSIGMA, FN_TINKER_FSIGMA, fn2d, ngal_from_mthresh, trapz_lastaxis
@@ -1091,48 +1091,57 @@ class HaloModel(Cosmology):
     # integrals to the transform (realspace.py); only the (nz, nr) results cross to the host.
     _XI_TERMS = ("total", "1h", "2h")
 
-    def _xi_request(self, rs, term):
-        """The checked radii of a transform request (everything that can be refused is, before any launch)."""
+    def _xi_request(self, rs, term, what="rs"):
+        """The checked radii (or angles: `what`) of a transform request (everything that can be refused is, before any
+        launch)."""
         if term not in self._XI_TERMS:
             raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
         realspace.check_ks(self.ks)
-        return realspace.check_rs(rs)
+        return realspace.check_rs(rs, what)
 
     def _xi_rows(self, d1, d2, term):
         """The device rows a term transforms; "total" is the device sum get_power brings to the host."""
         return d1 if term == "1h" else d2 if term == "2h" else self._sum_device(d1, d2)
 
-    def _transform_rows(self, rows, nrows, rs, orders):
+    def _transform_rows(self, rows, nrows, rs, orders, zsum=None):
         """The transforms of nrows device rows at the radii rs as a tuple of (nrows, nr) host arrays: (xi,) for
-        orders=None, else (W_n for n in orders), one launch either way."""
+        orders=None, else (W_n for n in orders), one launch either way.  With zsum = (chis, zw) rs are angles, the row
+        at z is transformed at chis[z] rs and the rows of a block are summed with the (nw, nz) weights zw (section
+        22): a tuple of (nrows / nz, nw, nr) arrays from one transform launch and one contraction."""
         if orders is None:
             return (realspace.transform_rows(self._ctx(), self._d_ks(), rows, nrows, self._nk, rs),)
+        if zsum is not None:
+            return angular.angular_rows(self._ctx(), self._d_ks(), rows, nrows // self._nz, self._nz, self._nk, rs,
+                                        *zsum, orders)
         return realspace.hankel_rows(self._ctx(), self._d_ks(), rows, nrows, self._nk, rs, orders)
 
-    def _realspace_pair(self, rs, name, name2, term, orders):
-        """What get_xi and the projected statistics of one pair share: the request's checks, the tSZ notice, the
-        pair's cached device spectra and one transform launch.  A tuple of (nz, nr) arrays (see _transform_rows)."""
-        rs = self._xi_request(rs, term)
+    def _realspace_pair(self, rs, name, name2, term, orders, zsum=None):
+        """What get_xi, the projected and the angular statistics of one pair share: the request's checks, the tSZ
+        notice, the pair's cached device spectra and one transform launch.  A tuple of (nz, nr) arrays, with zsum of
+        (1, nw, nr) arrays (see _transform_rows)."""
+        rs = self._xi_request(rs, term, "rs" if zsum is None else "thetas")
         ra, rb = self._resolve(name, name if name2 is None else name2)
         if term != "1h":          # (get_power and get_power_2halo print it, get_power_1halo does not)
             self._tsz_notice(ra, rb)
         if rs.size == 0:
-            return tuple(np.empty((self._nz, 0)) for _ in (orders or (None,)))
+            shape = (self._nz, 0) if zsum is None else (1, zsum[1].shape[0], 0)
+            return tuple(np.empty(shape) for _ in (orders or (None,)))
         ent = self._power_cached(ra, rb)
-        return self._transform_rows(self._xi_rows(ent.p1h, ent.p2h, term), self._nz, rs, orders)
+        return self._transform_rows(self._xi_rows(ent.p1h, ent.p2h, term), self._nz, rs, orders, zsum)
 
-    def _realspace_all(self, pairs, rs, term, orders):
+    def _realspace_all(self, pairs, rs, term, orders, zsum=None):
         """The same for several pairs: their spectra from one pass over the profile tensors (get_power_all's) into one
         block and all of them through ONE transform launch of len(pairs) * nz rows.  (pairs, tuple of (n, nz, nr)
-        arrays); every [i] is bit for bit what _realspace_pair gives for pairs[i]."""
-        rs = self._xi_request(rs, term)
+        arrays, with zsum of (n, nw, nr) arrays); every [i] is bit for bit what _realspace_pair gives for pairs[i]."""
+        rs = self._xi_request(rs, term, "rs" if zsum is None else "thetas")
         pairs = [tuple(p) for p in pairs]
         rpairs = self._resolve_pairs(pairs)
         if term != "1h":
             self._tsz_notice(*dict.fromkeys(r for rp in rpairs for r in rp))
         n, nz, nk = len(pairs), self._nz, self._nk
         if rs.size == 0 or n == 0:
-            return pairs, tuple(np.empty((n, nz, rs.size)) for _ in (orders or (None,)))
+            shape = (n, nz, rs.size) if zsum is None else (n, zsum[1].shape[0], rs.size)
+            return pairs, tuple(np.empty(shape) for _ in (orders or (None,)))
         ctx = self._ctx()
         blk = ctx.empty((2 * n, nz, nk))
         o1 = [blk.view(i * nz * nk, (nz, nk)) for i in range(n)]
@@ -1147,7 +1156,8 @@ class HaloModel(Cosmology):
                 ctx.call("hmg_memcpy_d2d", d1.ptr, ent.p1h.ptr, d1.nbytes)
                 ctx.call("hmg_memcpy_d2d", d2.ptr, ent.p2h.ptr, d2.nbytes)
         rows = self._xi_rows(blk.view(0, (n * nz, nk)), blk.view(n * nz * nk, (n * nz, nk)), term)
-        return pairs, tuple(o.reshape(n, nz, rs.size) for o in self._transform_rows(rows, n * nz, rs, orders))
+        outs = self._transform_rows(rows, n * nz, rs, orders, zsum)
+        return pairs, tuple(o.reshape(n, -1, rs.size) for o in outs)
 
     def get_xi(self, rs, name="nfw", name2=None, term="total"):
         """Correlation function xi(z, r), shape (nz, nr), of the spectrum of (name, name2) - of P_1h + P_2h
@@ -1201,6 +1211,115 @@ class HaloModel(Cosmology):
         pairs, (w0, w2) = self._realspace_all(pairs, Rs, term, (0, 2))
         rho = self._rho_m0()
         return {p: (rho * w0[i], rho * w2[i]) for i, p in enumerate(pairs)}
+
+    # ------------------------------------------------------------------ angular correlation functions
+    # w(theta), gamma_t(theta), xi+-(theta): the rows at the model's redshifts are transformed at chi(z) theta and summed
+    # over z with the windows' weights on the device (angular.py); only the (nw, ntheta) results cross to the host.
+    def _angular_request(self, zweights, order, term):
+        """(zsum, orders, stacked) of an angular request: the distances of self.zs, the checked (nw, nz) weights
+        (None: the z measure alone, both windows 1) and orders, and whether the weights came with the nw axis."""
+        if term not in self._XI_TERMS:
+            raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
+        orders = angular.check_order(order)
+        nz = np.size(self.zs)
+        if zweights is None:
+            zweights = self.angular_weights(self.zs, 1.0, 1.0)
+        zw, stacked = angular.check_zweights(zweights, nz)
+        chis = angular.check_chis(np.reshape(self.comoving_radial_distance(self.zs), -1), nz)
+        return (chis, zw), orders, stacked
+
+    def get_angular(self, thetas, name, name2=None, zweights=None, order=0, term="total"):
+        """Angular correlation function zeta_order(theta) = sum_z zweights[z] W_order^(z)(chi(z) theta) of the spectrum
+        of (name, name2) - term as for get_xi - on the model's redshifts self.zs, chi = comoving_radial_distance(zs)
+        (every z must be positive): bit for bit angular.angular_from_power(ks, get_power(name, name2), thetas, chi,
+        zweights, order).  thetas in radians.  zweights: (nz,) or (nw, nz), the z measure times the two windows
+        (angular_weights(zs, W1, W2)); None is the measure alone.  order: 0, 2, 4 or a strictly increasing tuple of
+        them.  Returns (ntheta,), or (nw, ntheta) for two-dimensional weights; a tuple of them for a tuple of
+        orders."""
+        zsum, orders, stacked = self._angular_request(zweights, order, term)
+        outs = self._realspace_pair(thetas, name, name2, term, orders, zsum)
+        outs = tuple(o[0] if stacked else o[0, 0] for o in outs)
+        return outs if isinstance(order, (tuple, list)) else outs[0]
+
+    def _dndz_window(self, dndz, what):
+        """dndz / int dndz dz on self.zs (C_gg's convention); None is a uniform distribution over the range of zs."""
+        zs = np.reshape(self.zs, -1)
+        if zs.size < 2:
+            raise ValueError(f"{what} needs at least two redshifts in the model")
+        dndz = np.ones(zs.size) if dndz is None else np.asarray(dndz, dtype=np.float64)
+        if dndz.shape != zs.shape or not np.all(np.isfinite(dndz)):
+            raise ValueError(f"{what} must be a finite vector of {zs.size} values on the model's redshifts")
+        norm = _trapz(dndz, zs)
+        if not norm > 0:
+            raise ValueError(f"{what} must have a positive integral over the model's redshifts")
+        return dndz / norm
+
+    def _source_window(self, zsource, sdndz, what):
+        """lensing_window on self.zs of a source plane (zsource a scalar) or of sources sdndz on the grid zsource."""
+        if zsource is None:
+            raise ValueError(f"{what} is required: a source redshift, or the grid of a source distribution")
+        zsource = np.asarray(zsource, dtype=np.float64).reshape(-1)
+        if (zsource.size == 1) != (sdndz is None) or (sdndz is not None and np.shape(sdndz) != zsource.shape):
+            raise ValueError(f"{what}: one source redshift without a distribution, or a grid with its distribution")
+        return self.lensing_window(np.reshape(self.zs, -1), zsource, sdndz)
+
+    def get_w_theta(self, thetas, name, name2=None, dndz=None, dndz2=None, term="total"):
+        """Angular clustering w(theta), shape (ntheta,): order 0 with the windows dndz / int dndz dz of the two samples
+        on self.zs (C_gg's convention; dndz None: uniform over the range of zs, dndz2 None: the first sample's) -
+        bit for bit get_angular(thetas, name, name2, angular_weights(zs, W1, W2), 0, term)."""
+        if term not in self._XI_TERMS:
+            raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
+        W1 = self._dndz_window(dndz, "dndz")
+        W2 = W1 if dndz2 is None else self._dndz_window(dndz2, "dndz2")
+        return self.get_angular(thetas, name, name2, self.angular_weights(self.zs, W1, W2), 0, term)
+
+    def get_gamma_t(self, thetas, name, name2="nfw", dndz=None, zsource=None, sdndz=None, term="total"):
+        """Tangential shear gamma_t(theta), shape (ntheta,), of the lenses `name` (window dndz / int dndz dz as for
+        get_w_theta) about sources at zsource (a single redshift, or a grid with the distribution sdndz: the arguments
+        of lensing_window): order 2 of the lens-matter spectrum - bit for bit
+        get_angular(thetas, name, name2, angular_weights(zs, W_lens, lensing_window(zs, zsource, sdndz)), 2, term)."""
+        if term not in self._XI_TERMS:
+            raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
+        W1 = self._dndz_window(dndz, "dndz")
+        W2 = self._source_window(zsource, sdndz, "zsource")
+        return self.get_angular(thetas, name, name2, self.angular_weights(self.zs, W1, W2), 2, term)
+
+    def get_xi_pm(self, thetas, name="nfw", name2=None, zsource=None, sdndz=None, zsource2=None, sdndz2=None,
+                  term="total"):
+        """Shear correlation functions (xi+(theta), xi-(theta)), each (ntheta,), of sources at zsource (and zsource2,
+        default the same; arguments as for get_gamma_t): orders 0 and 4 of the matter spectrum from ONE launch - bit
+        for bit get_angular(thetas, name, name2, angular_weights(zs, W_kappa1, W_kappa2), (0, 4), term)."""
+        if term not in self._XI_TERMS:
+            raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
+        W1 = self._source_window(zsource, sdndz, "zsource")
+        W2 = W1 if zsource2 is None else self._source_window(zsource2, sdndz2, "zsource2")
+        return self.get_angular(thetas, name, name2, self.angular_weights(self.zs, W1, W2), (0, 4), term)
+
+    def get_angular_all(self, pairs, thetas, zweights, order=0, term="total"):
+        """{(name, name2): zeta_order(theta)} for several pairs: their spectra from one pass over the profile tensors
+        (get_power_all's), ONE transform launch of len(pairs) * nz rows and one contraction over z.  zweights: (nz,)
+        or (nw, nz) shared by all pairs, or a dict {pair: weights}.  Each entry is bit for bit get_angular of that
+        pair with its weights."""
+        pairs = [tuple(p) for p in pairs]
+        if isinstance(zweights, dict):
+            missing = [p for p in pairs if p not in zweights]
+            if missing:
+                raise ValueError(f"zweights has no entry for {missing}")
+            per = [angular.check_zweights(zweights[p], np.size(self.zs)) for p in pairs]
+        else:
+            per = [angular.check_zweights(zweights, np.size(self.zs))] * len(pairs)
+        # every pair's rows of weights go stacked into the one contraction and the pair keeps its own: an output's
+        # chain reads its row of weights alone, so its bits are those of the pair's own call
+        shared = not isinstance(zweights, dict)
+        stack = None if not per else per[0][0] if shared else np.concatenate([zw for zw, _ in per])
+        zsum, orders, _ = self._angular_request(stack, order, term)
+        pairs, outs = self._realspace_all(pairs, thetas, term, orders, zsum)
+        res, lo = {}, 0
+        for i, (p, (zw, stacked)) in enumerate(zip(pairs, per)):
+            ent = tuple(o[i, lo:lo + zw.shape[0]] if stacked else o[i, lo] for o in outs)
+            res[p] = ent if isinstance(order, (tuple, list)) else ent[0]
+            lo += 0 if shared else zw.shape[0]
+        return res
 
     # ------------------------------------------------------------------ 1-halo trispectrum (DESIGN.md section 15)
     # T[z,i,j] = sum_m wm nzm s_ab[z,m,i] s_cd[z,m,j]: the mass integral of get_power_1halo with one more free index,

@@ -34,13 +34,14 @@ def check_ks(ks):
     return ks
 
 
-def check_rs(rs):
-    """The radii of a transform as a float64 vector of finite, positive values (may be empty)."""
+def check_rs(rs, what="rs"):
+    """The radii (`what`: their name in a message) of a transform as a float64 vector of finite, positive values (may
+    be empty)."""
     rs = np.atleast_1d(np.asarray(rs, dtype=np.float64))
     if rs.ndim != 1:
-        raise ValueError("rs must be a scalar or a vector of radii")
+        raise ValueError(f"{what} must be a scalar or a vector")
     if not np.all(np.isfinite(rs)) or np.any(rs <= 0):
-        raise ValueError("rs must be finite and positive")
+        raise ValueError(f"{what} must be finite and positive")
     return rs
 
 
@@ -71,8 +72,9 @@ def hankel_rows(ctx, d_ks, d_P, rows, nk, rs, orders):
     return tuple(outs[n].numpy() for n in orders)
 
 
-def _request(ks, P, rs):
-    """The checks xi_from_power and projected_from_power share, all before any launch: (ks, P, rs, lead, rows) with
+def _request(ks, P, rs, what="rs"):
+    """The checks xi_from_power, projected_from_power and angular_from_power (whose radii are angles: `what`) share,
+    all before any launch: (ks, P, rs, lead, rows) with
     ks and rs checked, P a DeviceArray or a finite float64 host array of nk values per row, lead its leading shape."""
     ks = check_ks(ks)
     nk = ks.size
@@ -85,7 +87,7 @@ def _request(ks, P, rs):
         raise ValueError(f"P must have shape ({nk},), (nz, {nk}) or (n, nz, {nk}), got {tuple(shape)}")
     if not isinstance(P, nat.DeviceArray) and not np.all(np.isfinite(P)):
         raise ValueError("P must be finite")
-    rs = check_rs(rs)
+    rs = check_rs(rs, what)
     lead = tuple(shape[:-1])
     return ks, P, rs, lead, int(np.prod(lead, dtype=np.int64))
 

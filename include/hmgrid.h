@@ -668,6 +668,22 @@ int hmg_xi_transform(hmg_ctx* ctx, int rows, int nk, int nr, const double* d_ks,
 int hmg_hankel_transform(hmg_ctx* ctx, int rows, int nk, int nr, const double* d_ks, const double* d_P,
                          const double* d_rs, double* d_w0, double* d_w2);
 
+/* ---- angular correlation functions of tabulated spectra: w(theta), gamma_t, xi+- ----------
+ * hmg_angular_transform: d_w0, d_w2 and d_w4 (n * nz, nt), wN[row, j] = W_N(R) of d_P[row, :] at the radius
+ *   R = fl(chis[row % nz] * thetas[j])    (one rounding),     W_N(R) = 1/(2 pi) int k P~(k) J_N(k R) dk,   N = 0, 2, 4,
+ * P~ as for hmg_hankel_transform, the integrals exact panel by panel.  d_P (n * nz, nk): n blocks of nz rows, row z of
+ * every block at the distance d_chis[z] (nz, positive); d_thetas (nt) positive, in radians.  Any output pointer may be
+ * NULL (that order is not computed), not all three.  W_0 and W_2 are bit for bit what hmg_hankel_transform gives at
+ * the radius R.  fp64, no atomics: bit-identical on repeat, a result depends on nk, ks, its row and its R alone, and
+ * an output does not depend on which others were asked for.
+ * hmg_angular_zsum: d_out (n, nw, nt), out[i, w, j] = sum_z zw[w, z] W[i * nz + z, j], d_zw (nw, nz), d_w (n * nz, nt):
+ * one fused multiply-add chain over z in index order from 0.0 per output (a single z of weight 1.0 returns W's bits);
+ * no atomics, no dependence on the launch shape.  d_out must not overlap d_w.                                       */
+int hmg_angular_transform(hmg_ctx* ctx, int n, int nz, int nk, int nt, const double* d_ks, const double* d_P,
+                          const double* d_chis, const double* d_thetas, double* d_w0, double* d_w2, double* d_w4);
+int hmg_angular_zsum(hmg_ctx* ctx, int n, int nz, int nt, int nw, const double* d_zw, const double* d_w,
+                     double* d_out);
+
 /* ---- 1-halo trispectrum of two spectra -----------------------------------------------------
  * hmg_trispectrum_1h: d_T (nz, n, n),
  *   T[z,i,j] = sum_m wm[m] nzm[z,m] s_ab[z,m,i] s_cd[z,m,j],

@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, angular.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -49,6 +49,14 @@ KERNELS = [   # (label, regex on the mangled name)
     ("hankel_transform_kernel<256,4,true,false>  (W_0: w_p, Sigma; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb1ELb0EE"),
     ("hankel_transform_kernel<256,4,false,true>  (W_2: Delta Sigma; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb0ELb1EE"),
     ("hankel_transform_kernel<256,4,true,true>  (W_0 and W_2 from one pass; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb1ELb1EE"),
+    ("angular_transform_kernel<256,4,true,false,false>  (W_0: w(theta), xi+; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb0ELb0EE"),
+    ("angular_transform_kernel<256,4,false,true,false>  (W_2: gamma_t; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb1ELb0EE"),
+    ("angular_transform_kernel<256,4,true,true,false>  (W_0 and W_2; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb1ELb0EE"),
+    ("angular_transform_kernel<256,4,false,false,true>  (W_4: xi-; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb0ELb1EE"),
+    ("angular_transform_kernel<256,4,true,false,true>  (W_0 and W_4: xi+ and xi-; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb0ELb1EE"),
+    ("angular_transform_kernel<256,4,false,true,true>  (W_2 and W_4; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb1ELb1EE"),
+    ("angular_transform_kernel<256,4,true,true,true>  (all three orders; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb1ELb1EE"),
+    ("angular_zsum_kernel  (the z sum of the angular transforms, angular.hip)", r"19angular_zsum_kernelE"),
     ("trispectrum_1h_kernel  (1-halo trispectrum, 64 x 64 tile, trispectrum.hip)", r"21trispectrum_1h_kernelE"),
     ("bispectrum_kernel  (bispectrum of three tracers, 1024 triangles per workgroup, bispectrum.hip)", r"17bispectrum_kernelE"),
     ("bispectrum_check_kernel  (its table and triangle check, bispectrum.hip)", r"23bispectrum_check_kernelE"),
@@ -82,7 +90,7 @@ KERNELS = [   # (label, regex on the mangled name)
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "sampled")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "angular", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16

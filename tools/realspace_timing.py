@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Device time of the correlation-function transform (hmg_xi_transform) and of the Hankel
-transforms (hmg_hankel_transform: W_0 alone, W_2 alone and both from one launch; section 14) on GPU 0, one launch of
+"""Device time of the correlation-function transform (hmg_xi_transform), of the Hankel
+transforms (hmg_hankel_transform: W_0 alone, W_2 alone and both from one launch; section 14) and of the angular
+transforms (hmg_angular_transform: W_0, W_2, W_4 alone, W_0 with W_4 - xi+ and xi- - and all three, with every distance
+1 so that the radii are the same; hmg_angular_zsum with ten rows of weights; section 22) on GPU 0, one launch of
   * 6 spectra x nz 32 rows of nk 4096 at 64 radii (the Config-3 grid), and
   * 6 spectra x nz 20 rows of nk 1001 at 64 radii (the README grid).
 Rows are a matter-like spectrum with per-row amplitudes, radii geomspace(0.1, 200, 64).  Inputs are uploaded once; the
@@ -62,6 +64,22 @@ def main():
             res[label]["panel_radius_pairs"] = rows * (nk - 1) * rs.size
             got = out.numpy()
             assert np.all(np.isfinite(got)) and np.all(got[:, 0] > 0) and np.all(np.isfinite(out2.numpy()))
+        w0 = out.numpy()                 # (W_0 of the last Hankel launch: the angular launch must give its bits)
+        n, nz, nw = 6, rows // 6, 10
+        d_chi, d_zw = ctx.upload(np.ones(nz)), ctx.upload(rng.uniform(-1.0, 1.0, (nw, nz)))
+        a0, a2, a4 = (ctx.empty((rows, rs.size)) for _ in range(3))
+        zs = ctx.empty((n, nw, rs.size))
+        ang = (n, nz, nk, rs.size, d_ks.ptr, d_P.ptr, d_chi.ptr, d_rs.ptr)
+        for label, outs in (("ang_w0", (a0.ptr, None, None)), ("ang_w2", (None, a2.ptr, None)),
+                            ("ang_w4", (None, None, a4.ptr)), ("ang_w0_w4", (a0.ptr, None, a4.ptr)),
+                            ("ang_w0_w2_w4", (a0.ptr, a2.ptr, a4.ptr))):
+            label = f"{label}_{shape}"
+            res[label] = timed(ctx, a.reps, a.warmup, a.batch, "hmg_angular_transform", *ang, *outs)
+            res[label]["panel_radius_pairs"] = rows * (nk - 1) * rs.size
+        assert np.array_equal(a0.numpy(), w0) and np.all(np.isfinite(a4.numpy()))
+        res[f"ang_zsum_nw{nw}_{shape}"] = timed(ctx, a.reps, a.warmup, a.batch, "hmg_angular_zsum", n, nz, rs.size, nw,
+                                                d_zw.ptr, a4.ptr, zs.ptr)
+        assert np.all(np.isfinite(zs.numpy()))
     res["kernel_source_sha16"] = nat.kernel_source_sha16()
     print(json.dumps(res))
     ctx.close()
