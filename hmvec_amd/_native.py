@@ -1,5 +1,11 @@
 """ctypes binding of libhmgrid.so (C ABI in include/hmgrid.h).
 
+Nothing of the ABI is written down here a second time: at import, _abi.py reads the header and this module publishes
+what it finds - SIGNATURES (name -> argtypes), PARAMS (name -> parameter names), DEFINES (HMG_<NAME> -> integer), the
+Structure classes (Tracer, HodPart, ...) and the constants under their short names (HOD_ALL, GNFW_SIGMA, ...).  A
+pointer named d_* is bound as a device address, one named h_* as typed host memory; a header the reader does not
+understand fails the import.  Context.call takes keywords by the header's parameter names (arguments()).
+
 There is NO CPU fallback: if the shared library is missing or a call fails, this
 module raises.  Build the library with ``python -c "import __graft_entry__ as g; g.build()"``
 or ``make -C hmvec_amd/csrc``.
@@ -10,10 +16,10 @@ import os
 
 import numpy as np
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HMG_LIB_PATH") or os.path.join(_HERE, "libhmgrid.so")   # override: tuning experiments only
-ABI_VERSION = 10
-COMM_ID_BYTES = 128
 
 c_double_p = C.c_void_p  # device or host pointers travel as plain addresses
 
@@ -22,214 +28,41 @@ class NativeError(RuntimeError):
     pass
 
 
-class HaloStageArgs(C.Structure):
-    """hmg_halo_stage_args (include/hmgrid.h): the halo-stage half of hmg_sigma2_massfn_halo."""
-    _fields_ = [("d_zs", C.c_void_p), ("d_delta", C.c_void_p), ("d_rho", C.c_void_p),
-                ("duffy_A", C.c_double), ("duffy_alpha", C.c_double), ("duffy_beta", C.c_double),
-                ("h", C.c_double), ("d_cs", C.c_void_p), ("d_rvir", C.c_void_p), ("d_rs", C.c_void_p),
-                ("d_nfw_series", C.c_void_p), ("d_drho1", C.c_void_p), ("delta2", C.c_double),
-                ("d_rho2", C.c_void_p), ("d_m2", C.c_void_p), ("d_r2", C.c_void_p)]
-
-
-class MassFnParams(C.Structure):
-    _fields_ = [("mode", C.c_int), ("deltac", C.c_double), ("st_A", C.c_double),
-                ("st_a", C.c_double), ("st_p", C.c_double), ("rho_m0", C.c_double),
-                ("lnm_uniform", C.c_int), ("lnm_step", C.c_double)]
-
-
-class HodParams(C.Structure):
-    _fields_ = [("sig_log_mstellar", C.c_double), ("alphasat", C.c_double), ("Bsat", C.c_double),
-                ("betasat", C.c_double), ("Bcut", C.c_double), ("betacut", C.c_double),
-                ("corr", C.c_int)]
-
-
-class Tracer(C.Structure):
-    _fields_ = [("kind", C.c_int), ("d_prof", C.c_void_p), ("d_cprof", C.c_void_p),
-                ("d_Nc", C.c_void_p), ("d_Ns", C.c_void_p), ("d_NcNs", C.c_void_p),
-                ("d_NsNsm1", C.c_void_p), ("d_ngal", C.c_void_p),
-                ("d_bias_override", C.c_void_p),
-                ("d_prof_nconst", C.c_void_p), ("d_prof_cconst", C.c_void_p),
-                ("d_cprof_nconst", C.c_void_p), ("d_cprof_cconst", C.c_void_p)]
-
-
-class MassFnPart(C.Structure):
-    """hmg_massfn_part: second stage of the sigma^2 contraction + n(z,m), b(z,m) as a link of a per-z chain."""
-    _fields_ = [("h_par", C.POINTER(MassFnParams)), ("d_ms", C.c_void_p), ("d_lnms", C.c_void_p),
-                ("d_tinker_z", C.c_void_p), ("d_sigma2", C.c_void_p), ("d_nzm", C.c_void_p), ("d_bh", C.c_void_p)]
-
-
-class HodPart(C.Structure):
-    """hmg_hod_part: hmg_hod's arguments."""
-    _fields_ = [("stage", C.c_int), ("h_par", C.POINTER(HodParams)), ("d_zs", C.c_void_p), ("d_ms", C.c_void_p),
-                ("d_log10mstar_thresh", C.c_void_p), ("d_nzm", C.c_void_p), ("d_bh", C.c_void_p),
-                ("d_wm", C.c_void_p), ("d_Nc", C.c_void_p), ("d_Ns", C.c_void_p), ("d_NsNsm1", C.c_void_p),
-                ("d_NcNs", C.c_void_p), ("d_ngal", C.c_void_p), ("d_bg", C.c_void_p)]
-
-
-class RowsPart(C.Structure):
-    """hmg_rows_part: hmg_profile_rowparams's arguments."""
-    _fields_ = [("kind", C.c_int), ("d_m200c", C.c_void_p), ("d_r200c", C.c_void_p), ("d_rvir", C.c_void_p),
-                ("d_zs", C.c_void_p), ("d_rhocz", C.c_void_p), ("d_hz", C.c_void_p), ("fit", C.c_double * 9),
-                ("gamma", C.c_double), ("alpha_const", C.c_double), ("amp_prefactor", C.c_double),
-                ("post_prefactor", C.c_double), ("d_amp", C.c_void_p), ("d_xc", C.c_void_p),
-                ("d_alpha", C.c_void_p), ("d_expo", C.c_void_p), ("d_cmax", C.c_void_p),
-                ("d_rscale", C.c_void_p), ("d_post", C.c_void_p),
-                ("d_ks", C.c_void_p), ("d_kts", C.c_void_p), ("nk", C.c_int), ("fft_m", C.c_int), ("d_rowsc", C.c_void_p)]
-
-
-class NfwPart(C.Structure):
-    """hmg_nfw_part: hmg_nfw_analytic's arguments."""
-    _fields_ = [("d_cs", C.c_void_p), ("d_rs", C.c_void_p), ("d_zs", C.c_void_p), ("d_ks", C.c_void_p),
-                ("d_nfw_series", C.c_void_p), ("d_uk", C.c_void_p)]
-
-
-class ProfileFftPart(C.Structure):
-    """hmg_profile_fft_part: hmg_profile_fft's arguments after nk."""
-    _fields_ = [("nxs", C.c_int), ("fft_step", C.c_double), ("d_xs", C.c_void_p), ("d_kts", C.c_void_p),
-                ("d_amp", C.c_void_p), ("d_xc", C.c_void_p), ("d_alpha", C.c_void_p), ("d_expo", C.c_void_p),
-                ("amp_const", C.c_double), ("xc_const", C.c_double), ("alpha_const", C.c_double),
-                ("expo_const", C.c_double), ("gamma", C.c_double), ("d_cmax", C.c_void_p), ("d_rss", C.c_void_p),
-                ("d_zs", C.c_void_p), ("d_ks", C.c_void_p), ("do_mass_norm", C.c_int), ("d_post", C.c_void_p),
-                ("d_out", C.c_void_p), ("d_nconst", C.c_void_p), ("d_cconst", C.c_void_p), ("d_logxs", C.c_void_p),
-                ("d_rowsc", C.c_void_p)]
-
-
-class PowerBatchDesc(C.Structure):
-    """hmg_power_batch_desc: hmg_power_batch's arguments after nk."""
-    _fields_ = [("ntr", C.c_int), ("h_tr", C.POINTER(Tracer)), ("npairs", C.c_int),
-                ("h_pair_a", C.POINTER(C.c_int)), ("h_pair_b", C.POINTER(C.c_int)),
-                ("d_nzm", C.c_void_p), ("d_bh", C.c_void_p), ("d_ms", C.c_void_p), ("d_wm", C.c_void_p),
-                ("d_ks", C.c_void_p), ("d_Pzk", C.c_void_p), ("rho_m0", C.c_double), ("kstar", C.c_double),
-                ("h_P1h", C.POINTER(C.c_void_p)), ("h_P2h", C.POINTER(C.c_void_p))]
-
-
-PB_PREPARED = 1
-HOD_ALL, HOD_OCCUPATIONS, HOD_SUMS = 0, 1, 2
-MF_SHETH_TORMEN, MF_TINKER10 = 0, 1
-PROF_BATTAGLIA_GAS, PROF_BATTAGLIA_PRES = 1, 2
-TRACER_MATTER, TRACER_HOD, TRACER_PRESSURE = 0, 1, 2
-KERNEL_POWER, KERNEL_NFW, KERNEL_PROFILE_FFT = 0, 1, 2
-EVENT_SLOTS = 4096
-NFW_SERIES_STRIDE = 36     # HMG_NFW_SERIES_STRIDE
-ROWSC_STRIDE = 8            # HMG_ROWSC_STRIDE
-GNFW_SIGMA, GNFW_MEAN, GNFW_EXCESS, GNFW_GENERAL = 0, 1, 2, 4
-GNFW_TABLE_DOUBLES = 416    # HMG_GNFW_TABLE_DOUBLES
-
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "hmgrid.h"))   # the tree travels whole: no installed layout
+_STRUCTS = {"hmg_halo_stage_args": "HaloStageArgs", "hmg_massfn_params": "MassFnParams", "hmg_hod_params": "HodParams",
+            "hmg_tracer": "Tracer", "hmg_massfn_part": "MassFnPart", "hmg_hod_part": "HodPart",
+            "hmg_rows_part": "RowsPart", "hmg_nfw_part": "NfwPart", "hmg_profile_fft_part": "ProfileFftPart",
+            "hmg_power_batch_desc": "PowerBatchDesc"}
+# DEFINES: HMG_<NAME> -> integer; SIGNATURES: name -> argtypes (restype is int for all but hmg_last_error); PARAMS: name ->
+# parameter names.  Read once, here, without the library: a header the reader does not understand fails the import.
+try:
+    with open(HEADER_PATH) as _f:
+        DEFINES, _structs, SIGNATURES, PARAMS = _abi.read(_f.read(), _STRUCTS)
+except OSError as e:
+    raise ImportError(f"{HEADER_PATH}: the C ABI's header cannot be read ({e}); the binding is derived from it") from e
+globals().update({_STRUCTS[c]: s for c, s in _structs.items()})      # nat.Tracer, nat.HodPart, ...
+ABI_VERSION = DEFINES["HMG_ABI_VERSION"]
+globals().update({n: DEFINES["HMG_" + n] for n in (
+    "PB_PREPARED", "HOD_ALL", "HOD_OCCUPATIONS", "HOD_SUMS", "MF_SHETH_TORMEN", "MF_TINKER10", "PROF_BATTAGLIA_GAS",
+    "PROF_BATTAGLIA_PRES", "TRACER_MATTER", "TRACER_HOD", "TRACER_PRESSURE", "KERNEL_POWER", "KERNEL_NFW",
+    "KERNEL_PROFILE_FFT", "EVENT_SLOTS", "NFW_SERIES_STRIDE", "ROWSC_STRIDE", "GNFW_SIGMA", "GNFW_MEAN", "GNFW_EXCESS",
+    "GNFW_GENERAL", "GNFW_TABLE_DOUBLES", "COMM_ID_BYTES")})
 _I, _D, _P, _Z = C.c_int, C.c_double, C.c_void_p, C.c_size_t
-# name -> argtypes (restype is int for all but hmg_last_error); mirrors include/hmgrid.h
-SIGNATURES = {
-    "hmg_abi_version": [],
-    "hmg_ctx_create": [_I, C.POINTER(_P)],
-    "hmg_ctx_destroy": [_P],
-    "hmg_malloc": [_P, _Z, C.POINTER(_P)],
-    "hmg_free": [_P, _P],
-    "hmg_memcpy_h2d": [_P, _P, _P, _Z],
-    "hmg_memcpy_d2h": [_P, _P, _P, _Z],
-    "hmg_memcpy_d2d": [_P, _P, _P, _Z],
-    "hmg_sync": [_P],
-    "hmg_host_alloc": [_P, _Z, C.POINTER(_P)],
-    "hmg_host_free": [_P, _P],
-    "hmg_memcpy_d2h_async": [_P, _P, _P, _Z],
-    "hmg_memcpy_h2d_async": [_P, _P, _P, _Z],
-    "hmg_event_synchronize": [_P, _I],
-    "hmg_graph_begin": [_P],
-    "hmg_graph_end": [_P, C.POINTER(_I)],
-    "hmg_graph_abort": [_P],
-    "hmg_graph_kernel_nodes": [_P, _I, C.POINTER(_I)],
-    "hmg_graph_launch": [_P, _I],
-    "hmg_graph_destroy": [_P, _I],
-    "hmg_lane_set": [_P, _I],
-    "hmg_profile_support_epoch": [_P, C.c_longlong],
-    "hmg_event_wait": [_P, _I],
-    "hmg_event_record": [_P, _I],
-    "hmg_elapsed_ms": [_P, _I, _I, C.POINTER(_D)],
-    "hmg_bracket_next": [_P, _I, _I, _I],
-    "hmg_sigma2": [_P, _I, _I, _I, _P, _P, _P, _P, _D, _P],
-    "hmg_sigma2_layout_size": [_I, _I, C.POINTER(_Z)],
-    "hmg_sigma2_prepare": [_P, _I, _I, _P, _P],
-    "hmg_sigma2_prepared": [_P, _I, _I, _I, _P, _P, _P, _P, _D, _P],
-    "hmg_sigma2_massfn": [_P, _I, _I, _I, _P, _P, _P, _P, _D, C.POINTER(MassFnParams), _P, _P, _P, _P, _P, _P],
-    "hmg_sigma2_massfn_halo": [_P, _I, _I, _I, _P, _P, _P, _P, _D, C.POINTER(MassFnParams), _P, _P, _P, _P, _P, _P,
-                               C.POINTER(HaloStageArgs)],
-    "hmg_halo_stage": [_P, _I, _I, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P, _P, _P, _P, _D, _P, _P, _P],
-    "hmg_massfn": [_P, _I, _I, C.POINTER(MassFnParams), _P, _P, _P, _P, _P, _P],
-    "hmg_halo_structure": [_P, _I, _I, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P, _P],
-    "hmg_mdelta_convert": [_P, _I, _I, _P, _P, _P, _D, _P, _P, _P],
-    "hmg_nfw_analytic": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "hmg_profile_rowparams": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(_D * 9), _D, _D, _D,
-                              _D, _P, _P, _P, _P, _P, _P, _P],
-    "hmg_profile_rows_from_mvir": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _D, _P, _P, C.POINTER(_D * 9), _D, _D,
-                                   _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "hmg_profile_fft": [_P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _D,
-                        _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
-    "hmg_profile_fft_logx": [_P, _I, _P, _P],
-    "hmg_prefix_deferral": [_P, _I],
-    "hmg_prefix_fill": [_P, _P],
-    "hmg_prefix_pending": [_P, _P, C.POINTER(_I)],
-    "hmg_prefix_fill_rows": [_P, _P, _P, _P, _I, _I],
-    "hmg_hod": [_P, _I, _I, C.POINTER(HodParams), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "hmg_power": [_P, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), _P, _P, _P, _P, _P, _P,
-                  _D, _D, _P, _P],
-    "hmg_power_batch": [_P, _I, _I, _I, _I, C.POINTER(Tracer), _I, C.POINTER(_I), C.POINTER(_I),
-                        _P, _P, _P, _P, _P, _P, _D, _D, C.POINTER(_P), C.POINTER(_P)],
-    "hmg_power_2halo_terms": [_P, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), _P, _P, _P, _P, _P, _D,
-                              _P, _P, _P],
-    "hmg_sigma2_halo_front": [_P, _I, _I, _I, _P, _P, _P, _P, _D, _P, C.POINTER(HaloStageArgs), C.POINTER(HodPart),
-                              C.POINTER(RowsPart)],
-    "hmg_group_rows": [_P, _I, _I, _I, _I, C.POINTER(MassFnPart), C.POINTER(HodPart), C.POINTER(RowsPart),
-                       C.POINTER(NfwPart)],
-    "hmg_group_profile": [_P, _I, _I, _I, C.POINTER(ProfileFftPart), C.POINTER(HodPart), C.POINTER(PowerBatchDesc)],
-    "hmg_group_tensors": [_P, _I, _I, _I, _I, C.POINTER(MassFnPart), C.POINTER(HodPart), C.POINTER(PowerBatchDesc),
-                          C.POINTER(NfwPart), C.POINTER(ProfileFftPart)],
-    "hmg_power_batch_run": [_P, _I, _I, _I, C.POINTER(PowerBatchDesc), _I],
-    "hmg_add": [_P, _Z, _P, _P, _P],
-    "hmg_limber": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
-    "hmg_fn2d": [_P, _I, _I, _I, _I, C.POINTER(_P), C.POINTER(_I), C.POINTER(_I), C.POINTER(_D), _I, _P],
-    "hmg_mstellar_halo": [_P, _I, _I, _P, _P, _P],
-    "hmg_trapz_rows": [_P, _I, _I, _P, _P, _P],
-    "hmg_sine_transform": [_P, _I, _I, _P, _P, _P],
-    "hmg_profile_fft_table": [_P, _I, _I, _I, _I, _D, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P],
-    "hmg_lensing_sigma_nfw": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
-    "hmg_lensing_sigma_nfw_off": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "hmg_lensing_kappa_2h": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P],
-    "hmg_lensing_delta_sigma_nfw": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
-    "hmg_lensing_delta_sigma_nfw_off": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "hmg_lensing_gamma_t_2h": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P],
-    "hmg_ksz_pqperp": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "hmg_ksz_nvv": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "hmg_ksz_limber_cl": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _D, _D, _P],
-    "hmg_xi_transform": [_P, _I, _I, _I, _P, _P, _P, _P],
-    "hmg_hankel_transform": [_P, _I, _I, _I, _P, _P, _P, _P, _P],
-    "hmg_angular_transform": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "hmg_angular_zsum": [_P, _I, _I, _I, _I, _P, _P, _P],
-    "hmg_trispectrum_1h": [_P, _I, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), C.POINTER(Tracer), C.POINTER(Tracer),
-                           _P, _P, _P, _D, _P, _P, _P, _P, _P, _P],
-    "hmg_bispectrum": [_P, _I, _I, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), C.POINTER(Tracer),
-                       _P, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P],
-    "hmg_response": [_P, _I, _I, _I, _I, _I, C.POINTER(Tracer), _P, _P, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P, _P],
-    "hmg_ssc": [_P, _I, _I, _I, _P, _P, _P, _P],
-    "hmg_gnfw_projected": [_P, _I, _I, _I, _I, _P, _P, _P, _D, _P, _P],
-    "hmg_gnfw_projected_smooth": [_P, _I, _I, _I, _I, _P, _P, _P, _D, _P, _P, _P],
-    "hmg_gnfw_quad_table": [_P],
-    "hmg_rsd_wedges": [_P, _I, _I, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), _P, _P, _P, _P, _P, _P, _D, _P, _P, _P,
-                       _P, _P, _D, _D, _D, _P, _P],
-    "hmg_rsd_multipoles": [_P, _I, _I, _I, _I, _I, C.POINTER(Tracer), C.POINTER(Tracer), _P, _P, _P, _P, _P, _P, _D, _P, _P,
-                           _P, _P, _P, _P, _D, _D, _D, _P, _P],
-    "hmg_onepoint_exponent": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _P, _P],
-    "hmg_onepoint_moments": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
-    "hmg_hod_ensemble": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "hmg_hod_ensemble_power": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P],
-    "hmg_comm_unique_id": [C.c_char * COMM_ID_BYTES],
-    "hmg_comm_init": [_P, C.c_char * COMM_ID_BYTES, _I, _I],
-    "hmg_comm_allgather": [_P, _P, _P, _Z],
-    "hmg_comm_allgather_multi": [_P, _I, C.POINTER(_P), C.POINTER(_P), _Z],
-    "hmg_comm_gather_async": [_P, _I, C.POINTER(_P), C.POINTER(_P), _Z, _I, _I, _I],
-    "hmg_comm_allgatherv_multi": [_P, _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z)],
-    "hmg_comm_gatherv_async": [_P, _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(_Z), _I, _I, _I],
-    "hmg_comm_info": [_P, C.POINTER(_I), C.POINTER(_I)],
-    "hmg_comm_barrier": [_P],
-    "hmg_comm_destroy": [_P],
-}
+
+
+def arguments(name, args, kw):
+    """The arguments of entry point `name` behind its context handle as one positional tuple: `args`, then the keywords
+    `kw` placed by the header's parameter names.  Raises NativeError on an unknown, duplicate or missing name."""
+    ctx, *names = PARAMS.get(name) or (None,)
+    if ctx != "ctx":
+        raise NativeError(f"{name}: not an entry point that takes a context")
+    given, rest = names[:len(args)], names[len(args):]
+    bad = ([f"unknown {k}" for k in kw if k not in names] + [f"duplicate {k}" for k in kw if k in given]
+           + [f"missing {n}" for n in rest if n not in kw])
+    if bad or len(args) > len(names):
+        raise NativeError(f"{name}: {', '.join(bad) or f'{len(args)} arguments for {len(names)} parameters'}")
+    return (*args, *(kw[n] for n in rest))
+
 
 _lib = None
 
@@ -477,7 +310,10 @@ class Context:
 
     _NO_FLUSH = frozenset(["hmg_bracket_next", "hmg_profile_support_epoch", "hmg_prefix_deferral"])      # calls that enqueue nothing and read nothing
 
-    def call(self, name, *args):
+    def call(self, name, *args, **kw):
+        """A native call behind the deferred stages.  Keywords are placed by the header's parameter names (arguments)."""
+        if kw:
+            args = arguments(name, args, kw)
         if name not in self._NO_FLUSH:
             self.flush()
         if self._trace is not None:

@@ -20,11 +20,8 @@ import scipy.constants as constants
 from . import _native as nat
 from .params import battaglia_defaults, default_params
 
-# hmg_fn2d function ids (include/hmgrid.h)
-(FN_TINKER_BIAS, FN_TINKER_FNU, FN_MHALO_STELLAR, FN_HOD_NC, FN_HOD_NS, FN_HOD_MFUNC, FN_HOD_NSNSM1,
- FN_HOD_NCNS, FN_FCON, FN_RHO_NFW, FN_R_FROM_M, FN_DUFFY, FN_BATT_FIT, FN_RHO_GAS_X, FN_RHO_GAS_R,
- FN_PE_X, FN_PE_R, FN_NGAL_INTEGRAND, FN_A2Z, FN_MDELTA, FN_BG_INTEGRAND, FN_ST_FSIGMA, FN_TINKER_FSIGMA, FN_WKR,
- FN_LINCOMB3, FN_MHALO_STELLAR_CORE, FN_BRUTE_INTEGRAND) = range(27)
+# hmg_fn2d function ids: HMG_FN_<X> of include/hmgrid.h as FN_<X>
+globals().update({k[4:]: v for k, v in nat.DEFINES.items() if k.startswith("HMG_FN_")})
 
 _ctx_override = None
 

@@ -1388,13 +1388,14 @@ class HaloModel(Cosmology):
         whatever reuses them is enqueued behind it."""
         return ctx.upload_int32(tables[0]), ctx.upload(tables[1]), ctx.upload(tables[2])
 
-    def _grid_ptrs(self, bias=True):
-        """The model block of a native call in the order of its arguments: nzm, bh, ms, wm, ks, Pzk, rho_m0 (bias=False,
-        the trispectrum: nzm, ms, wm, rho_m0)."""
-        if not bias:
-            return self._d_nzm.ptr, self._d_ms().ptr, self._d_wm().ptr, self._rho_m0()
-        return (self._d_nzm.ptr, self._d_bh.ptr, self._d_ms().ptr, self._d_wm().ptr, self._d_ks().ptr, self._d_Pzk().ptr,
-                self._rho_m0())
+    _MODEL_BLOCK = {"d_nzm": lambda h: h._d_nzm.ptr, "d_bh": lambda h: h._d_bh.ptr, "d_ms": lambda h: h._d_ms().ptr,
+                    "d_wm": lambda h: h._d_wm().ptr, "d_ks": lambda h: h._d_ks().ptr, "d_Pzk": lambda h: h._d_Pzk().ptr,
+                    "rho_m0": lambda h: h._rho_m0()}
+
+    def _model_block(self, entry):
+        """The model block of a native call, by the header's parameter names: those of d_nzm, d_bh, d_ms, d_wm, d_ks,
+        d_Pzk, rho_m0 that `entry` declares, in its order."""
+        return {n: self._MODEL_BLOCK[n](self) for n in nat.PARAMS[entry] if n in self._MODEL_BLOCK}
 
     def trispectrum_device(self, name, name2=None, name3=None, name4=None, kindex=None, damping=True, idx=None,
                            frac=None, scale=None, zweights=None, per_z=True):
@@ -1423,8 +1424,10 @@ class HaloModel(Cosmology):
         d_g = ctx.upload(zweights) if zweights is not None else None
         T = ctx.empty((nz, n, n)) if per_z else None
         Tz = ctx.empty((n, n)) if zweights is not None else None
-        ctx.call("hmg_trispectrum_1h", nz, nm, nk, n, *(C.byref(t) for t in tr), *self._grid_ptrs(bias=False), d_idx.ptr,
-                 d_frac.ptr, d_scale.ptr, nat.ptr(d_g), nat.ptr(T), nat.ptr(Tz))
+        ha, hb, hc, hd = (C.byref(t) for t in tr)
+        ctx.call("hmg_trispectrum_1h", nz=nz, nm=nm, nk=nk, n=n, h_a=ha, h_b=hb, h_c=hc, h_d=hd,
+                 **self._model_block("hmg_trispectrum_1h"), d_idx=d_idx.ptr, d_frac=d_frac.ptr, d_scale=d_scale.ptr,
+                 d_zweights=nat.ptr(d_g), d_T=nat.ptr(T), d_Tz=nat.ptr(Tz))
         self._sync_point()
         return T, Tz
 
@@ -1482,9 +1485,11 @@ class HaloModel(Cosmology):
         B = ctx.empty((3, nz, nt)) if per_z else None
         Bz = ctx.empty((3, nt)) if zweights is not None else None
         J = ctx.empty((3, nz, n)) if want_J else None
-        ctx.call("hmg_bispectrum", nz, nm, nk, n, nt, *(C.byref(t) for t in tr), *self._grid_ptrs(),
-                 float(self.p["kstar_damping"]) if damping else 0.0, d_idx.ptr, d_frac.ptr, d_scale.ptr, d_tri.ptr,
-                 nat.ptr(d_g), nat.ptr(B), nat.ptr(Bz), nat.ptr(J))
+        ha, hb, hc = (C.byref(t) for t in tr)
+        ctx.call("hmg_bispectrum", nz=nz, nm=nm, nk=nk, n=n, nt=nt, h_a=ha, h_b=hb, h_c=hc,
+                 **self._model_block("hmg_bispectrum"), kstar=float(self.p["kstar_damping"]) if damping else 0.0,
+                 d_idx=d_idx.ptr, d_frac=d_frac.ptr, d_scale=d_scale.ptr, d_tri=d_tri.ptr, d_zweights=nat.ptr(d_g),
+                 d_B=nat.ptr(B), d_Bz=nat.ptr(Bz), d_J=nat.ptr(J))
         self._sync_point()
         return B, Bz, J
 
@@ -1526,9 +1531,9 @@ class HaloModel(Cosmology):
         d_dlnP = self._dev("dlnP", lambda: covmod.dlnp_table(self.ks, self.Pzk))
         R = ctx.empty((npairs, nz, n))
         P = ctx.empty((3, npairs, nz, n)) if parts else None
-        grid = self._grid_ptrs()
-        ctx.call("hmg_response", nz, nm, nk, n, npairs, tr, *grid[:6], d_dlnP.ptr, grid[6],
-                 float(self.p["kstar_damping"]) if damping else 0.0, d_idx.ptr, d_frac.ptr, d_scale.ptr, R.ptr, nat.ptr(P))
+        ctx.call("hmg_response", nz=nz, nm=nm, nk=nk, n=n, np=npairs, h_pairs=tr, **self._model_block("hmg_response"),
+                 d_dlnP=d_dlnP.ptr, kstar=float(self.p["kstar_damping"]) if damping else 0.0, d_idx=d_idx.ptr,
+                 d_frac=d_frac.ptr, d_scale=d_scale.ptr, d_R=R.ptr, d_parts=nat.ptr(P))
         self._sync_point()
         return R, P
 
@@ -1609,11 +1614,13 @@ class HaloModel(Cosmology):
         ta, tb = (self._tracer(r, 1) for r in recs)
         d_k, d_damp, d_sig, d_f = ctx.upload_int32(tables[0]), ctx.upload(tables[1]), ctx.upload(tables[2]), ctx.upload(tables[3])
         d_mus = ctx.upload(mus)
-        extra = () if wl is None else (ctx.upload(np.ascontiguousarray(wl, dtype=np.float64)),)
+        d_wl = None if wl is None else ctx.upload(np.ascontiguousarray(wl, dtype=np.float64))
         out = ctx.empty((2, nz, n, out_last))
         parts = ctx.empty(parts_shape(nz, n)) if parts_shape else None
-        ctx.call(entry, nz, nm, nk, n, nmu, C.byref(ta), C.byref(tb), *self._grid_ptrs(), d_k.ptr, d_damp.ptr, d_mus.ptr,
-                 *(e.ptr for e in extra), d_sig.ptr, d_f.ptr, *alphas, out.ptr, nat.ptr(parts))
+        own = dict(d_parts=nat.ptr(parts)) if wl is None else dict(d_wl=d_wl.ptr, d_Q=nat.ptr(parts))
+        ctx.call(entry, nz=nz, nm=nm, nk=nk, n=n, nmu=nmu, h_a=C.byref(ta), h_b=C.byref(tb), **self._model_block(entry),
+                 d_kindex=d_k.ptr, d_damp=d_damp.ptr, d_mus=d_mus.ptr, d_sigma=d_sig.ptr, d_f=d_f.ptr, alpha_m=alphas[0],
+                 alpha_c=alphas[1], alpha_s=alphas[2], d_out=out.ptr, **own)
         self._sync_point()
         return out, parts      # (the tables go back to the free list: whatever reads them was enqueued before)
 
@@ -2103,8 +2110,9 @@ class HaloModel(Cosmology):
         """One hmg_hod_ensemble launch at the thresholds l10 (S, nz): (d_lthr, d_ngal, d_bg)."""
         nz, nm = self._nz, self._nm
         d_thr, d_ngal, d_bg = ctx.upload(np.ascontiguousarray(l10)), ctx.empty((S, nz)), ctx.empty((S, nz))
-        ctx.call("hmg_hod_ensemble", S, nz, nm, flag, d_par.ptr, d_thr.ptr, self._d_zs().ptr, self._d_ms().ptr,
-                 self._d_nzm.ptr, self._d_bh.ptr, self._d_wm().ptr, d_ngal.ptr, d_bg.ptr, nat.ptr(occ), nat.ptr(coef))
+        ctx.call("hmg_hod_ensemble", S=S, nz=nz, nm=nm, corr=flag, d_par=d_par.ptr, d_lthr=d_thr.ptr, d_zs=self._d_zs().ptr,
+                 **self._model_block("hmg_hod_ensemble"), d_ngal=d_ngal.ptr, d_bg=d_bg.ptr, d_occ=nat.ptr(occ),
+                 d_coef=nat.ptr(coef))
         return d_thr, d_ngal, d_bg
 
     def _hodens_bisect(self, ctx, d_par, target):
@@ -2181,8 +2189,9 @@ class HaloModel(Cosmology):
         d_damp = ctx.upload(np.ascontiguousarray(damp, dtype=np.float64))
         out = ctx.empty((4, S, nz, n))
         P = ctx.empty((3, S, nz, n)) if parts else None
-        ctx.call("hmg_hod_ensemble_power", S, nz, nm, nk, n, d_us.ptr, d_um.ptr, coef.ptr, d_ngal.ptr, d_bg.ptr,
-                 *self._grid_ptrs(), nat.ptr(d_k), d_damp.ptr, out.ptr, nat.ptr(P))
+        ctx.call("hmg_hod_ensemble_power", S=S, nz=nz, nm=nm, nk=nk, n=n, d_us=d_us.ptr, d_um=d_um.ptr, d_coef=coef.ptr,
+                 d_ngal=d_ngal.ptr, d_bg=d_bg.ptr, **self._model_block("hmg_hod_ensemble_power"), d_kindex=nat.ptr(d_k),
+                 d_damp=d_damp.ptr, d_out=out.ptr, d_parts=nat.ptr(P))
         self._sync_point()
         return hodens.HodEnsembleResult(out, d_ngal, d_bg, d_thr, P, n_iter)
 

@@ -146,13 +146,14 @@ def _launch(ctx, entry, arrays, amp, dims, window, extra, width, per_z):
     d_amp = None if amp is None else _dev(ctx, amp)
     rows = ctx.empty((nz, width))
     total = None if per_z else ctx.empty((width,))
-    ctx.call(entry, nz, nm, nt, d_signal.ptr, d_area.ptr, nat.ptr(d_amp), d_nzm.ptr, d_wm.ptr, d_zw.ptr, *window, *extra,
-             rows.ptr, nat.ptr(total))
+    ctx.call(entry, nz=nz, nm=nm, nt=nt, d_signal=d_signal.ptr, d_area=d_area.ptr, d_amp=nat.ptr(d_amp), d_nzm=d_nzm.ptr,
+             d_wm=d_wm.ptr, d_zw=d_zw.ptr, m_lo=window[0], m_hi=window[1], **extra, d_rows=rows.ptr, d_total=nat.ptr(total))
     return (rows if per_z else total).numpy()
 
 
 def _exponent(ctx, arrays, amp, dims, window, nlambda, dlambda, per_z):
-    out = _launch(ctx, "hmg_onepoint_exponent", arrays, amp, dims, window, (nlambda, dlambda), 2 * nlambda, per_z)
+    out = _launch(ctx, "hmg_onepoint_exponent", arrays, amp, dims, window, dict(nlambda=nlambda, dlambda=dlambda), 2 * nlambda,
+                  per_z)
     out = out.reshape(-1, 2, nlambda)
     A = np.empty((out.shape[0], nlambda), dtype=np.complex128)
     A.real, A.imag = out[:, 0], out[:, 1]
@@ -160,7 +161,7 @@ def _exponent(ctx, arrays, amp, dims, window, nlambda, dlambda, per_z):
 
 
 def _moments(ctx, arrays, amp, dims, window, per_z):
-    return _launch(ctx, "hmg_onepoint_moments", arrays, amp, dims, window, (), 4, per_z)
+    return _launch(ctx, "hmg_onepoint_moments", arrays, amp, dims, window, {}, 4, per_z)
 
 
 def check_lambda(nlambda, dlambda):

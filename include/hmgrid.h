@@ -12,6 +12,12 @@
  *    (hmvec/hmvec.py:24-31).
  *  - Pointers named d_* are DEVICE pointers obtained from hmg_malloc; pointers
  *    named h_* are host pointers.  No framework types cross this boundary.
+ *  - This header is the ONE declaration of the ABI: the Python package derives its ctypes binding from it at import
+ *    (hmvec_amd/_abi.py) and binds nothing by hand.  That makes the style binding: `#define HMG_<NAME> <integer>`,
+ *    `typedef struct { ... } hmg_<x>;`, `int hmg_<name>(...);`, scalars int / double / size_t / long long, and every
+ *    pointer parameter or field other than hmg_ctx*, void* and a pointer to one of the structs named d_* (bound as a
+ *    plain address) or h_* (bound as a typed host pointer).  An unprefixed pointer or a declaration in another style
+ *    fails the import, naming it.  Parameter names are what keyword calls of the Python layer go by.
  *  - Every function returns 0 on success, non-zero on failure; the message for the
  *    calling thread's last failure is returned by hmg_last_error().
  *  - All work is enqueued on the context's stream; only hmg_memcpy_h2d, hmg_memcpy_d2h, hmg_sync,
@@ -328,7 +334,7 @@ int hmg_prefix_deferral(hmg_ctx* ctx, int on);
  * Inside a captured step the fill is recorded whenever the context has ever seen a deferred transform into d_out
  * (what a replay leaves pending is decided per replay, not at capture time).                                  */
 int hmg_prefix_fill(hmg_ctx* ctx, double* d_out);
-int hmg_prefix_pending(hmg_ctx* ctx, const double* d_out, int* pending);
+int hmg_prefix_pending(hmg_ctx* ctx, const double* d_out, int* h_pending);
 /* The fill itself, for a caller that keeps its own books: d_cconst[row] into [0, d_nconst[row] & ~(HMG_PREFIX_TILE-1))
  * of each of the `rows` rows of nk doubles.                                                                    */
 int hmg_prefix_fill_rows(hmg_ctx* ctx, double* d_out, const int* d_nconst, const double* d_cconst, int rows, int nk);

@@ -216,7 +216,7 @@ def test_refusals_and_no_side_effects(h):
     ctx = h._ctx()
     launched = []
     orig_call, orig_now = ctx.call, ctx.call_now
-    ctx.call = lambda name, *a: (launched.append(name), orig_call(name, *a))[1]
+    ctx.call = lambda name, *a, **kw: (launched.append(name), orig_call(name, *a, **kw))[1]
     ctx.call_now = lambda name, *a: (launched.append(name), orig_now(name, *a))[1]
     try:
         for kw in (dict(), dict(mthresh=MTHRESH, ngal=MTHRESH), dict(mthresh=MTHRESH[:5]), dict(mthresh=MTHRESH[:, :2]),
@@ -251,13 +251,14 @@ def test_refusals_and_no_side_effects(h):
              h._d_wm().ptr, d_ngal.ptr, d_bg.ptr, None, coef.ptr)
     d_u = h.uk_profiles.dev("nfw")
     out, d_damp = ctx.empty((4, S, nz, 2)), ctx.upload(np.ones(2))
+    block = h._model_block("hmg_hod_ensemble_power").values()      # (in the order of the entry point's parameters)
     for bad in ([0, NK], [-1, 5]):
         d_k = ctx.upload_int32(np.array(bad, dtype=np.int32))
         rc = ctx.lib.hmg_hod_ensemble_power(ctx.handle, S, nz, NM, NK, 2, d_u.ptr, d_u.ptr, coef.ptr, d_ngal.ptr, d_bg.ptr,
-                                            *h._grid_ptrs(), d_k.ptr, d_damp.ptr, out.ptr, None)
+                                            *block, d_k.ptr, d_damp.ptr, out.ptr, None)
         assert rc != 0 and b"outside 0 .. nk-1" in ctx.lib.hmg_last_error()
     rc = ctx.lib.hmg_hod_ensemble_power(ctx.handle, S, nz, NM, NK, 2, d_u.ptr, d_u.ptr, coef.ptr, d_ngal.ptr, d_bg.ptr,
-                                        *h._grid_ptrs(), None, d_damp.ptr, out.ptr, None)
+                                        *block, None, d_damp.ptr, out.ptr, None)
     assert rc != 0 and b"n must be nk" in ctx.lib.hmg_last_error()
     rc = ctx.lib.hmg_hod_ensemble(ctx.handle, S, nz, NM, 2, d_par.ptr, d_thr.ptr, h._d_zs().ptr, h._d_ms().ptr, h._d_nzm.ptr,
                                   h._d_bh.ptr, h._d_wm().ptr, d_ngal.ptr, d_bg.ptr, None, None)

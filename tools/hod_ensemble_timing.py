@@ -122,7 +122,8 @@ def main():
 
                 def kernel():
                     ctx.call("hmg_hod_ensemble_power", S, nz, nm, nk, nk, d_u.ptr, d_u.ptr, coef.ptr, d_ngal.ptr, d_bg.ptr,
-                             *h._grid_ptrs(), None, d_damp.ptr, out.ptr, None)
+                             **h._model_block("hmg_hod_ensemble_power"), d_kindex=None, d_damp=d_damp.ptr, d_out=out.ptr,
+                             d_parts=None)
 
                 occupations()
                 k = alternate(ctx, {"occupations": occupations, "kernel": kernel}, a.reps, a.warmup, a.window)
