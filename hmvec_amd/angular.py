@@ -13,11 +13,12 @@ times the two windows (``Cosmology.angular_weights``).  n = 0 gives w(theta) and
 """
 import numpy as np
 
-from . import realspace
+from . import realspace, spectra
 
 __all__ = ["angular_from_power"]
 
 ORDERS = (0, 2, 4)
+_trapz = getattr(np, "trapezoid", None) or np.trapz
 
 
 def check_order(order):
@@ -95,3 +96,110 @@ def angular_from_power(ks, P, thetas, chis, zweights, order=0, *, ctx=None):
         ctx, d_ks, d_P = realspace._resident(ks, P, ctx)
         outs = tuple(o.reshape(shape) for o in angular_rows(ctx, d_ks, d_P, n, nz, ks.size, thetas, chis, zw, orders))
     return outs if isinstance(order, (tuple, list)) else outs[0]
+
+
+class AngularMixin:
+    """HaloModel's w(theta), gamma_t(theta), xi+-(theta): the rows are transformed at chi(z) theta
+    and summed over z on the device (RealspaceMixin's _realspace_pair, _realspace_all); only (nw, ntheta) results cross."""
+
+    def _angular_request(self, zweights, order, term):
+        """(zsum, orders, stacked) of an angular request: the distances of self.zs, the checked (nw, nz) weights
+        (None: the z measure alone, both windows 1) and orders, and whether the weights came with the nw axis."""
+        spectra.check_term(term, self._XI_TERMS)
+        orders = check_order(order)
+        nz = np.size(self.zs)
+        if zweights is None:
+            zweights = self.angular_weights(self.zs, 1.0, 1.0)
+        zw, stacked = check_zweights(zweights, nz)
+        chis = check_chis(np.reshape(self.comoving_radial_distance(self.zs), -1), nz)
+        return (chis, zw), orders, stacked
+
+    def get_angular(self, thetas, name, name2=None, zweights=None, order=0, term="total"):
+        """Angular correlation function zeta_order(theta) = sum_z zweights[z] W_order^(z)(chi(z) theta) of the spectrum
+        of (name, name2) - term as for get_xi - on the model's redshifts self.zs, chi = comoving_radial_distance(zs)
+        (every z must be positive): bit for bit angular.angular_from_power(ks, get_power(name, name2), thetas, chi,
+        zweights, order).  thetas in radians.  zweights: (nz,) or (nw, nz), the z measure times the two windows
+        (angular_weights(zs, W1, W2)); None is the measure alone.  order: 0, 2, 4 or a strictly increasing tuple of
+        them.  Returns (ntheta,), or (nw, ntheta) for two-dimensional weights; a tuple of them for a tuple of
+        orders."""
+        zsum, orders, stacked = self._angular_request(zweights, order, term)
+        outs = self._realspace_pair(thetas, name, name2, term, orders, zsum)
+        outs = tuple(o[0] if stacked else o[0, 0] for o in outs)
+        return outs if isinstance(order, (tuple, list)) else outs[0]
+
+    def _dndz_window(self, dndz, what):
+        """dndz / int dndz dz on self.zs (C_gg's convention); None is a uniform distribution over the range of zs."""
+        zs = np.reshape(self.zs, -1)
+        if zs.size < 2:
+            raise ValueError(f"{what} needs at least two redshifts in the model")
+        dndz = np.ones(zs.size) if dndz is None else np.asarray(dndz, dtype=np.float64)
+        if dndz.shape != zs.shape or not np.all(np.isfinite(dndz)):
+            raise ValueError(f"{what} must be a finite vector of {zs.size} values on the model's redshifts")
+        norm = _trapz(dndz, zs)
+        if not norm > 0:
+            raise ValueError(f"{what} must have a positive integral over the model's redshifts")
+        return dndz / norm
+
+    def _source_window(self, zsource, sdndz, what):
+        """lensing_window on self.zs of a source plane (zsource a scalar) or of sources sdndz on the grid zsource."""
+        if zsource is None:
+            raise ValueError(f"{what} is required: a source redshift, or the grid of a source distribution")
+        zsource = np.asarray(zsource, dtype=np.float64).reshape(-1)
+        if (zsource.size == 1) != (sdndz is None) or (sdndz is not None and np.shape(sdndz) != zsource.shape):
+            raise ValueError(f"{what}: one source redshift without a distribution, or a grid with its distribution")
+        return self.lensing_window(np.reshape(self.zs, -1), zsource, sdndz)
+
+    def get_w_theta(self, thetas, name, name2=None, dndz=None, dndz2=None, term="total"):
+        """Angular clustering w(theta), shape (ntheta,): order 0 with the windows dndz / int dndz dz of the two samples
+        on self.zs (C_gg's convention; dndz None: uniform over the range of zs, dndz2 None: the first sample's) -
+        bit for bit get_angular(thetas, name, name2, angular_weights(zs, W1, W2), 0, term)."""
+        spectra.check_term(term, self._XI_TERMS)
+        W1 = self._dndz_window(dndz, "dndz")
+        W2 = W1 if dndz2 is None else self._dndz_window(dndz2, "dndz2")
+        return self.get_angular(thetas, name, name2, self.angular_weights(self.zs, W1, W2), 0, term)
+
+    def get_gamma_t(self, thetas, name, name2="nfw", dndz=None, zsource=None, sdndz=None, term="total"):
+        """Tangential shear gamma_t(theta), shape (ntheta,), of the lenses `name` (window dndz / int dndz dz as for
+        get_w_theta) about sources at zsource (a single redshift, or a grid with the distribution sdndz: the arguments
+        of lensing_window): order 2 of the lens-matter spectrum - bit for bit
+        get_angular(thetas, name, name2, angular_weights(zs, W_lens, lensing_window(zs, zsource, sdndz)), 2, term)."""
+        spectra.check_term(term, self._XI_TERMS)
+        W1 = self._dndz_window(dndz, "dndz")
+        W2 = self._source_window(zsource, sdndz, "zsource")
+        return self.get_angular(thetas, name, name2, self.angular_weights(self.zs, W1, W2), 2, term)
+
+    def get_xi_pm(self, thetas, name="nfw", name2=None, zsource=None, sdndz=None, zsource2=None, sdndz2=None,
+                  term="total"):
+        """Shear correlation functions (xi+(theta), xi-(theta)), each (ntheta,), of sources at zsource (and zsource2,
+        default the same; arguments as for get_gamma_t): orders 0 and 4 of the matter spectrum from ONE launch - bit
+        for bit get_angular(thetas, name, name2, angular_weights(zs, W_kappa1, W_kappa2), (0, 4), term)."""
+        spectra.check_term(term, self._XI_TERMS)
+        W1 = self._source_window(zsource, sdndz, "zsource")
+        W2 = W1 if zsource2 is None else self._source_window(zsource2, sdndz2, "zsource2")
+        return self.get_angular(thetas, name, name2, self.angular_weights(self.zs, W1, W2), (0, 4), term)
+
+    def get_angular_all(self, pairs, thetas, zweights, order=0, term="total"):
+        """{(name, name2): zeta_order(theta)} for several pairs: their spectra from one pass over the profile tensors
+        (get_power_all's), ONE transform launch of len(pairs) * nz rows and one contraction over z.  zweights: (nz,)
+        or (nw, nz) shared by all pairs, or a dict {pair: weights}.  Each entry is bit for bit get_angular of that
+        pair with its weights."""
+        pairs = [tuple(p) for p in pairs]
+        if isinstance(zweights, dict):
+            missing = [p for p in pairs if p not in zweights]
+            if missing:
+                raise ValueError(f"zweights has no entry for {missing}")
+            per = [check_zweights(zweights[p], np.size(self.zs)) for p in pairs]
+        else:
+            per = [check_zweights(zweights, np.size(self.zs))] * len(pairs)
+        # every pair's rows of weights go stacked into the one contraction and the pair keeps its own: an output's
+        # chain reads its row of weights alone, so its bits are those of the pair's own call
+        shared = not isinstance(zweights, dict)
+        stack = None if not per else per[0][0] if shared else np.concatenate([zw for zw, _ in per])
+        zsum, orders, _ = self._angular_request(stack, order, term)
+        pairs, outs = self._realspace_all(pairs, thetas, term, orders, zsum)
+        res, lo = {}, 0
+        for i, (p, (zw, stacked)) in enumerate(zip(pairs, per)):
+            ent = tuple(o[i, lo:lo + zw.shape[0]] if stacked else o[i, lo] for o in outs)
+            res[p] = ent if isinstance(order, (tuple, list)) else ent[0]
+            lo += 0 if shared else zw.shape[0]
+        return res

@@ -9,9 +9,12 @@ profiles are members of the family.  The kernels are in hmvec_amd/csrc/kernels/g
 import ctypes as C
 
 import numpy as np
+import scipy.constants as constants
 
 from . import _native as nat
 from ._native import as_device as _dev, context_or_default as _context
+from .params import default_params
+from .utils import _R_from_M
 
 __all__ = ["projected_gnfw", "quadrature_table"]
 
@@ -136,3 +139,167 @@ def quadrature_table():
         out[name] = t[at:at + size].copy()
         at += size
     return out
+
+
+_X_H = 0.76      # hydrogen mass fraction of the Battaglia profiles (hmvec/hmvec.py:922)
+
+
+def _battaglia_fit(m200c, z, A0, alpham, alphaz):
+    """A0 (M200c / 1e14)^alpha_m (1+z)^alpha_z on the host (hmvec/hmvec.py:800-802)."""
+    return A0 * (m200c / 1.0e14) ** alpham * (1.0 + z) ** alphaz
+
+
+def _mdelta_host(M1, c1, drho1, drho2):
+    """Mass in the definition Delta rho = drho2 of NFW halos of mass M1 and concentration c1 in the definition drho1
+    (hmvec/hmvec.py:770-798) on the host: equal r_s and rho_s give M2 / F(c2) = M1 / F(c1) with
+    c2 = c1 (M2 drho1 / (M1 drho2))^(1/3), F(c) = ln(1+c) - c/(1+c); Newton in ln(M2/M1) to machine precision."""
+    def F(c):
+        return np.log1p(c) - c / (1.0 + c)
+    lnF1 = np.log(F(c1))
+    lq = np.zeros_like(M1)
+    for _ in range(60):
+        c2 = c1 * (np.exp(lq) * drho1 / drho2) ** (1.0 / 3.0)
+        F2 = F(c2)
+        resid = lq - np.log(F2) + lnF1
+        dlnF = c2 * c2 / (1.0 + c2) ** 2 / F2           # d ln F / d ln c
+        step = resid / (1.0 - dlnF / 3.0)
+        lq = lq - step
+        if np.all(np.abs(step) < 1e-15):
+            break
+    return M1 * np.exp(lq)
+
+
+def halo_rings(halos, rowfn, truncate, angles):
+    """The per-redshift loop over the rows of _gas_halos that the projected profiles and the rings of the one-point PDF
+    share; angles[z]: the angles [rad] of redshift z, (1, ntheta) or one row per halo.  Yields per redshift
+    (x, alpha, eta, xcut, pref, r, gamma): the arguments of the projection in scaled units, the prefactor and the scale
+    radius of every halo, and the family's gamma.  The beam width in scaled units is left to the caller: the two do not
+    form it with the same operations."""
+    for (z, da, rhoc, rvir, m200c, r200c), ang in zip(halos, angles):
+        r, al, gamma, et, pf = rowfn(z, rhoc, m200c, r200c)
+        yield da * ang / r[:, None], al + 0.0 * r, et, truncate * rvir / r, pf, r, gamma
+
+
+class GasProjectionMixin:
+    """HaloModel's projected gas and pressure profiles.  Per-halo scalars on the host, one redshift
+    at a time, as for the cluster-lensing profiles: a z slice of a batch is bit for bit a single-z model's result."""
+
+    def _gas_halos(self, Ms, concs, truncate):
+        """(Ms, [(z, D_A, rho_crit, r_vir, M200c, R200c) per z]) with the mass conversion of add_battaglia_profile
+        (hmvec/hmvec.py:215-225): the model's mass definition -> 200 rho_crit(z), concs=None the Duffy concentration."""
+        Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()
+        if not np.all(np.isfinite(Ms)) or np.any(Ms <= 0):
+            raise ValueError("Ms must be finite and positive")
+        if concs is not None:
+            concs = np.atleast_1d(np.asarray(concs, dtype=np.float64)).ravel()
+            if concs.size != Ms.size:
+                raise ValueError("Ms and concs must have the same length")
+            if not np.all(np.isfinite(concs)) or np.any(concs <= 0):
+                raise ValueError("concs must be finite and positive")
+        if not np.isfinite(truncate) or truncate <= 0:
+            raise ValueError("truncate must be finite and positive")
+        A, al, be = (float(self.p[f"duffy_{k}_{self.mdef}"]) for k in ("A", "alpha", "beta"))
+        rows = []
+        for z in self.zs:
+            zz = np.array([z])
+            rhoc = float(self.rho_critical_z(zz)[0])
+            if self.mdef == "vir":
+                drho1 = rhoc * float(self.deltav(zz)[0])
+            elif self.mdef == "mean":
+                drho1 = float(self.rho_matter_z(zz)[0]) * 200.0
+            else:
+                raise NotImplementedError(self.mdef)
+            cs = A * (self.h * Ms / 2.0e12) ** al * (1.0 + z) ** be if concs is None else concs
+            m200c = _mdelta_host(Ms, cs, drho1, 200.0 * rhoc)
+            rows.append((float(z), float(self.angular_diameter_distance(zz)[0]), rhoc,
+                         _R_from_M(Ms, drho1, delta=1.0), m200c, _R_from_M(m200c, rhoc, delta=200.0)))
+        return Ms, rows
+
+    def _projected_profile(self, kind, thetas, Ms, concs, truncate, fwhm, rowfn, norm="fit"):
+        """prefactor x projected_gnfw(kind) for every (z, M, theta).  rowfn(z, rho_crit, M200c, R200c) returns the halo's
+        (scale radius, alpha, gamma, eta, prefactor) with gamma one number.  norm="mass": the prefactor is M / (N r^2)
+        instead, N = 4 pi int_0^xcut x^2 f dx from the "mean" kind at s = xcut."""
+        th = self._lensing_thetas(thetas)
+        if norm not in ("fit", "mass"):
+            raise ValueError(f"norm must be 'fit' or 'mass', got {norm!r}")
+        if fwhm is not None and (not np.isfinite(fwhm) or fwhm < 0):
+            raise ValueError("fwhm must be finite and non-negative")
+        Ms, halos = self._gas_halos(Ms, concs, truncate)
+        x, alpha, eta, xcut, pref, rscale, (*_, gamma) = zip(*halo_rings(halos, rowfn, truncate, [th[None, :]] * len(halos)))
+        smooth = [da * float(fwhm or 0.0) / np.sqrt(8.0 * np.log(2.0)) / r for (_, da, *_), r in zip(halos, rscale)]
+        x, alpha, eta, xcut, pref, smooth, rscale = (np.concatenate(a) for a in (x, alpha, eta, xcut, pref, smooth, rscale))
+        ctx = self._main()
+        if norm == "mass":
+            N = projected_gnfw(xcut[:, None], alpha, gamma, eta, xcut, kind="mean", ctx=ctx)[:, 0] * np.pi * xcut ** 2
+            pref = np.tile(Ms, self._nz) / (N * rscale ** 2)
+        prof = projected_gnfw(x, alpha, gamma, eta, xcut, kind=kind, smooth=smooth if fwhm else None, ctx=ctx)
+        prof = (pref[:, None] * prof).reshape(self._nz, Ms.size, th.size)
+        return prof[0] if self._nz == 1 else prof
+
+    def _gas_rowfn(self, family, param_override):
+        """Battaglia gas density (hmvec/hmvec.py:844-860) as a member of the family: x = r / (R200c / 2),
+        eta = (beta + gamma) / alpha, amplitude (Omega_b / Omega_m) rho_crit(z) rho0 times the scale radius."""
+        pp = self._battaglia_gas_pparams(family, param_override)
+        gamma = float(pp["battaglia_gas_gamma"])
+        fb = self.p["ombh2"] / self.h ** 2.0 / self.omm0
+
+        def rowfn(z, rhoc, m200c, r200c):
+            rho0, alpha, beta = (_battaglia_fit(m200c, z, *(pp[q + s] for s in ("A0", "alpham", "alphaz")))
+                                 for q in ("rho0_", "alpha_", "beta_"))
+            rg = 0.5 * r200c
+            return rg, alpha, gamma, (beta + gamma) / alpha, fb * rhoc * rho0 * rg
+        return rowfn
+
+    def gas_sigma_1h_profiles(self, thetas, Ms, concs=None, family=None, param_override=None, truncate=1.0, norm="fit",
+                              fwhm=None):
+        """Projected gas surface density Sigma_gas [Msun/Mpc^2] of the Battaglia gas profile (the profile of
+        add_battaglia_profile) around halos of mass Ms (the model's mass definition; concs=None: Duffy) at angles thetas
+        [rad]: (nM, ntheta), or (nz, nM, ntheta) with several redshifts.  The profile is cut at truncate r_vir.
+        norm="fit": the amplitude of the fit, (Omega_b / Omega_m) rho_crit(z) rho0; norm="mass": the same shape holding
+        the halo mass Ms inside the cut (the profile whose transform uk_profiles approximates).  fwhm [rad]: convolved
+        with a circular Gaussian beam of that full width at half maximum.  family and param_override as in
+        add_battaglia_profile."""
+        return self._projected_profile("sigma", thetas, Ms, concs, truncate, fwhm,
+                                       self._gas_rowfn(family, param_override), norm)
+
+    def gas_delta_sigma_1h_profiles(self, thetas, Ms, concs=None, family=None, param_override=None, truncate=1.0,
+                                    norm="fit"):
+        """Excess gas surface density Sigmabar_gas(<R) - Sigma_gas(R) [Msun/Mpc^2]; arguments, conventions and shapes of
+        gas_sigma_1h_profiles (no beam)."""
+        return self._projected_profile("excess", thetas, Ms, concs, truncate, None,
+                                       self._gas_rowfn(family, param_override), norm)
+
+    def tau_1h_profiles(self, thetas, Ms, concs=None, family=None, param_override=None, truncate=1.0, fwhm=None):
+        """Thomson optical depth tau(theta) = sigma_T (1 + X_H) / (2 m_p) Sigma_gas of fully ionised gas with hydrogen
+        mass fraction X_H = 0.76 (norm="fit"); dimensionless.  Arguments and shapes of gas_sigma_1h_profiles."""
+        sigma_gas = self.gas_sigma_1h_profiles(thetas, Ms, concs=concs, family=family, param_override=param_override,
+                                               truncate=truncate, norm="fit", fwhm=fwhm)
+        sigmaT = constants.physical_constants["Thomson cross section"][0] / (default_params["parsec"] * 1e6) ** 2
+        m_p = constants.physical_constants["proton mass"][0] / default_params["mSun"]
+        return sigmaT * (1.0 + _X_H) / (2.0 * m_p) * sigma_gas
+
+    def y_1h_profiles(self, thetas, Ms, concs=None, family=None, param_override=None, truncate=1.0, fwhm=None):
+        """Compton-y profile y(theta) = sigma_T / (m_e c^2) int P_e dl of the Battaglia pressure profile (the profile of
+        add_battaglia_pres_profile; hmvec/hmvec.py:906-927, units of 313-316), dimensionless: (nM, ntheta), or
+        (nz, nM, ntheta).  Arguments as gas_sigma_1h_profiles; family and param_override as in
+        add_battaglia_pres_profile."""
+        return self._projected_profile("sigma", thetas, Ms, concs, truncate, fwhm, self._pres_rowfn(family, param_override))
+
+    def _pres_rowfn(self, family, param_override):
+        """Battaglia pressure profile as a member of the family, in Compton-y units: x = r / (xc R200c), eta = beta,
+        amplitude sigma_T / (m_e c^2) A_P times the scale radius."""
+        pp = self._battaglia_pres_pparams(family, param_override)
+        gamma, alpha = float(pp["battaglia_pres_gamma"]), float(pp["battaglia_pres_alpha"])
+        eFrac = 2.0 * (_X_H + 1.0) / (5.0 * _X_H + 3.0)
+        G_newt = constants.G / (default_params["parsec"] * 1e6) ** 3 * default_params["mSun"]
+        sigmaT = constants.physical_constants["Thomson cross section"][0]
+        mElect = constants.physical_constants["electron mass"][0] / default_params["mSun"]
+        fb = self.p["ombh2"] / self.h ** 2.0 / self.omm0
+
+        def rowfn(z, rhoc, m200c, r200c):
+            P0, xc, beta = (_battaglia_fit(m200c, z, *(pp[q + s] for s in ("A0", "alpham", "alphaz")))
+                            for q in ("P0_", "xc_", "beta_"))
+            rp = xc * r200c
+            A_P = eFrac * fb * 200.0 * m200c * G_newt * rhoc / (2.0 * r200c) * P0
+            return rp, alpha, gamma, beta, sigmaT / (mElect * constants.c ** 2) * A_P * rp
+        return rowfn

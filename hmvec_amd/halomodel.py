@@ -9,6 +9,12 @@ State mirrors the reference: ``uk_profiles`` / ``pk_profiles`` map name -> (nz,n
 array, ``hods`` maps name -> dict, plus ``sigma2``, ``nzm``, ``bh``, ``Pzk``.  Reads of
 those return numpy arrays (copied from the device on first access, then cached);
 assigning a numpy array to ``uk_profiles[name]`` uploads it.
+
+This file holds the core: device plumbing, grouped launches, mass function, profiles, HODs and power spectra.  The
+statistics derived from them are mixins the class inherits, each in the module of its section: ``RealspaceMixin``,
+``AngularMixin``, ``SampledMixin``, ``RsdMixin``, ``ClusterLensingMixin``, ``GasProjectionMixin``, ``OnePointMixin``,
+``HodEnsembleMixin``.  A mixin holds no state and reaches the core through ``self`` alone, by the names DESIGN.md lists
+("The facade's sections").
 """
 import ctypes as C
 import itertools
@@ -20,20 +26,15 @@ import numpy as np
 import scipy.constants as constants
 
 from . import _native as nat
-from . import bispectrum as bispec
-from . import cov as covmod
-from . import angular, realspace, spectra, stages
-from . import rsd as rsdmod
-from . import onepoint
-from . import hod_ensemble as hodens
-from .cosmology import Cosmology, _is_shared_product, _trapz, sigma2_kgrid, sigma2_weights
+from . import angular, gasprofiles, hod_ensemble, lensing, onepoint, realspace, rsd, sampled, spectra, stages
+from .cosmology import Cosmology, _is_shared_product, sigma2_kgrid, sigma2_weights
 from .params import battaglia_defaults, default_params
 from .quadrature import gradient_is_uniform, simpson_weights, trapz_weights
 from .functions import FN_BG_INTEGRAND, FN_ST_FSIGMA, FN_TINKER_FSIGMA, fn2d, ngal_from_mthresh, trapz_lastaxis
 from .functions import context as fn_context
-from .utils import vectorized_bisection_search
+from .spectra import _same_lookups  # noqa: F401  (moved there; kept under its name here)
+from .utils import _R_from_M, vectorized_bisection_search
 
-_trapz = getattr(np, "trapezoid", None) or np.trapz
 _EPOCHS = itertools.count(1)      # content tags of the per-model (z,m) arrays (hmg_profile_support_epoch)
 _DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 # A cached pair of spectra: the model's state version it was computed for, P_1h and P_2h on the device and, from a batched
@@ -159,21 +160,9 @@ class HodEntry(MutableMapping):
         return len(set(self.dev) | set(self._vals))
 
 
-def _same_lookups(recs, what):
-    """Refuse a request of `what` that names something the 1-halo and 2-halo lookups resolve differently."""
-    for r in recs:
-        if not r.same:
-            raise ValueError(f"{what}: the 1-halo and 2-halo lookups resolve {r.name!r} differently (it names both an HOD "
-                             f"and a profile)")
-
-
-def _R_from_M(M, rho, delta):
-    """hmvec/hmvec.py:627-628 for the handful of grid radii the constructor needs (host input
-    preparation; the public, device-backed R_from_M lives in functions.py)."""
-    return (3.0 * M / 4.0 / np.pi / delta / rho) ** (1.0 / 3.0)
-
-
-class HaloModel(Cosmology):
+class HaloModel(realspace.RealspaceMixin, angular.AngularMixin, sampled.SampledMixin, rsd.RsdMixin,
+                lensing.ClusterLensingMixin, gasprofiles.GasProjectionMixin, onepoint.OnePointMixin,
+                hod_ensemble.HodEnsembleMixin, Cosmology):
     def __init__(self, zs, ks, ms=None, params={}, mass_function="sheth-torman",
                  halofit=None, mdef="vir", nfw_numeric=False, skip_nfw=False, accuracy="medium",
                  engine="camb", *, device=0, ctx=None, background=None):
@@ -1086,308 +1075,7 @@ class HaloModel(Cosmology):
         print("Two-halo consistency1: ", c1, i1)
         print("Two-halo consistency2: ", c2, i2)
 
-    # ------------------------------------------------------- configuration-space statistics (DESIGN.md sections 13, 14)
-    # xi(r), w_p(r_p), Sigma(R) and Delta Sigma(R) of the model's spectra: the rows stay on the device from the mass
-    # integrals to the transform (realspace.py); only the (nz, nr) results cross to the host.
-    _XI_TERMS = ("total", "1h", "2h")
-
-    def _xi_request(self, rs, term, what="rs"):
-        """The checked radii (or angles: `what`) of a transform request (everything that can be refused is, before any
-        launch)."""
-        if term not in self._XI_TERMS:
-            raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
-        realspace.check_ks(self.ks)
-        return realspace.check_rs(rs, what)
-
-    def _xi_rows(self, d1, d2, term):
-        """The device rows a term transforms; "total" is the device sum get_power brings to the host."""
-        return d1 if term == "1h" else d2 if term == "2h" else self._sum_device(d1, d2)
-
-    def _transform_rows(self, rows, nrows, rs, orders, zsum=None):
-        """The transforms of nrows device rows at the radii rs as a tuple of (nrows, nr) host arrays: (xi,) for
-        orders=None, else (W_n for n in orders), one launch either way.  With zsum = (chis, zw) rs are angles, the row
-        at z is transformed at chis[z] rs and the rows of a block are summed with the (nw, nz) weights zw (section
-        22): a tuple of (nrows / nz, nw, nr) arrays from one transform launch and one contraction."""
-        if orders is None:
-            return (realspace.transform_rows(self._ctx(), self._d_ks(), rows, nrows, self._nk, rs),)
-        if zsum is not None:
-            return angular.angular_rows(self._ctx(), self._d_ks(), rows, nrows // self._nz, self._nz, self._nk, rs,
-                                        *zsum, orders)
-        return realspace.hankel_rows(self._ctx(), self._d_ks(), rows, nrows, self._nk, rs, orders)
-
-    def _realspace_pair(self, rs, name, name2, term, orders, zsum=None):
-        """What get_xi, the projected and the angular statistics of one pair share: the request's checks, the tSZ
-        notice, the pair's cached device spectra and one transform launch.  A tuple of (nz, nr) arrays, with zsum of
-        (1, nw, nr) arrays (see _transform_rows)."""
-        rs = self._xi_request(rs, term, "rs" if zsum is None else "thetas")
-        ra, rb = self._resolve(name, name if name2 is None else name2)
-        if term != "1h":          # (get_power and get_power_2halo print it, get_power_1halo does not)
-            self._tsz_notice(ra, rb)
-        if rs.size == 0:
-            shape = (self._nz, 0) if zsum is None else (1, zsum[1].shape[0], 0)
-            return tuple(np.empty(shape) for _ in (orders or (None,)))
-        ent = self._power_cached(ra, rb)
-        return self._transform_rows(self._xi_rows(ent.p1h, ent.p2h, term), self._nz, rs, orders, zsum)
-
-    def _realspace_all(self, pairs, rs, term, orders, zsum=None):
-        """The same for several pairs: their spectra from one pass over the profile tensors (get_power_all's) into one
-        block and all of them through ONE transform launch of len(pairs) * nz rows.  (pairs, tuple of (n, nz, nr)
-        arrays, with zsum of (n, nw, nr) arrays); every [i] is bit for bit what _realspace_pair gives for pairs[i]."""
-        rs = self._xi_request(rs, term, "rs" if zsum is None else "thetas")
-        pairs = [tuple(p) for p in pairs]
-        rpairs = self._resolve_pairs(pairs)
-        if term != "1h":
-            self._tsz_notice(*dict.fromkeys(r for rp in rpairs for r in rp))
-        n, nz, nk = len(pairs), self._nz, self._nk
-        if rs.size == 0 or n == 0:
-            shape = (n, nz, rs.size) if zsum is None else (n, zsum[1].shape[0], rs.size)
-            return pairs, tuple(np.empty(shape) for _ in (orders or (None,)))
-        ctx = self._ctx()
-        blk = ctx.empty((2 * n, nz, nk))
-        o1 = [blk.view(i * nz * nk, (nz, nk)) for i in range(n)]
-        o2 = [blk.view((n + i) * nz * nk, (nz, nk)) for i in range(n)]
-        if spectra.batchable(spectra.pair_plan(rpairs)[0], rpairs):
-            self._power_batch(rpairs, o1, o2)
-        else:
-            # one pair the batch cannot express sends all of them to the one-pair kernel there (another summation
-            # order): take each pair's spectra as the one-pair call does, so that the entries keep its bits
-            for (ra, rb), d1, d2 in zip(rpairs, o1, o2):
-                ent = self._power_cached(ra, rb)
-                ctx.call("hmg_memcpy_d2d", d1.ptr, ent.p1h.ptr, d1.nbytes)
-                ctx.call("hmg_memcpy_d2d", d2.ptr, ent.p2h.ptr, d2.nbytes)
-        rows = self._xi_rows(blk.view(0, (n * nz, nk)), blk.view(n * nz * nk, (n * nz, nk)), term)
-        outs = self._transform_rows(rows, n * nz, rs, orders, zsum)
-        return pairs, tuple(o.reshape(n, -1, rs.size) for o in outs)
-
-    def get_xi(self, rs, name="nfw", name2=None, term="total"):
-        """Correlation function xi(z, r), shape (nz, nr), of the spectrum of (name, name2) - of P_1h + P_2h
-        (term="total"), P_1h ("1h") or P_2h ("2h") - by the exact transform of realspace.xi_from_power: bit for bit
-        xi_from_power(ks, get_power(name, name2), rs) and its get_power_1halo / get_power_2halo counterparts."""
-        return self._realspace_pair(rs, name, name2, term, None)[0]
-
-    def get_xi_all(self, pairs, rs, term="total"):
-        """{(name, name2): xi(z, r)} for several pairs: their spectra from one pass over the profile tensors
-        (get_power_all's) and all of them through ONE transform launch of len(pairs) * nz rows.  Each entry is bit for
-        bit get_xi of that pair."""
-        pairs, (xi,) = self._realspace_all(pairs, rs, term, None)
-        return {p: xi[i] for i, p in enumerate(pairs)}
-
-    def get_wp(self, rps, name, name2=None, term="total"):
-        """Projected correlation function w_p(z, r_p), shape (nz, nr), of the spectrum of (name, name2) - term as for
-        get_xi - integrated along the whole line of sight (pi_max -> infinity): W_0 of
-        realspace.projected_from_power, bit for bit projected_from_power(ks, get_power(name, name2), rps).  r_p is
-        comoving, in the inverse units of ks; w_p has the units of P times those of ks squared (a length for a
-        three-dimensional spectrum)."""
-        return self._realspace_pair(rps, name, name2, term, (0,))[0]
-
-    def get_surface_density(self, Rs, name, name2=None, term="total"):
-        """Surface density Sigma(z, R) = rho_m0 W_0(R), shape (nz, nr), of the spectrum of (name, name2), e.g. P_gm -
-        term as for get_xi; W_0 of realspace.projected_from_power.  Comoving units: rho_m0 = rho_matter_z(0) is the
-        comoving matter density, R a comoving transverse distance in the inverse units of ks, Sigma a mass per comoving
-        area with the mean density's contribution left out (the line-of-sight integral of rho_m0 xi).  The physical
-        convention of sigma_2h_profiles (physical radius R_phys = R / (1 + z), mass per
-        physical area, at the angle theta = R_phys / d_A(z) = R / chi(z)) is
-        Sigma_phys(R_phys) = (1 + z)^2 Sigma(R_phys (1 + z))."""
-        w0 = self._realspace_pair(Rs, name, name2, term, (0,))[0]          # (the request is checked first)
-        return self._rho_m0() * w0
-
-    def get_excess_surface_density(self, Rs, name, name2=None, term="total"):
-        """Excess surface density Delta Sigma(z, R) = mean Sigma(< R) - Sigma(R) = rho_m0 W_2(R), shape (nz, nr), of
-        the spectrum of (name, name2); units and the conversion to the physical convention of
-        delta_sigma_2h_profiles as for get_surface_density: Delta Sigma_phys(R_phys) = (1 + z)^2 Delta Sigma(R_phys (1 + z))."""
-        w2 = self._realspace_pair(Rs, name, name2, term, (2,))[0]
-        return self._rho_m0() * w2
-
-    def get_wp_all(self, pairs, rps, term="total"):
-        """{(name, name2): w_p(z, r_p)} for several pairs, spectra and launches as for get_xi_all.  Each entry is bit
-        for bit get_wp of that pair."""
-        pairs, (wp,) = self._realspace_all(pairs, rps, term, (0,))
-        return {p: wp[i] for i, p in enumerate(pairs)}
-
-    def get_surface_density_all(self, pairs, Rs, term="total"):
-        """{(name, name2): (Sigma(z, R), Delta Sigma(z, R))} for several pairs, spectra as for get_xi_all and both
-        statistics from ONE transform launch.  Each entry is bit for bit get_surface_density and
-        get_excess_surface_density of that pair."""
-        pairs, (w0, w2) = self._realspace_all(pairs, Rs, term, (0, 2))
-        rho = self._rho_m0()
-        return {p: (rho * w0[i], rho * w2[i]) for i, p in enumerate(pairs)}
-
-    # ------------------------------------------------------------------ angular correlation functions (DESIGN.md section 22)
-    # w(theta), gamma_t(theta), xi+-(theta): the rows at the model's redshifts are transformed at chi(z) theta and summed
-    # over z with the windows' weights on the device (angular.py); only the (nw, ntheta) results cross to the host.
-    def _angular_request(self, zweights, order, term):
-        """(zsum, orders, stacked) of an angular request: the distances of self.zs, the checked (nw, nz) weights
-        (None: the z measure alone, both windows 1) and orders, and whether the weights came with the nw axis."""
-        if term not in self._XI_TERMS:
-            raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
-        orders = angular.check_order(order)
-        nz = np.size(self.zs)
-        if zweights is None:
-            zweights = self.angular_weights(self.zs, 1.0, 1.0)
-        zw, stacked = angular.check_zweights(zweights, nz)
-        chis = angular.check_chis(np.reshape(self.comoving_radial_distance(self.zs), -1), nz)
-        return (chis, zw), orders, stacked
-
-    def get_angular(self, thetas, name, name2=None, zweights=None, order=0, term="total"):
-        """Angular correlation function zeta_order(theta) = sum_z zweights[z] W_order^(z)(chi(z) theta) of the spectrum
-        of (name, name2) - term as for get_xi - on the model's redshifts self.zs, chi = comoving_radial_distance(zs)
-        (every z must be positive): bit for bit angular.angular_from_power(ks, get_power(name, name2), thetas, chi,
-        zweights, order).  thetas in radians.  zweights: (nz,) or (nw, nz), the z measure times the two windows
-        (angular_weights(zs, W1, W2)); None is the measure alone.  order: 0, 2, 4 or a strictly increasing tuple of
-        them.  Returns (ntheta,), or (nw, ntheta) for two-dimensional weights; a tuple of them for a tuple of
-        orders."""
-        zsum, orders, stacked = self._angular_request(zweights, order, term)
-        outs = self._realspace_pair(thetas, name, name2, term, orders, zsum)
-        outs = tuple(o[0] if stacked else o[0, 0] for o in outs)
-        return outs if isinstance(order, (tuple, list)) else outs[0]
-
-    def _dndz_window(self, dndz, what):
-        """dndz / int dndz dz on self.zs (C_gg's convention); None is a uniform distribution over the range of zs."""
-        zs = np.reshape(self.zs, -1)
-        if zs.size < 2:
-            raise ValueError(f"{what} needs at least two redshifts in the model")
-        dndz = np.ones(zs.size) if dndz is None else np.asarray(dndz, dtype=np.float64)
-        if dndz.shape != zs.shape or not np.all(np.isfinite(dndz)):
-            raise ValueError(f"{what} must be a finite vector of {zs.size} values on the model's redshifts")
-        norm = _trapz(dndz, zs)
-        if not norm > 0:
-            raise ValueError(f"{what} must have a positive integral over the model's redshifts")
-        return dndz / norm
-
-    def _source_window(self, zsource, sdndz, what):
-        """lensing_window on self.zs of a source plane (zsource a scalar) or of sources sdndz on the grid zsource."""
-        if zsource is None:
-            raise ValueError(f"{what} is required: a source redshift, or the grid of a source distribution")
-        zsource = np.asarray(zsource, dtype=np.float64).reshape(-1)
-        if (zsource.size == 1) != (sdndz is None) or (sdndz is not None and np.shape(sdndz) != zsource.shape):
-            raise ValueError(f"{what}: one source redshift without a distribution, or a grid with its distribution")
-        return self.lensing_window(np.reshape(self.zs, -1), zsource, sdndz)
-
-    def get_w_theta(self, thetas, name, name2=None, dndz=None, dndz2=None, term="total"):
-        """Angular clustering w(theta), shape (ntheta,): order 0 with the windows dndz / int dndz dz of the two samples
-        on self.zs (C_gg's convention; dndz None: uniform over the range of zs, dndz2 None: the first sample's) -
-        bit for bit get_angular(thetas, name, name2, angular_weights(zs, W1, W2), 0, term)."""
-        if term not in self._XI_TERMS:
-            raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
-        W1 = self._dndz_window(dndz, "dndz")
-        W2 = W1 if dndz2 is None else self._dndz_window(dndz2, "dndz2")
-        return self.get_angular(thetas, name, name2, self.angular_weights(self.zs, W1, W2), 0, term)
-
-    def get_gamma_t(self, thetas, name, name2="nfw", dndz=None, zsource=None, sdndz=None, term="total"):
-        """Tangential shear gamma_t(theta), shape (ntheta,), of the lenses `name` (window dndz / int dndz dz as for
-        get_w_theta) about sources at zsource (a single redshift, or a grid with the distribution sdndz: the arguments
-        of lensing_window): order 2 of the lens-matter spectrum - bit for bit
-        get_angular(thetas, name, name2, angular_weights(zs, W_lens, lensing_window(zs, zsource, sdndz)), 2, term)."""
-        if term not in self._XI_TERMS:
-            raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
-        W1 = self._dndz_window(dndz, "dndz")
-        W2 = self._source_window(zsource, sdndz, "zsource")
-        return self.get_angular(thetas, name, name2, self.angular_weights(self.zs, W1, W2), 2, term)
-
-    def get_xi_pm(self, thetas, name="nfw", name2=None, zsource=None, sdndz=None, zsource2=None, sdndz2=None,
-                  term="total"):
-        """Shear correlation functions (xi+(theta), xi-(theta)), each (ntheta,), of sources at zsource (and zsource2,
-        default the same; arguments as for get_gamma_t): orders 0 and 4 of the matter spectrum from ONE launch - bit
-        for bit get_angular(thetas, name, name2, angular_weights(zs, W_kappa1, W_kappa2), (0, 4), term)."""
-        if term not in self._XI_TERMS:
-            raise ValueError(f"term must be one of {self._XI_TERMS}, got {term!r}")
-        W1 = self._source_window(zsource, sdndz, "zsource")
-        W2 = W1 if zsource2 is None else self._source_window(zsource2, sdndz2, "zsource2")
-        return self.get_angular(thetas, name, name2, self.angular_weights(self.zs, W1, W2), (0, 4), term)
-
-    def get_angular_all(self, pairs, thetas, zweights, order=0, term="total"):
-        """{(name, name2): zeta_order(theta)} for several pairs: their spectra from one pass over the profile tensors
-        (get_power_all's), ONE transform launch of len(pairs) * nz rows and one contraction over z.  zweights: (nz,)
-        or (nw, nz) shared by all pairs, or a dict {pair: weights}.  Each entry is bit for bit get_angular of that
-        pair with its weights."""
-        pairs = [tuple(p) for p in pairs]
-        if isinstance(zweights, dict):
-            missing = [p for p in pairs if p not in zweights]
-            if missing:
-                raise ValueError(f"zweights has no entry for {missing}")
-            per = [angular.check_zweights(zweights[p], np.size(self.zs)) for p in pairs]
-        else:
-            per = [angular.check_zweights(zweights, np.size(self.zs))] * len(pairs)
-        # every pair's rows of weights go stacked into the one contraction and the pair keeps its own: an output's
-        # chain reads its row of weights alone, so its bits are those of the pair's own call
-        shared = not isinstance(zweights, dict)
-        stack = None if not per else per[0][0] if shared else np.concatenate([zw for zw, _ in per])
-        zsum, orders, _ = self._angular_request(stack, order, term)
-        pairs, outs = self._realspace_all(pairs, thetas, term, orders, zsum)
-        res, lo = {}, 0
-        for i, (p, (zw, stacked)) in enumerate(zip(pairs, per)):
-            ent = tuple(o[i, lo:lo + zw.shape[0]] if stacked else o[i, lo] for o in outs)
-            res[p] = ent if isinstance(order, (tuple, list)) else ent[0]
-            lo += 0 if shared else zw.shape[0]
-        return res
-
-    # ------------------------------------------------------------------ 1-halo trispectrum (DESIGN.md section 15)
-    # T[z,i,j] = sum_m wm nzm s_ab[z,m,i] s_cd[z,m,j]: the mass integral of get_power_1halo with one more free index,
-    # contracted on the device over the resident tensors (hmg_trispectrum_1h); only (nz, n, n) or (n, n) results cross.
-    TRISPECTRUM_MAX_SAMPLES = 1024
-
-    def _sample_tables(self, kindex, idx, frac, scale, damping, max_samples, what):
-        """The checked (nz, n) sample tables of a request of `what` ("the trispectrum", ...), which takes at most
-        max_samples per redshift: int32 idx, frac, scale (damping=True: folded in).  Everything that can be refused is,
-        here, before any launch."""
-        nz, nk = self._nz, self._nk
-        if idx is None:
-            if frac is not None:
-                raise ValueError("frac needs idx")
-            kindex = np.arange(nk) if kindex is None else np.asarray(kindex)
-            if kindex.ndim != 1 or not np.issubdtype(kindex.dtype, np.integer):
-                raise ValueError("kindex must be a one-dimensional integer array of indices into ks")
-            idx = np.broadcast_to(kindex[None, :], (nz, kindex.size))
-        else:
-            if kindex is not None:
-                raise ValueError("give kindex or the idx / frac tables, not both")
-            idx = np.asarray(idx)
-            if not np.issubdtype(idx.dtype, np.integer):
-                raise ValueError("idx must be an integer array")
-            if idx.ndim == 1:
-                idx = np.broadcast_to(idx[None, :], (nz, idx.size))
-            if idx.ndim != 2 or idx.shape[0] != nz:
-                raise ValueError(f"idx must have shape (n,) or (nz, n) with nz = {nz}, got {idx.shape}")
-        n = idx.shape[1]
-        if n < 1:
-            raise ValueError(f"kindex / idx is empty: {what} needs at least one sample")
-        if n > max_samples:
-            raise ValueError(f"kindex / idx asks for {n} samples per redshift; {what} takes at most {max_samples}: pass "
-                             f"a shorter kindex")
-        if idx.min() < 0 or idx.max() > nk - 1:
-            raise ValueError(f"kindex / idx must lie in 0 .. nk - 1 = {nk - 1}, got {idx.min()} .. {idx.max()}")
-        frac = np.zeros((nz, n)) if frac is None else np.broadcast_to(np.asarray(frac, dtype=np.float64), (nz, n))
-        if not np.all((frac >= 0.0) & (frac <= 1.0)):
-            raise ValueError("frac must lie in [0, 1]")
-        if np.any((idx == nk - 1) & (frac != 0.0)):
-            raise ValueError("idx = nk - 1 needs frac = 0 (there is no node to its right)")
-        scale = np.ones((nz, n)) if scale is None else np.broadcast_to(np.asarray(scale, dtype=np.float64), (nz, n))
-        if not np.all(np.isfinite(scale)):
-            raise ValueError("scale must be finite")
-        if damping:
-            ks = self.ks
-            k = np.where(frac == 0.0, ks[idx], (1.0 - frac) * ks[idx] + frac * ks[np.minimum(idx + 1, nk - 1)])
-            scale = scale * (1.0 - np.exp(-(k / self.p["kstar_damping"]) ** 2.0))
-        return (np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(frac, dtype=np.float64),
-                np.ascontiguousarray(scale, dtype=np.float64))
-
-    def _trispectrum_tables(self, kindex, idx, frac, scale, damping):
-        """_sample_tables of a trispectrum request (the result has nz * n * n entries: at most 1024 samples)."""
-        return self._sample_tables(kindex, idx, frac, scale, damping, self.TRISPECTRUM_MAX_SAMPLES, "the trispectrum")
-
-    # what the requests of sections 15, 16, 17 and 19 share
-    def _zweights(self, zweights):
-        zweights = np.ascontiguousarray(zweights, dtype=np.float64).reshape(-1)
-        if zweights.size != self._nz:
-            raise ValueError(f"zweights must have one entry per redshift ({self._nz}), got {zweights.size}")
-        return zweights
-
-    @staticmethod
-    def _upload_tables(ctx, tables):
-        """(d_idx, d_frac, d_scale).  They may go back to the free list as soon as the call that reads them is enqueued:
-        whatever reuses them is enqueued behind it."""
-        return ctx.upload_int32(tables[0]), ctx.upload(tables[1]), ctx.upload(tables[2])
-
+    # ------------------------------------------------------------------ the model block of the mixins' native calls
     _MODEL_BLOCK = {"d_nzm": lambda h: h._d_nzm.ptr, "d_bh": lambda h: h._d_bh.ptr, "d_ms": lambda h: h._d_ms().ptr,
                     "d_wm": lambda h: h._d_wm().ptr, "d_ks": lambda h: h._d_ks().ptr, "d_Pzk": lambda h: h._d_Pzk().ptr,
                     "rho_m0": lambda h: h._rho_m0()}
@@ -1396,862 +1084,6 @@ class HaloModel(Cosmology):
         """The model block of a native call, by the header's parameter names: those of d_nzm, d_bh, d_ms, d_wm, d_ks,
         d_Pzk, rho_m0 that `entry` declares, in its order."""
         return {n: self._MODEL_BLOCK[n](self) for n in nat.PARAMS[entry] if n in self._MODEL_BLOCK}
-
-    def trispectrum_device(self, name, name2=None, name3=None, name4=None, kindex=None, damping=True, idx=None,
-                           frac=None, scale=None, zweights=None, per_z=True):
-        """(T, Tz) on the device: T (nz, n, n) the 1-halo trispectrum of the spectra (name, name2) and (name3, name4) -
-        per_z=False: None - and Tz (n, n) = sum_z zweights[z] T[z], in z order, if zweights (nz,) is given, else None.
-
-        Samples: kindex (nodes of ks, the same for every z; default all of them), or tables idx / frac (n,) or (nz, n) -
-        sample i of redshift z is the square term interpolated linearly between the nodes idx and idx + 1 at the
-        fraction frac (default 0; idx = nk - 1 needs frac = 0), times scale (default 1).  damping=True multiplies scale
-        by 1 - exp(-(k / kstar)^2) at the sample's wavenumber, as get_power_1halo damps P_1h.  At most 1024 samples.
-        name3 / name4 default to the first pair; the square terms are get_power_1halo's, first-name-only rules
-        included."""
-        name2 = name if name2 is None else name2
-        name3, name4 = (name if name3 is None else name3), (name2 if name4 is None else name4)
-        recs = self._resolve(name, name2, name3, name4)
-        tables = self._trispectrum_tables(kindex, idx, frac, scale, damping)
-        if zweights is not None:
-            zweights = self._zweights(zweights)
-        elif not per_z:
-            raise ValueError("nothing asked for: per_z=False needs zweights")
-        nz, nm, nk, n = self._nz, self._nm, self._nk, tables[0].shape[1]
-        ctx = self._main(needs_aux=True)
-        # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
-        tr = [self._tracer(r, 1) for r in recs]
-        d_idx, d_frac, d_scale = self._upload_tables(ctx, tables)
-        d_g = ctx.upload(zweights) if zweights is not None else None
-        T = ctx.empty((nz, n, n)) if per_z else None
-        Tz = ctx.empty((n, n)) if zweights is not None else None
-        ha, hb, hc, hd = (C.byref(t) for t in tr)
-        ctx.call("hmg_trispectrum_1h", nz=nz, nm=nm, nk=nk, n=n, h_a=ha, h_b=hb, h_c=hc, h_d=hd,
-                 **self._model_block("hmg_trispectrum_1h"), d_idx=d_idx.ptr, d_frac=d_frac.ptr, d_scale=d_scale.ptr,
-                 d_zweights=nat.ptr(d_g), d_T=nat.ptr(T), d_Tz=nat.ptr(Tz))
-        self._sync_point()
-        return T, Tz
-
-    def get_trispectrum_1halo(self, name, name2=None, name3=None, name4=None, kindex=None, damping=True):
-        """1-halo trispectrum T(z; k_i, k_j) = int dm n(z,m) S_ab(z,m,k_i) S_cd(z,m,k_j), shape (nz, n, n), of the spectra
-        (name, name2) and (name3, name4; default: the first pair) at the nodes ks[kindex] (default: all; at most 1024).
-        S is the square term get_power_1halo integrates, so without damping T[z,i,i] of a pair with itself is the mass
-        integral of its square.  damping=True (default) multiplies by D(k_i) D(k_j), D = 1 - exp(-(k/kstar)^2), which
-        makes T consistent with the damped P_1h the model returns; damping=False leaves it out."""
-        return self.trispectrum_device(name, name2, name3, name4, kindex=kindex, damping=damping)[0].numpy()
-
-    # ------------------------------------------------------------------ bispectrum of three tracers (DESIGN.md section 16)
-    # B1h, B2h, B3h at triangles of sample wavenumbers, contracted on the device over the resident tensors
-    # (hmg_bispectrum); only (3, nz, nt) or (3, nt) results cross.  The host side of the contract is bispectrum.py.
-    def bispectrum_device(self, name, name2=None, name3=None, triangles=None, kindex=None, damping=True, idx=None,
-                          frac=None, scale=None, zweights=None, per_z=True):
-        """(B, Bz) on the device: B (3, nz, nt) the 1-halo, 2-halo and 3-halo terms of the bispectrum of the tracers
-        (name, name2, name3) - per_z=False: None - and Bz (3, nt) = sum_z zweights[z] B[:, z], in z order, if zweights
-        (nz,) is given, else None.  Missing names default to the first.
-
-        Samples as for trispectrum_device (kindex, or idx / frac / scale tables; at most 256), except that damping is
-        not folded into scale: the factors D = 1 - exp(-(k / kstar)^2) multiply the 1-halo term and the 1-halo factor of
-        each 2-halo term.  triangles: (nt, 3) integer array of sample indices, the same for every redshift - leg
-        `name` sits at column 0, name2 at 1, name3 at 2; default: all i <= j <= l that close at every redshift; at most
-        2^20.  A triangle must close at every redshift.  At most one of the names may be an HOD."""
-        return self._bispectrum(name, name2, name3, triangles, kindex, damping, idx, frac, scale, zweights, per_z)[:2]
-
-    def _bispectrum(self, name, name2, name3, triangles, kindex, damping, idx, frac, scale, zweights, per_z, want_J=False):
-        """(B, Bz, J) of bispectrum_device; J (3, nz, n), the 2-halo bracket (I + b) - C of each leg at the samples, if
-        want_J, else None.  Every refusal happens here on the host, before any launch."""
-        name2 = name if name2 is None else name2
-        name3 = name if name3 is None else name3
-        triple = (name, name2, name3)
-        recs = self._resolve(*triple)
-        if sum(r.kind1 == "h" for r in recs) >= 2:
-            raise NotImplementedError(
-                f"bispectrum of {triple!r}: two or more HOD names in one triple need the third factorial moments of the "
-                f"HOD for the 1-halo term, which the model does not carry (the product of two galaxy weights would "
-                f"count self-pairs)")
-        _same_lookups(recs, f"bispectrum of {triple!r}")
-        tables = self._sample_tables(kindex, idx, frac, scale, False, bispec.MAX_SAMPLES, "the bispectrum")
-        n = tables[0].shape[1]
-        tri = bispec.check_triangles(triangles, bispec.sample_wavenumbers(self.ks, tables[0], tables[1]), self.zs)
-        if zweights is not None:
-            zweights = self._zweights(zweights)
-        elif not per_z and not want_J:
-            raise ValueError("nothing asked for: per_z=False needs zweights")
-        nz, nm, nk, nt = self._nz, self._nm, self._nk, tri.shape[0]
-        ctx = self._main(needs_aux=True)
-        # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
-        tr = [self._tracer(r, 1) for r in recs]
-        d_idx, d_frac, d_scale = self._upload_tables(ctx, tables)
-        d_tri = ctx.upload_int32(tri)
-        d_g = ctx.upload(zweights) if zweights is not None else None
-        B = ctx.empty((3, nz, nt)) if per_z else None
-        Bz = ctx.empty((3, nt)) if zweights is not None else None
-        J = ctx.empty((3, nz, n)) if want_J else None
-        ha, hb, hc = (C.byref(t) for t in tr)
-        ctx.call("hmg_bispectrum", nz=nz, nm=nm, nk=nk, n=n, nt=nt, h_a=ha, h_b=hb, h_c=hc,
-                 **self._model_block("hmg_bispectrum"), kstar=float(self.p["kstar_damping"]) if damping else 0.0,
-                 d_idx=d_idx.ptr, d_frac=d_frac.ptr, d_scale=d_scale.ptr, d_tri=d_tri.ptr, d_zweights=nat.ptr(d_g),
-                 d_B=nat.ptr(B), d_Bz=nat.ptr(Bz), d_J=nat.ptr(J))
-        self._sync_point()
-        return B, Bz, J
-
-    def get_bispectrum(self, name, name2=None, name3=None, triangles=None, kindex=None, term="total", damping=True):
-        """The halo-model bispectrum B(z; k_1, k_2, k_3) of three tracers (missing names: the first), shape (nz, nt), at
-        triangles of the nodes ks[kindex] (default: all nodes; at most 256) - triangles (nt, 3) indexes kindex, leg
-        `name` at column 0; default: all i <= j <= l that close.  term: "1h", "2h", "3h" or "total" (their sum in that
-        order).  Linear halo bias only (no b_2 term); the 3-halo term uses the tree-level matter bispectrum of the
-        model's P_lin.  damping as in get_power_1halo, per leg."""
-        if term not in bispec.TERMS:
-            raise ValueError(f"term must be one of {bispec.TERMS}, got {term!r}")
-        B = self.bispectrum_device(name, name2, name3, triangles=triangles, kindex=kindex, damping=damping)[0]
-        return bispec.pick_term(B.numpy(), term)
-
-    # ------------------------------------------------------------------ response and super-sample covariance (section 17)
-    # R_ab = dP_ab / d delta_b at sample wavenumbers for several pairs at once (hmg_response) and the rank-nz contraction
-    # Cov = sum_z g r r of such responses (hmg_ssc); only (np, nz, n) and (np n)^2 results cross.  The host side of the
-    # contract - sigma_b, the Limber tables, the slope table - is cov.py.
-    RESPONSE_MAX_PAIRS = 16
-
-    def _response_request(self, pairs, kindex, idx, frac, scale):
-        """(pairs as names, records, tables) of a response request.  Every refusal happens here on the host, before any
-        launch."""
-        pairs = [(a, a if b is None else b) for a, b in ([p, None] if isinstance(p, str) else p for p in pairs)]
-        if len(pairs) < 1:
-            raise ValueError("pairs is empty: the response needs at least one (name, name2)")
-        if len(pairs) > self.RESPONSE_MAX_PAIRS:
-            raise ValueError(f"{len(pairs)} pairs; at most {self.RESPONSE_MAX_PAIRS} are taken in one call")
-        recs = self._resolve(*[nm_ for p in pairs for nm_ in p])
-        _same_lookups(recs, f"response of {pairs!r}")
-        return pairs, recs, self._sample_tables(kindex, idx, frac, scale, False, bispec.MAX_SAMPLES, "the response")
-
-    def _response_launch(self, recs, tables, damping, parts):
-        nz, nm, nk, n, npairs = self._nz, self._nm, self._nk, tables[0].shape[1], len(recs) // 2
-        ctx = self._main(needs_aux=True)
-        # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
-        tr = (nat.Tracer * len(recs))(*[self._tracer(r, 1) for r in recs])
-        d_idx, d_frac, d_scale = self._upload_tables(ctx, tables)
-        d_dlnP = self._dev("dlnP", lambda: covmod.dlnp_table(self.ks, self.Pzk))
-        R = ctx.empty((npairs, nz, n))
-        P = ctx.empty((3, npairs, nz, n)) if parts else None
-        ctx.call("hmg_response", nz=nz, nm=nm, nk=nk, n=n, np=npairs, h_pairs=tr, **self._model_block("hmg_response"),
-                 d_dlnP=d_dlnP.ptr, kstar=float(self.p["kstar_damping"]) if damping else 0.0, d_idx=d_idx.ptr,
-                 d_frac=d_frac.ptr, d_scale=d_scale.ptr, d_R=R.ptr, d_parts=nat.ptr(P))
-        self._sync_point()
-        return R, P
-
-    def response_device(self, pairs, kindex=None, damping=True, idx=None, frac=None, scale=None, parts=False):
-        """R on the device, (np, nz, n): the response dP_ab / d delta_b of the halo-model spectrum of each pair (a, b) of
-        `pairs` (1 to 16; a lone name or (a, None) is (a, a)) to a long-wavelength density mode,
-
-            R = scale [ (47/21 - n_s/3) P2h + D I1 - (beta_a + beta_b) (P2h + D A1) ],
-
-        A1 the undamped 1-halo integral of get_power_1halo (first-name-only rules included), I1 the same integral weighted
-        with the halo bias, P2h = P_lin J_a J_b the 2-halo term of get_power_2halo, n_s the logarithmic slope of P_lin,
-        D the damping factor of get_power_1halo (damping=False: 1) and beta the mean galaxy bias of an HOD name (0 of a
-        matter or pressure name: a galaxy overdensity is defined against the local mean density).  The growth and
-        dilation factor takes the slope of P_lin only, not of the 2-halo brackets - the usual halo-model approximation.
-        Samples as for bispectrum_device (kindex, or idx / frac / scale tables; at most 256).  parts=True: (R, parts),
-        parts (3, np, nz, n) = (A1, I1, P2h), unscaled and undamped.  Two HOD names in one pair are allowed."""
-        _, recs, tables = self._response_request(pairs, kindex, idx, frac, scale)
-        R, P = self._response_launch(recs, tables, damping, parts)
-        return (R, P) if parts else R
-
-    def get_power_response(self, name, name2=None, kindex=None, damping=True):
-        """dP_ab(z, k) / d delta_b of the pair (name, name2; default name) at the nodes ks[kindex] (default: all, at most
-        256), shape (nz, n); see response_device."""
-        return self.response_device([(name, name2)], kindex=kindex, damping=damping).numpy()[0]
-
-    def ssc_device(self, pairs, zweights, zscale=None, kindex=None, damping=True, idx=None, frac=None, scale=None):
-        """Cov on the device, (np, n, np, n): Cov[p,i,q,j] = sum_z zweights[z] r[p,z,i] r[q,z,j], in z order, of the
-        responses r[p,z,s] = zscale[p][z] R_p[z,s] (response_device's; zscale (np, nz), default 1).  Each term is formed
-        as fma(r r, g, acc) with the weight on neither side: Cov[p,i,q,j] has the bits of Cov[q,j,p,i]."""
-        pairs, recs, tables = self._response_request(pairs, kindex, idx, frac, scale)
-        nz, n, npairs = self._nz, tables[0].shape[1], len(pairs)
-        zweights = np.ascontiguousarray(zweights, dtype=np.float64)
-        if zweights.shape != (nz,):
-            raise ValueError(f"zweights must have one entry per redshift ({nz}), got shape {zweights.shape}")
-        if zscale is not None:
-            zscale = np.ascontiguousarray(zscale, dtype=np.float64)
-            if zscale.shape != (npairs, nz):
-                raise ValueError(f"zscale must have shape (np, nz) = {(npairs, nz)}, got {zscale.shape}")
-        R, _ = self._response_launch(recs, tables, damping, False)
-        return self._ssc_launch(R, zweights, zscale)
-
-    def _ssc_launch(self, R, zweights, zscale):
-        npairs, nz, n = R.shape
-        ctx = self._main()
-        d_g = ctx.upload(zweights)
-        d_zs = ctx.upload(zscale) if zscale is not None else None
-        cov_ = ctx.empty((npairs, n, npairs, n))
-        ctx.call("hmg_ssc", nz, n, npairs, R.ptr, nat.ptr(d_zs), d_g.ptr, cov_.ptr)
-        self._sync_point()
-        return cov_
-
-    # ------------------------------------------------------------------ redshift-space spectra (DESIGN.md section 19)
-    # Wedges P^s(k, mu) and multipoles P_0, P_2, P_4 of one pair at nodes of the k grid (hmg_rsd_wedges,
-    # hmg_rsd_multipoles): a mass integral with a Gaussian of the bin's line-of-sight dispersion inside it.  The host side
-    # of the contract - the default dispersion, the rule in mu, the checks - is rsd.py.
-    def _rsd_request(self, name, name2, kindex, sigma_s, f, alphas, damping):
-        """(records, uploaded tables, alphas) of a redshift-space request.  Every refusal happens here on the host,
-        before any launch."""
-        pair = (name, name if name2 is None else name2)
-        recs = self._resolve(*pair)
-        for r in recs:
-            if r.kind1 == "p" or r.kind2 == "p":
-                raise ValueError(f"redshift-space spectrum of {pair!r}: {r.name!r} is a pressure profile, which has no "
-                                 f"line-of-sight velocity in this model")
-        _same_lookups(recs, f"redshift-space spectrum of {pair!r}")
-        nz, nm, nk = self._nz, self._nm, self._nk
-        kindex = rsdmod.check_kindex(kindex, nk)
-        sigma_s = rsdmod.check_sigma(rsdmod.virial_dispersion(self) if sigma_s is None else sigma_s, nz, nm)
-        f = rsdmod.check_f(self.get_growth_rate_f(self.zs) if f is None else f, nz)
-        alphas = rsdmod.check_alphas(alphas)
-        damp = bispec.damping(self.ks[kindex], self.p["kstar_damping"]) if damping else np.ones(kindex.size)
-        return recs, (kindex, np.ascontiguousarray(damp, dtype=np.float64), sigma_s, f), alphas
-
-    def _rsd_launch(self, entry, recs, tables, alphas, mus, wl, out_last, parts_shape):
-        nz, nm, nk, n, nmu = self._nz, self._nm, self._nk, tables[0].size, mus.size
-        ctx = self._main(needs_aux=True)
-        # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
-        ta, tb = (self._tracer(r, 1) for r in recs)
-        d_k, d_damp, d_sig, d_f = ctx.upload_int32(tables[0]), ctx.upload(tables[1]), ctx.upload(tables[2]), ctx.upload(tables[3])
-        d_mus = ctx.upload(mus)
-        d_wl = None if wl is None else ctx.upload(np.ascontiguousarray(wl, dtype=np.float64))
-        out = ctx.empty((2, nz, n, out_last))
-        parts = ctx.empty(parts_shape(nz, n)) if parts_shape else None
-        own = dict(d_parts=nat.ptr(parts)) if wl is None else dict(d_wl=d_wl.ptr, d_Q=nat.ptr(parts))
-        ctx.call(entry, nz=nz, nm=nm, nk=nk, n=n, nmu=nmu, h_a=C.byref(ta), h_b=C.byref(tb), **self._model_block(entry),
-                 d_kindex=d_k.ptr, d_damp=d_damp.ptr, d_mus=d_mus.ptr, d_sigma=d_sig.ptr, d_f=d_f.ptr, alpha_m=alphas[0],
-                 alpha_c=alphas[1], alpha_s=alphas[2], d_out=out.ptr, **own)
-        self._sync_point()
-        return out, parts      # (the tables go back to the free list: whatever reads them was enqueued before)
-
-    def rsd_device(self, name, name2=None, mus=None, kindex=None, sigma_s=None, f=None, alphas=(1, 0, 1), damping=True,
-                   parts=False):
-        """The redshift-space wedges of the pair (name, name2; default name) on the device, (2, nz, n, nmu) = (P1h, P2h),
-        at the nodes ks[kindex] (default: all) and the values mus of mu in [0, 1] (default: rsd.mu_rule(16)'s nodes; at
-        most 32).  Dispersion halo model: a halo's members of species i are displaced along the line of sight with the
-        Gaussian dispersion alphas[i] sigma_s[z, m] - alphas = (alpha_m, alpha_c, alpha_s) for matter, centrals and
-        satellites; sigma_s (nz, nm) in comoving Mpc, default rsd.virial_dispersion(self) - so every product of two species
-        in a mass integral carries exp(-(alpha_i^2 + alpha_j^2) (k sigma_s mu)^2 / 2), and the 2-halo term is
-
-            P2h = P_lin (J_a + f mu^2 K_a) (J_b + f mu^2 K_b),
-
-        J the bracket of get_power_2halo with the damped weights, K the same bracket without the halo bias (the Kaiser
-        term of the tracer's own velocity) and f (nz,) the growth rate, default get_growth_rate_f(zs).  The square term
-        of P1h is get_power_1halo's, first-name-only rule for two HOD names included; damping=True multiplies P1h by
-        1 - exp(-(k / kstar)^2) as get_power_1halo does.  A matter or an HOD name is taken, a pressure name refused.
-        parts=True: (out, parts), parts (4, nz, n, nmu) = (I_a, V_a, I_b, V_b), the damped mass sums of the brackets."""
-        mus = rsdmod.mu_rule(rsdmod.DEFAULT_NMU)[0] if mus is None else mus
-        mus = rsdmod.check_mus(mus)
-        recs, tables, alphas = self._rsd_request(name, name2, kindex, sigma_s, f, alphas, damping)
-        out, P = self._rsd_launch("hmg_rsd_wedges", recs, tables, alphas, mus, None, mus.size,
-                                  (lambda nz, n: (4, nz, n, mus.size)) if parts else None)
-        return (out, P) if parts else out
-
-    def get_power_rsd(self, name, name2=None, mus=None, kindex=None, sigma_s=None, f=None, alphas=(1, 0, 1), damping=True):
-        """{"1h", "2h", "total"}: the redshift-space wedges P^s(z, k, mu) of the pair on the host, each (nz, n, nmu); see
-        rsd_device."""
-        out = self.rsd_device(name, name2, mus=mus, kindex=kindex, sigma_s=sigma_s, f=f, alphas=alphas,
-                              damping=damping).numpy()
-        return {"1h": out[0], "2h": out[1], "total": out[0] + out[1]}
-
-    def multipoles_device(self, name, name2=None, nmu=16, kindex=None, sigma_s=None, f=None, alphas=(1, 0, 1), damping=True,
-                          parts=False):
-        """The multipoles P_l = (2l + 1) int_0^1 L_l(mu) P^s dmu, l = 0, 2, 4, of rsd_device's wedges on the device,
-        (2, nz, n, 3) = (1-halo, 2-halo).  The 1-halo multipoles are exact in mu (the moments of the Gaussians in closed
-        form inside the mass integral); the 2-halo ones are defined as the nmu-node Gauss-Legendre rule on [0, 1]
-        (rsd.mu_rule, rsd.legendre_weights; 1 <= nmu <= 32) of the 2-halo wedge.  parts=True: (out, Q), Q (3, nz, n) the
-        moment sums Q_0, Q_1, Q_2 of the 1-halo term (undamped by get_power_1halo's factor)."""
-        mus, _ = rsdmod.mu_rule(nmu)
-        wl = rsdmod.legendre_weights(nmu)
-        recs, tables, alphas = self._rsd_request(name, name2, kindex, sigma_s, f, alphas, damping)
-        out, Q = self._rsd_launch("hmg_rsd_multipoles", recs, tables, alphas, np.ascontiguousarray(mus), wl, 3,
-                                  (lambda nz, n: (3, nz, n)) if parts else None)
-        return (out, Q) if parts else out
-
-    def get_power_multipoles(self, name, name2=None, ells=(0, 2, 4), term="total", nmu=16, kindex=None, sigma_s=None,
-                             f=None, alphas=(1, 0, 1), damping=True):
-        """The multipoles ells (of 0, 2, 4) of the redshift-space spectrum of the pair at the nodes ks[kindex], shape
-        (len(ells), nz, n); term: "1h", "2h" or "total".  See multipoles_device."""
-        ells = rsdmod.check_ells(ells)
-        if term not in rsdmod.TERMS:
-            raise ValueError(f"term must be one of {rsdmod.TERMS}, got {term!r}")
-        out = self.multipoles_device(name, name2, nmu=nmu, kindex=kindex, sigma_s=sigma_s, f=f, alphas=alphas,
-                                     damping=damping).numpy()
-        picked = rsdmod.pick_term(out, term)
-        return np.stack([picked[..., rsdmod.ELLS.index(e)] for e in ells])
-
-    # ------------------------------------------------------------------ cluster lensing (DESIGN.md section 10)
-    # The per-halo scalars are formed on the host one lens redshift at a time (a few values per halo), so that a z slice
-    # of a model with several redshifts is the same computation as a model of that redshift alone.  With one redshift
-    # the results have the reference's shapes; with nz > 1 a leading z axis is added.
-    @staticmethod
-    def _lensing_thetas(thetas):
-        th = np.atleast_1d(np.asarray(thetas, dtype=np.float64)).ravel()
-        if not np.all(np.isfinite(th)) or np.any(th <= 0):
-            raise ValueError("thetas must be finite and positive")
-        return th
-
-    def _lensing_halos(self, Ms, concs, delta, rho, rho_at_z):
-        """(Ms, concs, [(D_A, r_s, delta_c, rho_crit) per z]) of sigma_1h_profiles (hmvec/hmvec.py:574-589)."""
-        Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()
-        concs = np.atleast_1d(np.asarray(concs, dtype=np.float64)).ravel()
-        if Ms.size != concs.size:
-            raise ValueError("Ms and concs must have the same length")
-        if not (np.all(np.isfinite(Ms)) and np.all(Ms > 0) and np.all(np.isfinite(concs)) and np.all(concs > 0)):
-            raise ValueError("masses and concentrations must be finite and positive")
-        if rho == "critical":
-            rhofunc = self.rho_critical_z
-        elif rho == "mean":
-            rhofunc = self.rho_matter_z
-        else:
-            raise ValueError(f"rho must be 'mean' or 'critical', got {rho!r}")
-        fcon = np.log(1.0 + concs) - (concs / (1.0 + concs))      # Fcon (hmvec/hmvec.py:737)
-        rows = []
-        for z in self.zs:
-            zz = np.array([z])
-            rhoz = zz if rho_at_z else zz * 0
-            rs = _R_from_M(Ms, rhofunc(rhoz), delta=delta) / concs
-            rhoc = self.rho_critical_z(zz)
-            delta_c = Ms / 4 / np.pi / rs ** 3 / rhoc / fcon
-            rows.append((float(self.angular_diameter_distance(zz)[0]), rs, delta_c, float(rhoc[0])))
-        return Ms, concs, rows
-
-    def sigma_1h_profiles(self, thetas, Ms, concs, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
-        """One-halo surface density Sigma [Msun/Mpc^2] of NFW halos (masses Ms, concentrations concs) at angles
-        thetas [rad] (hmvec/hmvec.py:574-590): (nM, ntheta), or (nz, nM, ntheta) with several lens redshifts.
-        sig_theta [rad] averages over Rayleigh-distributed miscentring of width D_A(z) sig_theta; 0 is the centred
-        profile."""
-        from .lensing import sigma_nfw
-        return self._lensing_1h(sigma_nfw, thetas, Ms, concs, sig_theta, delta, rho, rho_at_z)
-
-    def delta_sigma_1h_profiles(self, thetas, Ms, concs, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
-        """One-halo excess surface density Delta Sigma = Sigmabar(<R) - Sigma(R) [Msun/Mpc^2],
-        with the arguments, conventions and shapes of sigma_1h_profiles: (nM, ntheta), or (nz, nM, ntheta)."""
-        from .lensing import delta_sigma_nfw
-        return self._lensing_1h(delta_sigma_nfw, thetas, Ms, concs, sig_theta, delta, rho, rho_at_z)
-
-    def gamma_t_1h_profiles(self, thetas, Ms, concs, zsource, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
-        """One-halo tangential shear: delta_sigma_1h_profiles / Sigma_crit(z, zsource)."""
-        dsigma = self.delta_sigma_1h_profiles(thetas, Ms, concs, sig_theta=sig_theta, delta=delta, rho=rho,
-                                              rho_at_z=rho_at_z)
-        return self._over_sigma_crit(dsigma, zsource)
-
-    def _lensing_1h(self, profile, thetas, Ms, concs, sig_theta, delta, rho, rho_at_z):
-        """sigma_1h_profiles / delta_sigma_1h_profiles: `profile` is lensing.sigma_nfw or lensing.delta_sigma_nfw."""
-        th = self._lensing_thetas(thetas)
-        Ms, _, rows = self._lensing_halos(Ms, concs, delta, rho, rho_at_z)
-        if sig_theta is not None and (not np.isfinite(sig_theta) or sig_theta < 0):
-            raise ValueError("sig_theta must be finite and non-negative")
-        nz, nM, nt = self._nz, Ms.size, th.size
-        rs = np.concatenate([r[1] for r in rows])
-        dc = np.concatenate([r[2] for r in rows])
-        rhoc = np.repeat([r[3] for r in rows], nM)
-        rbins = np.repeat(np.stack([r[0] * th for r in rows]), nM, axis=0)           # (nz nM, ntheta)
-        offsets = None
-        if sig_theta is not None and sig_theta > 0:
-            offsets = np.repeat([r[0] * float(sig_theta) for r in rows], nM)
-        prof = profile(rs, dc, rhoc, rbins, offsets=offsets, ctx=self._main()).reshape(nz, nM, nt)
-        return prof[0] if nz == 1 else prof
-
-    def kappa_1h_profiles(self, thetas, Ms, concs, zsource, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
-        """sigma_1h_profiles / Sigma_crit(z, zsource) (hmvec/hmvec.py:592-595)."""
-        sigma = self.sigma_1h_profiles(thetas, Ms, concs, sig_theta=sig_theta, delta=delta, rho=rho,
-                                       rho_at_z=rho_at_z)
-        return self._over_sigma_crit(sigma, zsource)
-
-    def _over_sigma_crit(self, prof, zsource):
-        """A one-halo profile ((nM, ntheta), or (nz, nM, ntheta)) over Sigma_crit(z, zsource) of its lens redshift."""
-        sigmac = np.concatenate([np.atleast_1d(self.sigma_crit(np.array([z]), zsource)) for z in self.zs])
-        return prof / sigmac[0] if self._nz == 1 else prof / sigmac[:, None, None]
-
-    def kappa_2h_profiles(self, thetas, Ms, zsource, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
-                          verbose=True):
-        """Two-halo convergence (hmvec/hmvec.py:597-625) at angles thetas [rad] for halo masses Ms: (ntheta, nM), or
-        (nz, ntheta, nM) with several lens redshifts.  delta, rho and rho_at_z are accepted and unused, as in the
-        reference.  Ms outside the model's mass grid raise ValueError (the reference's interp1d does)."""
-        from .lensing import kappa_2h_integral
-        return self._lensing_2h(kappa_2h_integral, thetas, Ms, zsource, lmin, lmax, verbose)
-
-    def gamma_t_2h_profiles(self, thetas, Ms, zsource, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
-                            verbose=True):
-        """Two-halo tangential shear: kappa_2h_profiles with J0(l theta) replaced by J2(l theta)
-        (Oguri & Takada 2011), same arguments, conventions and shapes: (ntheta, nM), or (nz, ntheta, nM)."""
-        from .lensing import gamma_t_2h_integral
-        return self._lensing_2h(gamma_t_2h_integral, thetas, Ms, zsource, lmin, lmax, verbose)
-
-    def delta_sigma_2h_profiles(self, thetas, Ms, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
-                                verbose=True):
-        """Two-halo excess surface density Sigma_crit(z, zsource) gamma_t^2h [Msun/Mpc^2]: gamma_t_2h_profiles without
-        its 1/Sigma_crit, so no source redshift.  Shapes and keywords as kappa_2h_profiles; verbose prints the bias."""
-        from .lensing import gamma_t_2h_integral
-        return self._lensing_2h(gamma_t_2h_integral, thetas, Ms, None, lmin, lmax, verbose)
-
-    def sigma_2h_profiles(self, thetas, Ms, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
-                          verbose=True):
-        """Two-halo surface density Sigma_crit(z, zsource) kappa_2h [Msun/Mpc^2]: kappa_2h_profiles without its
-        1/Sigma_crit, so no source redshift.  Shapes and keywords as kappa_2h_profiles; verbose prints the bias."""
-        from .lensing import kappa_2h_integral
-        return self._lensing_2h(kappa_2h_integral, thetas, Ms, None, lmin, lmax, verbose)
-
-    def _lensing_2h(self, integral, thetas, Ms, zsource, lmin, lmax, verbose):
-        """The two-halo profiles: `integral` is lensing.kappa_2h_integral (J0) or gamma_t_2h_integral (J2); pre(z)
-        carries 1/Sigma_crit(z, zsource) unless zsource is None."""
-        th = self._lensing_thetas(thetas)
-        Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()       # (finite and positive: `integral` checks)
-        if np.any(Ms < self.ms[0]) or np.any(Ms > self.ms[-1]):
-            raise ValueError("A value in x_new is outside the interpolation range of the model's mass grid")
-        chi, pre, sigmac = [], [], []
-        for z in self.zs:
-            zz = np.array([z])
-            dA = self.angular_diameter_distance(zz)
-            if zsource is None:
-                pre.append((self.rho_matter_z(zz) / (1 + zz) ** 3.0 / dA ** 2)[0])
-            else:
-                sc = np.atleast_1d(self.sigma_crit(zz, zsource))
-                pre.append((self.rho_matter_z(zz) / (1 + zz) ** 3.0 / sc / dA ** 2)[0])
-                sigmac.append(sc[0])
-            chi.append(np.atleast_1d(self.comoving_radial_distance(zz))[0])
-        ctx = self._main(needs_aux=True)
-        out = integral(self.ks, np.array(chi), np.array(pre), self._d_Pzk(), th, lmin, lmax, self.ms, self._d_bh, Ms,
-                       ctx=ctx)
-        if verbose:
-            bhs = np.stack([np.interp(Ms, self.ms, b) for b in self.bh])
-            print("bias ", bhs)
-            if zsource is not None:
-                print("sigmacr ", np.array(sigmac))
-        return out[0] if self._nz == 1 else out
-
-    # ------------------------------------------------------------------ projected gas and pressure (DESIGN.md section 18)
-    # Per-halo scalars on the host, one redshift at a time, as for the cluster-lensing profiles above: a z slice of a
-    # batch is bit for bit a single-z model's result.
-    def _gas_halos(self, Ms, concs, truncate):
-        """(Ms, [(z, D_A, rho_crit, r_vir, M200c, R200c) per z]) with the mass conversion of add_battaglia_profile
-        (hmvec/hmvec.py:215-225): the model's mass definition -> 200 rho_crit(z), concs=None the Duffy concentration."""
-        Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()
-        if not np.all(np.isfinite(Ms)) or np.any(Ms <= 0):
-            raise ValueError("Ms must be finite and positive")
-        if concs is not None:
-            concs = np.atleast_1d(np.asarray(concs, dtype=np.float64)).ravel()
-            if concs.size != Ms.size:
-                raise ValueError("Ms and concs must have the same length")
-            if not np.all(np.isfinite(concs)) or np.any(concs <= 0):
-                raise ValueError("concs must be finite and positive")
-        if not np.isfinite(truncate) or truncate <= 0:
-            raise ValueError("truncate must be finite and positive")
-        A, al, be = (float(self.p[f"duffy_{k}_{self.mdef}"]) for k in ("A", "alpha", "beta"))
-        rows = []
-        for z in self.zs:
-            zz = np.array([z])
-            rhoc = float(self.rho_critical_z(zz)[0])
-            if self.mdef == "vir":
-                drho1 = rhoc * float(self.deltav(zz)[0])
-            elif self.mdef == "mean":
-                drho1 = float(self.rho_matter_z(zz)[0]) * 200.0
-            else:
-                raise NotImplementedError(self.mdef)
-            cs = A * (self.h * Ms / 2.0e12) ** al * (1.0 + z) ** be if concs is None else concs
-            m200c = _mdelta_host(Ms, cs, drho1, 200.0 * rhoc)
-            rows.append((float(z), float(self.angular_diameter_distance(zz)[0]), rhoc,
-                         _R_from_M(Ms, drho1, delta=1.0), m200c, _R_from_M(m200c, rhoc, delta=200.0)))
-        return Ms, rows
-
-    def _projected_profile(self, kind, thetas, Ms, concs, truncate, fwhm, rowfn, norm="fit"):
-        """prefactor x projected_gnfw(kind) for every (z, M, theta).  rowfn(z, rho_crit, M200c, R200c) returns the halo's
-        (scale radius, alpha, gamma, eta, prefactor) with gamma one number.  norm="mass": the prefactor is M / (N r^2)
-        instead, N = 4 pi int_0^xcut x^2 f dx from the "mean" kind at s = xcut."""
-        from .gasprofiles import projected_gnfw
-        th = self._lensing_thetas(thetas)
-        if norm not in ("fit", "mass"):
-            raise ValueError(f"norm must be 'fit' or 'mass', got {norm!r}")
-        if fwhm is not None and (not np.isfinite(fwhm) or fwhm < 0):
-            raise ValueError("fwhm must be finite and non-negative")
-        Ms, halos = self._gas_halos(Ms, concs, truncate)
-        x, alpha, eta, xcut, pref, smooth, rscale = [], [], [], [], [], [], []
-        for z, da, rhoc, rvir, m200c, r200c in halos:
-            r, al, gamma, et, pf = rowfn(z, rhoc, m200c, r200c)
-            x.append(da * th[None, :] / r[:, None])
-            alpha.append(al + 0.0 * r)
-            eta.append(et)
-            xcut.append(truncate * rvir / r)
-            pref.append(pf)
-            rscale.append(r)
-            smooth.append(da * float(fwhm or 0.0) / np.sqrt(8.0 * np.log(2.0)) / r)
-        x, alpha, eta, xcut, pref, smooth, rscale = (np.concatenate(a) for a in (x, alpha, eta, xcut, pref, smooth, rscale))
-        ctx = self._main()
-        if norm == "mass":
-            N = projected_gnfw(xcut[:, None], alpha, gamma, eta, xcut, kind="mean", ctx=ctx)[:, 0] * np.pi * xcut ** 2
-            pref = np.tile(Ms, self._nz) / (N * rscale ** 2)
-        prof = projected_gnfw(x, alpha, gamma, eta, xcut, kind=kind, smooth=smooth if fwhm else None, ctx=ctx)
-        prof = (pref[:, None] * prof).reshape(self._nz, Ms.size, th.size)
-        return prof[0] if self._nz == 1 else prof
-
-    def _gas_rowfn(self, family, param_override):
-        """Battaglia gas density (hmvec/hmvec.py:844-860) as a member of the family: x = r / (R200c / 2),
-        eta = (beta + gamma) / alpha, amplitude (Omega_b / Omega_m) rho_crit(z) rho0 times the scale radius."""
-        pp = self._battaglia_gas_pparams(family, param_override)
-        gamma = float(pp["battaglia_gas_gamma"])
-        fb = self.p["ombh2"] / self.h ** 2.0 / self.omm0
-
-        def rowfn(z, rhoc, m200c, r200c):
-            rho0, alpha, beta = (_battaglia_fit(m200c, z, *(pp[q + s] for s in ("A0", "alpham", "alphaz")))
-                                 for q in ("rho0_", "alpha_", "beta_"))
-            rg = 0.5 * r200c
-            return rg, alpha, gamma, (beta + gamma) / alpha, fb * rhoc * rho0 * rg
-        return rowfn
-
-    def gas_sigma_1h_profiles(self, thetas, Ms, concs=None, family=None, param_override=None, truncate=1.0, norm="fit",
-                              fwhm=None):
-        """Projected gas surface density Sigma_gas [Msun/Mpc^2] of the Battaglia gas profile (the profile of
-        add_battaglia_profile) around halos of mass Ms (the model's mass definition; concs=None: Duffy) at angles thetas
-        [rad]: (nM, ntheta), or (nz, nM, ntheta) with several redshifts.  The profile is cut at truncate r_vir.
-        norm="fit": the amplitude of the fit, (Omega_b / Omega_m) rho_crit(z) rho0; norm="mass": the same shape holding
-        the halo mass Ms inside the cut (the profile whose transform uk_profiles approximates).  fwhm [rad]: convolved
-        with a circular Gaussian beam of that full width at half maximum.  family and param_override as in
-        add_battaglia_profile."""
-        return self._projected_profile("sigma", thetas, Ms, concs, truncate, fwhm,
-                                       self._gas_rowfn(family, param_override), norm)
-
-    def gas_delta_sigma_1h_profiles(self, thetas, Ms, concs=None, family=None, param_override=None, truncate=1.0,
-                                    norm="fit"):
-        """Excess gas surface density Sigmabar_gas(<R) - Sigma_gas(R) [Msun/Mpc^2]; arguments, conventions and shapes of
-        gas_sigma_1h_profiles (no beam)."""
-        return self._projected_profile("excess", thetas, Ms, concs, truncate, None,
-                                       self._gas_rowfn(family, param_override), norm)
-
-    def tau_1h_profiles(self, thetas, Ms, concs=None, family=None, param_override=None, truncate=1.0, fwhm=None):
-        """Thomson optical depth tau(theta) = sigma_T (1 + X_H) / (2 m_p) Sigma_gas of fully ionised gas with hydrogen
-        mass fraction X_H = 0.76 (norm="fit"); dimensionless.  Arguments and shapes of gas_sigma_1h_profiles."""
-        sigma_gas = self.gas_sigma_1h_profiles(thetas, Ms, concs=concs, family=family, param_override=param_override,
-                                               truncate=truncate, norm="fit", fwhm=fwhm)
-        sigmaT = constants.physical_constants["Thomson cross section"][0] / (default_params["parsec"] * 1e6) ** 2
-        m_p = constants.physical_constants["proton mass"][0] / default_params["mSun"]
-        return sigmaT * (1.0 + _X_H) / (2.0 * m_p) * sigma_gas
-
-    def y_1h_profiles(self, thetas, Ms, concs=None, family=None, param_override=None, truncate=1.0, fwhm=None):
-        """Compton-y profile y(theta) = sigma_T / (m_e c^2) int P_e dl of the Battaglia pressure profile (the profile of
-        add_battaglia_pres_profile; hmvec/hmvec.py:906-927, units of 313-316), dimensionless: (nM, ntheta), or
-        (nz, nM, ntheta).  Arguments as gas_sigma_1h_profiles; family and param_override as in
-        add_battaglia_pres_profile."""
-        return self._projected_profile("sigma", thetas, Ms, concs, truncate, fwhm, self._pres_rowfn(family, param_override))
-
-    def _pres_rowfn(self, family, param_override):
-        """Battaglia pressure profile as a member of the family, in Compton-y units: x = r / (xc R200c), eta = beta,
-        amplitude sigma_T / (m_e c^2) A_P times the scale radius."""
-        pp = self._battaglia_pres_pparams(family, param_override)
-        gamma, alpha = float(pp["battaglia_pres_gamma"]), float(pp["battaglia_pres_alpha"])
-        eFrac = 2.0 * (_X_H + 1.0) / (5.0 * _X_H + 3.0)
-        G_newt = constants.G / (default_params["parsec"] * 1e6) ** 3 * default_params["mSun"]
-        sigmaT = constants.physical_constants["Thomson cross section"][0]
-        mElect = constants.physical_constants["electron mass"][0] / default_params["mSun"]
-        fb = self.p["ombh2"] / self.h ** 2.0 / self.omm0
-
-        def rowfn(z, rhoc, m200c, r200c):
-            P0, xc, beta = (_battaglia_fit(m200c, z, *(pp[q + s] for s in ("A0", "alpham", "alphaz")))
-                            for q in ("P0_", "xc_", "beta_"))
-            rp = xc * r200c
-            A_P = eFrac * fb * 200.0 * m200c * G_newt * rhoc / (2.0 * r200c) * P0
-            return rp, alpha, gamma, beta, sigmaT / (mElect * constants.c ** 2) * A_P * rp
-        return rowfn
-
-    # ------------------------------------------------------------------ one-point PDF (DESIGN.md section 20)
-    # P(y) of a Compton-y map and the PDF of any field that is a sum of halo profiles on the sky, for Poisson-placed halos
-    # (hmg_onepoint_exponent, hmg_onepoint_moments).  The host side of the contract - the grid in lambda, the ring rule,
-    # the transform, the checks - is onepoint.py.  Every refusal happens on the host before a context is touched: the
-    # *_request methods check and build host arrays, _onepoint_launch is the only one that reaches the device.
-    def _onepoint_request(self, ntheta, mmin, mmax, zweights):
-        """(u, w, (m_lo, m_hi), zw) of the shared tail of the one-point methods."""
-        u, w = onepoint.ring_rule(ntheta)
-        ms = np.asarray(self.ms, dtype=np.float64)
-        for name, v in (("mmin", mmin), ("mmax", mmax)):
-            if v is not None and not (np.isscalar(v) and np.isfinite(v) and v > 0):
-                raise ValueError(f"{name} must be a finite positive mass or None, got {v!r}")
-        keep = np.nonzero((ms >= (ms[0] if mmin is None else mmin)) & (ms <= (ms[-1] if mmax is None else mmax)))[0]
-        if keep.size == 0:
-            raise ValueError(f"no point of the mass grid lies in mmin .. mmax = {mmin!r} .. {mmax!r}")
-        if zweights is None:
-            if self._nz < 2:
-                raise ValueError("zweights=None needs at least two redshifts (the default is a trapezoid rule over zs times "
-                                 "the comoving volume per steradian); give the weight of the one redshift")
-            zs = np.asarray(self.zs, dtype=np.float64)
-            chi = np.asarray(self.comoving_radial_distance(zs), dtype=np.float64).reshape(-1)
-            hz = np.asarray(self.hubble_parameter(zs), dtype=np.float64).reshape(-1)
-            zweights = trapz_weights(zs) * (constants.c / 1.0e3) * chi ** 2 / hz       # dz dV/dz/dOmega, comoving Mpc^3/sr
-        return u, w, (int(keep[0]), int(keep[-1]) + 1), onepoint.check_zweights(zweights, self._nz)
-
-    def _profile_request(self, profiles, theta_out, ntheta, mmin, mmax, zweights):
-        u, w, window, zw = self._onepoint_request(ntheta, mmin, mmax, zweights)
-        shape = (self._nz, self._nm, u.size)
-        got = profiles.shape if isinstance(profiles, nat.DeviceArray) else np.shape(profiles)
-        if tuple(got) != shape:
-            raise ValueError(f"profiles must have shape (nz, nm, ntheta) = {shape}, got {tuple(got)}")
-        if not isinstance(profiles, nat.DeviceArray):
-            profiles = np.ascontiguousarray(profiles, dtype=np.float64)
-            if not np.all(np.isfinite(profiles)):
-                raise ValueError("profiles must be finite")
-        theta_out = np.asarray(theta_out, dtype=np.float64)
-        if theta_out.shape != shape[:2]:
-            raise ValueError(f"theta_out must have shape (nz, nm) = {shape[:2]}, got {theta_out.shape}")
-        if not np.all(np.isfinite(theta_out)) or np.any(theta_out <= 0):
-            raise ValueError("theta_out must be finite and positive")
-        area = (2.0 * np.pi * theta_out ** 2)[:, :, None] * (u * w)[None, None, :]
-        return dict(signal=profiles, amp=None, area=area, window=window, zw=zw)
-
-    def _y_request(self, truncate, fwhm, family, param_override, ntheta, mmin, mmax, zweights):
-        """The rings of every (zs, ms) halo's Compton-y profile: the arguments of the projection in scaled units, the
-        amplitudes and the solid angles, all on the host."""
-        u, w, window, zw = self._onepoint_request(ntheta, mmin, mmax, zweights)
-        if fwhm is not None and not (np.isscalar(fwhm) and np.isfinite(fwhm) and fwhm >= 0):
-            raise ValueError("fwhm must be finite and non-negative")
-        beam = float(fwhm or 0.0) / np.sqrt(8.0 * np.log(2.0))
-        rowfn = self._pres_rowfn(family, param_override)
-        Ms, halos = self._gas_halos(self.ms, None, truncate)
-        x, alpha, eta, xcut, pref, smooth, theta_out = [], [], [], [], [], [], []
-        for z, da, rhoc, rvir, m200c, r200c in halos:
-            r, al, gamma, et, pf = rowfn(z, rhoc, m200c, r200c)
-            tout = truncate * rvir / da + 5.0 * beam
-            x.append(da * (tout[:, None] * u[None, :]) / r[:, None])       # (the operations of y_1h_profiles at tout u)
-            alpha.append(al + 0.0 * r)
-            eta.append(et)
-            xcut.append(truncate * rvir / r)
-            pref.append(pf)
-            smooth.append(da * beam / r)
-            theta_out.append(tout)
-        x, alpha, eta, xcut, smooth = (np.concatenate(a) for a in (x, alpha, eta, xcut, smooth))
-        pref, theta_out = np.stack(pref), np.stack(theta_out)
-        for name, a in (("the profile's parameters", np.concatenate([alpha, eta, xcut, pref.ravel()])), ("the ring radii", x)):
-            if not np.all(np.isfinite(a)):
-                raise ValueError(f"{name} are not finite")
-        area = (2.0 * np.pi * theta_out ** 2)[:, :, None] * (u * w)[None, None, :]
-        return dict(signal=None, proj=(x, alpha, gamma, eta, xcut, smooth if beam > 0 else None), amp=pref, area=area,
-                    window=window, zw=zw)
-
-    def _onepoint_launch(self, req, grid, per_z):
-        """The contraction of a checked request on the device; grid = (nlambda, dlambda), or None for the cumulants."""
-        ctx = self._main(needs_aux=True)
-        signal = req["signal"]
-        if signal is None:          # the profiles stay on the device
-            from .gasprofiles import projected_gnfw_device
-            signal = projected_gnfw_device(*req["proj"], ctx=ctx)
-        arrays = (signal, req["area"], self._d_nzm, self._d_wm(), req["zw"])
-        dims = (self._nz, self._nm, req["area"].shape[-1])
-        if grid is None:
-            out = onepoint._moments(ctx, arrays, req["amp"], dims, req["window"], per_z)
-        else:
-            out = onepoint._exponent(ctx, arrays, req["amp"], dims, req["window"], *grid, per_z)
-        self._sync_point()
-        return out
-
-    def profile_char_exponent(self, profiles, theta_out, nbins, ds, ntheta=onepoint.DEFAULT_RINGS, mmin=None, mmax=None,
-                              zweights=None, per_z=False):
-        """The exponent A(lambda_j) of the characteristic function exp A of a field that is the sum of the profiles of
-        Poisson-placed halos of the model's mass function, on onepoint.lambda_grid(nbins, ds): complex (nbins / 2 + 1,),
-        or with per_z=True its rows (nz, nbins / 2 + 1).  profiles (nz, nm, ntheta), a host array or a device buffer, is
-        the profile of a halo of mass ms[m] at zs[z] at the angles theta_out[z, m] u_t [rad], u = onepoint.ring_rule(ntheta)
-        [0], and zero beyond theta_out (nz, nm) - built from kappa_1h_profiles, for instance.  zweights (nz,): the weight
-        of a redshift, default trapz_weights(zs) c chi^2 / H, the comoving volume per steradian that goes with the comoving
-        mass function; mmin, mmax: only the masses of the grid in [mmin, mmax].  onepoint.pdf_from_exponent turns the
-        result into the PDF.  Halo clustering is neglected; overlapping halos are not."""
-        grid = onepoint.lambda_grid(nbins, ds)
-        req = self._profile_request(profiles, theta_out, ntheta, mmin, mmax, zweights)
-        return self._onepoint_launch(req, grid, bool(per_z))
-
-    def get_y_char_exponent(self, nbins, dy, truncate=1.0, fwhm=None, family=None, param_override=None,
-                            ntheta=onepoint.DEFAULT_RINGS, mmin=None, mmax=None, zweights=None, per_z=False):
-        """profile_char_exponent of the Compton-y profile of y_1h_profiles (the Battaglia pressure profile cut at
-        truncate r_vir, Duffy concentrations; family and param_override as in add_battaglia_pres_profile) of every
-        (zs, ms) halo, on lambda_grid(nbins, dy).  The rings end at theta_out = truncate r_vir / D_A, with fwhm [rad] (the
-        beam the profile is convolved with) at 5 beam widths sigma = fwhm / sqrt(8 ln 2) beyond.  The profiles are
-        evaluated and contracted on the device."""
-        grid = onepoint.lambda_grid(nbins, dy)
-        req = self._y_request(truncate, fwhm, family, param_override, ntheta, mmin, mmax, zweights)
-        return self._onepoint_launch(req, grid, bool(per_z))
-
-    def get_y_pdf(self, nbins, dy, ymin=0.0, noise_sigma=0.0, truncate=1.0, fwhm=None, family=None, param_override=None,
-                  ntheta=onepoint.DEFAULT_RINGS, mmin=None, mmax=None, zweights=None, per_z=False):
-        """(ys, p): the one-point PDF of the Compton-y map in nbins bins of width dy from ymin, p the probability per bin
-        (nbins,), with Gaussian map noise of width noise_sigma - onepoint.pdf_from_exponent of get_y_char_exponent; see
-        there for the periodicity and for why noise_sigma >~ 2 dy.  per_z=True: p (nz, nbins), the PDF of each redshift's
-        halos alone."""
-        grid = onepoint.lambda_grid(nbins, dy)
-        noise_sigma = onepoint.check_noise(noise_sigma)
-        if not (np.isscalar(ymin) and np.isfinite(ymin)):
-            raise ValueError("ymin must be finite")
-        req = self._y_request(truncate, fwhm, family, param_override, ntheta, mmin, mmax, zweights)
-        A = self._onepoint_launch(req, grid, bool(per_z))
-        if not per_z:
-            return onepoint.pdf_from_exponent(A, dy, ymin, noise_sigma)
-        rows = [onepoint.pdf_from_exponent(a, dy, ymin, noise_sigma) for a in A]
-        return rows[0][0], np.stack([p for _, p in rows])
-
-    def get_y_cumulants(self, truncate=1.0, fwhm=None, family=None, param_override=None, ntheta=onepoint.DEFAULT_RINGS,
-                        mmin=None, mmax=None, zweights=None, per_z=False):
-        """[<y>, kappa_2, kappa_3, kappa_4]: the mean and the second to fourth cumulant of the Compton-y map of
-        get_y_char_exponent (without noise), kappa_p = sum zw wm n a y^p; (4,), or with per_z=True (nz, 4)."""
-        req = self._y_request(truncate, fwhm, family, param_override, ntheta, mmin, mmax, zweights)
-        return self._onepoint_launch(req, None, bool(per_z))
-
-    # ------------------------------------------------------------------ HOD parameter ensembles (DESIGN.md section 21)
-    # P_gg and P_gm of S parameter sets in one pass over the tensors (hmg_hod_ensemble, hmg_hod_ensemble_power).  The host
-    # side of the contract - the table of sets, the stencil, the checks - is hod_ensemble.py.  Nothing is registered in
-    # hods and the model's version does not change: cached spectra stay valid.
-    def _hodens_request(self, sets, mthresh, ngal, corr):
-        """(sets (S, 6), corr flag, log10 thresholds (S, nz) or None, n_gal targets (S, nz) or None): every refusal of the
-        HOD half of a request, on the host."""
-        sets = hodens.as_sets(sets)
-        if (mthresh is None) == (ngal is None):
-            raise ValueError("give exactly one of mthresh and ngal")
-        S, nz = sets.shape[0], self._nz
-        flag = hodens.check_corr(corr)
-        if ngal is not None:
-            return sets, flag, None, hodens.per_set(ngal, S, nz, "ngal")
-        return sets, flag, np.log10(hodens.per_set(mthresh, S, nz, "mthresh")), None
-
-    def _hodens_occ(self, ctx, d_par, flag, l10, S, occ=None, coef=None):
-        """One hmg_hod_ensemble launch at the thresholds l10 (S, nz): (d_lthr, d_ngal, d_bg)."""
-        nz, nm = self._nz, self._nm
-        d_thr, d_ngal, d_bg = ctx.upload(np.ascontiguousarray(l10)), ctx.empty((S, nz)), ctx.empty((S, nz))
-        ctx.call("hmg_hod_ensemble", S=S, nz=nz, nm=nm, corr=flag, d_par=d_par.ptr, d_lthr=d_thr.ptr, d_zs=self._d_zs().ptr,
-                 **self._model_block("hmg_hod_ensemble"), d_ngal=d_ngal.ptr, d_bg=d_bg.ptr, d_occ=nat.ptr(occ),
-                 d_coef=nat.ptr(coef))
-        return d_thr, d_ngal, d_bg
-
-    def _hodens_bisect(self, ctx, d_par, target):
-        """log10 mthresh (S, nz) by one batched bisection, and its number of launches.  The rules are those of
-        utils.vectorized_bisection_search with the stop test per set: a set stops updating once all of its redshifts meet
-        hod_bisection_search_rtol - the thresholds add_hod(ngal=target[s]) finds for that set alone - while the others go
-        on; the number of launches is the largest iteration count."""
-        p = self.p
-        S = target.shape[0]
-        lo = np.zeros_like(target) + p["hod_bisection_search_min_log10mthresh"]
-        hi = np.zeros_like(target) + p["hod_bisection_search_max_log10mthresh"]
-        out = np.zeros_like(target)
-        active = np.ones(S, dtype=bool)
-        n_iter, warned = 0, False
-        while active.any():
-            mid = np.where(active[:, None], (lo + hi) / 2.0, out)
-            got = self._hodens_occ(ctx, d_par, 0, mid, S)[1].numpy()
-            miss = (got - target) / target
-            out[active] = mid[active]
-            hodens.bisection_step(lo, hi, mid, miss, active)
-            active &= np.any(np.abs(miss) > p["hod_bisection_search_rtol"], axis=1)
-            n_iter += 1
-            if n_iter > p["hod_bisection_search_warn_iter"] and not warned:
-                print("WARNING: Bisection search has done more than ", p["hod_bisection_search_warn_iter"],
-                      " loops. Still searching...")
-                warned = True
-        return out, n_iter
-
-    def _hodens_thresholds(self, ctx, d_par, l10, target):
-        """The log10 thresholds of a request as add_hod forms them, and the bisection's launches."""
-        if l10 is not None:
-            return l10, 0
-        lm, n_iter = self._hodens_bisect(ctx, d_par, target)
-        return np.log10(10 ** (lm * self.p["hod_A_log10mthresh"])), n_iter
-
-    def _hodens_tensor(self, name, what):
-        if name in self.pk_profiles and name not in self.uk_profiles:
-            raise ValueError(f"{what} {name!r} is a pressure profile: an HOD ensemble takes matter profiles")
-        if name not in self.uk_profiles:
-            raise ValueError(f"{what} {name!r} is not a matter profile of this model")
-        return name
-
-    def hod_ensemble_device(self, sets, mthresh=None, ngal=None, corr="max", satellite_profile_name="nfw", matter_name=None,
-                            kindex=None, damping=True, parts=False):
-        """P_gg and P_gm of S HOD parameter sets at once, on the device: a hod_ensemble.HodEnsembleResult with power
-        (4, S, nz, n) = (P1h_gg, P2h_gg, P1h_gm, P2h_gm), ngal, bg and log10mthresh (S, nz) and parts (3, S, nz, n) =
-        (G, X, I) or None.  sets: (S, 6) as hod_ensemble.hod_sets makes them; exactly one of mthresh and ngal, each (nz,),
-        shared by the sets, or (S, nz) - ngal runs one batched bisection whose thresholds are those add_hod(ngal=...)
-        finds for each set alone.  Plane by plane the result is get_power_1halo / get_power_2halo of (g_s, g_s) and
-        (g_s, matter_name) for g_s = add_hod(mthresh=..., corr=corr, satellite_profile_name=..., param_override=set s)
-        without a central profile; matter_name defaults to the satellite profile.  kindex: the nodes of the k grid
-        (default: all); damping as in get_power_1halo.  Nothing is registered in hods; cached spectra stay valid."""
-        sets, flag, l10, target = self._hodens_request(sets, mthresh, ngal, corr)
-        sat = self._hodens_tensor(satellite_profile_name, "satellite_profile_name")
-        mat = sat if matter_name is None else self._hodens_tensor(matter_name, "matter_name")
-        nz, nm, nk = self._nz, self._nm, self._nk
-        kindex = hodens.check_kindex(kindex, nk)
-        S, n = sets.shape[0], nk if kindex is None else kindex.size
-        nodes = self.ks if kindex is None else self.ks[kindex]
-        damp = bispec.damping(nodes, self.p["kstar_damping"]) if damping else np.ones(n)
-        ctx = self._main(needs_aux=True)
-        shape = (nz, nm, nk)
-        # (another reader of the tensors than the batched mass integrals: a deferred left fill is written first)
-        d_us = self.uk_profiles.dev(sat, fill=True)
-        d_um = d_us if mat == sat else self.uk_profiles.dev(mat, fill=True)
-        for nm_, d_ in ((sat, d_us), (mat, d_um)):
-            if d_.shape != shape:
-                raise ValueError(f"profile {nm_!r} has shape {d_.shape}, the model's grid is {shape}")
-        d_par = ctx.upload(sets)
-        l10, n_iter = self._hodens_thresholds(ctx, d_par, l10, target)
-        coef = ctx.empty((hodens.coef_block_size(S, nz, nm),))
-        d_thr, d_ngal, d_bg = self._hodens_occ(ctx, d_par, flag, l10, S, coef=coef)
-        d_k = None if kindex is None else ctx.upload_int32(kindex)
-        d_damp = ctx.upload(np.ascontiguousarray(damp, dtype=np.float64))
-        out = ctx.empty((4, S, nz, n))
-        P = ctx.empty((3, S, nz, n)) if parts else None
-        ctx.call("hmg_hod_ensemble_power", S=S, nz=nz, nm=nm, nk=nk, n=n, d_us=d_us.ptr, d_um=d_um.ptr, d_coef=coef.ptr,
-                 d_ngal=d_ngal.ptr, d_bg=d_bg.ptr, **self._model_block("hmg_hod_ensemble_power"), d_kindex=nat.ptr(d_k),
-                 d_damp=d_damp.ptr, d_out=out.ptr, d_parts=nat.ptr(P))
-        self._sync_point()
-        return hodens.HodEnsembleResult(out, d_ngal, d_bg, d_thr, P, n_iter)
-
-    def get_power_hod_ensemble(self, sets, mthresh=None, ngal=None, corr="max", satellite_profile_name="nfw",
-                               matter_name=None, kindex=None, damping=True, parts=False):
-        """hod_ensemble_device on the host: a dict of gg_1h, gg_2h, gg, gm_1h, gm_2h, gm, each (S, nz, n), and ngal, bg,
-        log10mthresh (S, nz); with parts=True also G, X, I (S, nz, n)."""
-        r = self.hod_ensemble_device(sets, mthresh=mthresh, ngal=ngal, corr=corr,
-                                     satellite_profile_name=satellite_profile_name, matter_name=matter_name, kindex=kindex,
-                                     damping=damping, parts=parts)
-        power = r.power.numpy()
-        out = dict(zip(hodens.POWER_KEYS, power))
-        out["gg"], out["gm"] = power[0] + power[1], power[2] + power[3]
-        out["ngal"], out["bg"], out["log10mthresh"] = r.ngal.numpy(), r.bg.numpy(), r.log10mthresh.numpy()
-        if parts:
-            out.update(zip(("G", "X", "I"), r.parts.numpy()))
-        return out
-
-    def hod_ensemble_occupations(self, sets, mthresh=None, ngal=None, corr="max"):
-        """{Nc, Ns, NsNsm1, NcNs (S, nz, nm), ngal, bg (S, nz)}: the occupation numbers and sums of every set, each the
-        bits add_hod gives for that set alone."""
-        sets, flag, l10, target = self._hodens_request(sets, mthresh, ngal, corr)
-        S = sets.shape[0]
-        ctx = self._main(needs_aux=True)
-        d_par = ctx.upload(sets)
-        l10, _ = self._hodens_thresholds(ctx, d_par, l10, target)
-        occ = ctx.empty((4, S, self._nz, self._nm))
-        _, d_ngal, d_bg = self._hodens_occ(ctx, d_par, flag, l10, S, occ=occ)
-        self._sync_point()
-        out = dict(zip(("Nc", "Ns", "NsNsm1", "NcNs"), occ.numpy()))
-        out["ngal"], out["bg"] = d_ngal.numpy(), d_bg.numpy()
-        return out
-
-
-_X_H = 0.76      # hydrogen mass fraction of the Battaglia profiles (hmvec/hmvec.py:922)
-
-
-def _battaglia_fit(m200c, z, A0, alpham, alphaz):
-    """A0 (M200c / 1e14)^alpha_m (1+z)^alpha_z on the host (hmvec/hmvec.py:800-802)."""
-    return A0 * (m200c / 1.0e14) ** alpham * (1.0 + z) ** alphaz
-
-
-def _mdelta_host(M1, c1, drho1, drho2):
-    """Mass in the definition Delta rho = drho2 of NFW halos of mass M1 and concentration c1 in the definition drho1
-    (hmvec/hmvec.py:770-798) on the host: equal r_s and rho_s give M2 / F(c2) = M1 / F(c1) with
-    c2 = c1 (M2 drho1 / (M1 drho2))^(1/3), F(c) = ln(1+c) - c/(1+c); Newton in ln(M2/M1) to machine precision."""
-    def F(c):
-        return np.log1p(c) - c / (1.0 + c)
-    lnF1 = np.log(F(c1))
-    lq = np.zeros_like(M1)
-    for _ in range(60):
-        c2 = c1 * (np.exp(lq) * drho1 / drho2) ** (1.0 / 3.0)
-        F2 = F(c2)
-        resid = lq - np.log(F2) + lnF1
-        dlnF = c2 * c2 / (1.0 + c2) ** 2 / F2           # d ln F / d ln c
-        step = resid / (1.0 - dlnF / 3.0)
-        lq = lq - step
-        if np.all(np.abs(step) < 1e-15):
-            break
-    return M1 * np.exp(lq)
 
 
 class _HostBlock:

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _native as nat
 from ._native import as_device as _dev, context_or_default as _context
+from .utils import _R_from_M
 
 __all__ = ["sigma_nfw", "delta_sigma_nfw", "kappa_2h_integral", "gamma_t_2h_integral"]
 
@@ -127,3 +128,141 @@ def _two_halo(entry, ks, chi, pre, Pzk, thetas, lmin, lmax, ms, bh, Ms, ctx):
     ctx.call(entry, nz, nk, nt, nm, nM, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, d[4].ptr,
              float(lmin), float(lmax), d[5].ptr, d[6].ptr, d[7].ptr, out.ptr)
     return out.numpy()
+
+
+class ClusterLensingMixin:
+    """HaloModel's cluster-lensing profiles (DESIGN.md sections 10, 12).  The per-halo scalars are formed on the host one
+    lens redshift at a time (a few values per halo), so that a z slice of a model with several redshifts is the same
+    computation as a model of that redshift alone.  With one redshift the results have the reference's shapes; with
+    nz > 1 a leading z axis is added."""
+
+    @staticmethod
+    def _lensing_thetas(thetas):
+        th = np.atleast_1d(np.asarray(thetas, dtype=np.float64)).ravel()
+        if not np.all(np.isfinite(th)) or np.any(th <= 0):
+            raise ValueError("thetas must be finite and positive")
+        return th
+
+    def _lensing_halos(self, Ms, concs, delta, rho, rho_at_z):
+        """(Ms, concs, [(D_A, r_s, delta_c, rho_crit) per z]) of sigma_1h_profiles (hmvec/hmvec.py:574-589)."""
+        Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()
+        concs = np.atleast_1d(np.asarray(concs, dtype=np.float64)).ravel()
+        if Ms.size != concs.size:
+            raise ValueError("Ms and concs must have the same length")
+        if not (np.all(np.isfinite(Ms)) and np.all(Ms > 0) and np.all(np.isfinite(concs)) and np.all(concs > 0)):
+            raise ValueError("masses and concentrations must be finite and positive")
+        if rho == "critical":
+            rhofunc = self.rho_critical_z
+        elif rho == "mean":
+            rhofunc = self.rho_matter_z
+        else:
+            raise ValueError(f"rho must be 'mean' or 'critical', got {rho!r}")
+        fcon = np.log(1.0 + concs) - (concs / (1.0 + concs))      # Fcon (hmvec/hmvec.py:737)
+        rows = []
+        for z in self.zs:
+            zz = np.array([z])
+            rhoz = zz if rho_at_z else zz * 0
+            rs = _R_from_M(Ms, rhofunc(rhoz), delta=delta) / concs
+            rhoc = self.rho_critical_z(zz)
+            delta_c = Ms / 4 / np.pi / rs ** 3 / rhoc / fcon
+            rows.append((float(self.angular_diameter_distance(zz)[0]), rs, delta_c, float(rhoc[0])))
+        return Ms, concs, rows
+
+    def sigma_1h_profiles(self, thetas, Ms, concs, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
+        """One-halo surface density Sigma [Msun/Mpc^2] of NFW halos (masses Ms, concentrations concs) at angles
+        thetas [rad] (hmvec/hmvec.py:574-590): (nM, ntheta), or (nz, nM, ntheta) with several lens redshifts.
+        sig_theta [rad] averages over Rayleigh-distributed miscentring of width D_A(z) sig_theta; 0 is the centred
+        profile."""
+        return self._lensing_1h(sigma_nfw, thetas, Ms, concs, sig_theta, delta, rho, rho_at_z)
+
+    def delta_sigma_1h_profiles(self, thetas, Ms, concs, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
+        """One-halo excess surface density Delta Sigma = Sigmabar(<R) - Sigma(R) [Msun/Mpc^2],
+        with the arguments, conventions and shapes of sigma_1h_profiles: (nM, ntheta), or (nz, nM, ntheta)."""
+        return self._lensing_1h(delta_sigma_nfw, thetas, Ms, concs, sig_theta, delta, rho, rho_at_z)
+
+    def gamma_t_1h_profiles(self, thetas, Ms, concs, zsource, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
+        """One-halo tangential shear: delta_sigma_1h_profiles / Sigma_crit(z, zsource)."""
+        dsigma = self.delta_sigma_1h_profiles(thetas, Ms, concs, sig_theta=sig_theta, delta=delta, rho=rho,
+                                              rho_at_z=rho_at_z)
+        return self._over_sigma_crit(dsigma, zsource)
+
+    def _lensing_1h(self, profile, thetas, Ms, concs, sig_theta, delta, rho, rho_at_z):
+        """sigma_1h_profiles / delta_sigma_1h_profiles: `profile` is lensing.sigma_nfw or lensing.delta_sigma_nfw."""
+        th = self._lensing_thetas(thetas)
+        Ms, _, rows = self._lensing_halos(Ms, concs, delta, rho, rho_at_z)
+        if sig_theta is not None and (not np.isfinite(sig_theta) or sig_theta < 0):
+            raise ValueError("sig_theta must be finite and non-negative")
+        nz, nM, nt = self._nz, Ms.size, th.size
+        rs = np.concatenate([r[1] for r in rows])
+        dc = np.concatenate([r[2] for r in rows])
+        rhoc = np.repeat([r[3] for r in rows], nM)
+        rbins = np.repeat(np.stack([r[0] * th for r in rows]), nM, axis=0)           # (nz nM, ntheta)
+        offsets = None
+        if sig_theta is not None and sig_theta > 0:
+            offsets = np.repeat([r[0] * float(sig_theta) for r in rows], nM)
+        prof = profile(rs, dc, rhoc, rbins, offsets=offsets, ctx=self._main()).reshape(nz, nM, nt)
+        return prof[0] if nz == 1 else prof
+
+    def kappa_1h_profiles(self, thetas, Ms, concs, zsource, sig_theta=None, delta=200, rho="mean", rho_at_z=True):
+        """sigma_1h_profiles / Sigma_crit(z, zsource) (hmvec/hmvec.py:592-595)."""
+        sigma = self.sigma_1h_profiles(thetas, Ms, concs, sig_theta=sig_theta, delta=delta, rho=rho,
+                                       rho_at_z=rho_at_z)
+        return self._over_sigma_crit(sigma, zsource)
+
+    def _over_sigma_crit(self, prof, zsource):
+        """A one-halo profile ((nM, ntheta), or (nz, nM, ntheta)) over Sigma_crit(z, zsource) of its lens redshift."""
+        sigmac = np.concatenate([np.atleast_1d(self.sigma_crit(np.array([z]), zsource)) for z in self.zs])
+        return prof / sigmac[0] if self._nz == 1 else prof / sigmac[:, None, None]
+
+    def kappa_2h_profiles(self, thetas, Ms, zsource, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
+                          verbose=True):
+        """Two-halo convergence (hmvec/hmvec.py:597-625) at angles thetas [rad] for halo masses Ms: (ntheta, nM), or
+        (nz, ntheta, nM) with several lens redshifts.  delta, rho and rho_at_z are accepted and unused, as in the
+        reference.  Ms outside the model's mass grid raise ValueError (the reference's interp1d does)."""
+        return self._lensing_2h(kappa_2h_integral, thetas, Ms, zsource, lmin, lmax, verbose)
+
+    def gamma_t_2h_profiles(self, thetas, Ms, zsource, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
+                            verbose=True):
+        """Two-halo tangential shear: kappa_2h_profiles with J0(l theta) replaced by J2(l theta)
+        (Oguri & Takada 2011), same arguments, conventions and shapes: (ntheta, nM), or (nz, ntheta, nM)."""
+        return self._lensing_2h(gamma_t_2h_integral, thetas, Ms, zsource, lmin, lmax, verbose)
+
+    def delta_sigma_2h_profiles(self, thetas, Ms, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
+                                verbose=True):
+        """Two-halo excess surface density Sigma_crit(z, zsource) gamma_t^2h [Msun/Mpc^2]: gamma_t_2h_profiles without
+        its 1/Sigma_crit, so no source redshift.  Shapes and keywords as kappa_2h_profiles; verbose prints the bias."""
+        return self._lensing_2h(gamma_t_2h_integral, thetas, Ms, None, lmin, lmax, verbose)
+
+    def sigma_2h_profiles(self, thetas, Ms, delta=200, rho="mean", rho_at_z=True, lmin=100, lmax=10000,
+                          verbose=True):
+        """Two-halo surface density Sigma_crit(z, zsource) kappa_2h [Msun/Mpc^2]: kappa_2h_profiles without its
+        1/Sigma_crit, so no source redshift.  Shapes and keywords as kappa_2h_profiles; verbose prints the bias."""
+        return self._lensing_2h(kappa_2h_integral, thetas, Ms, None, lmin, lmax, verbose)
+
+    def _lensing_2h(self, integral, thetas, Ms, zsource, lmin, lmax, verbose):
+        """The two-halo profiles: `integral` is lensing.kappa_2h_integral (J0) or gamma_t_2h_integral (J2); pre(z)
+        carries 1/Sigma_crit(z, zsource) unless zsource is None."""
+        th = self._lensing_thetas(thetas)
+        Ms = np.atleast_1d(np.asarray(Ms, dtype=np.float64)).ravel()       # (finite and positive: `integral` checks)
+        if np.any(Ms < self.ms[0]) or np.any(Ms > self.ms[-1]):
+            raise ValueError("A value in x_new is outside the interpolation range of the model's mass grid")
+        chi, pre, sigmac = [], [], []
+        for z in self.zs:
+            zz = np.array([z])
+            dA = self.angular_diameter_distance(zz)
+            if zsource is None:
+                pre.append((self.rho_matter_z(zz) / (1 + zz) ** 3.0 / dA ** 2)[0])
+            else:
+                sc = np.atleast_1d(self.sigma_crit(zz, zsource))
+                pre.append((self.rho_matter_z(zz) / (1 + zz) ** 3.0 / sc / dA ** 2)[0])
+                sigmac.append(sc[0])
+            chi.append(np.atleast_1d(self.comoving_radial_distance(zz))[0])
+        ctx = self._main(needs_aux=True)
+        out = integral(self.ks, np.array(chi), np.array(pre), self._d_Pzk(), th, lmin, lmax, self.ms, self._d_bh, Ms,
+                       ctx=ctx)
+        if verbose:
+            bhs = np.stack([np.interp(Ms, self.ms, b) for b in self.bh])
+            print("bias ", bhs)
+            if zsource is not None:
+                print("sigmacr ", np.array(sigmac))
+        return out[0] if self._nz == 1 else out

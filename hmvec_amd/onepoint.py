@@ -12,10 +12,12 @@ kappa_p = sum zw wm n a s^p.  ``char_exponent`` and ``cumulants`` are the two co
 Overlapping halos are included (that is what the exponential does); halo clustering is not.
 """
 import numpy as np
+import scipy.constants as constants
 
 from . import _native as nat
+from . import gasprofiles
 from ._native import as_device as _dev, context_or_default as _context
-from .quadrature import gauss_legendre_unit
+from .quadrature import gauss_legendre_unit, trapz_weights
 
 __all__ = ["char_exponent", "cumulants", "pdf_from_exponent", "lambda_grid", "ring_rule", "chain_length",
            "MAX_BINS", "MAX_RINGS", "DEFAULT_RINGS"]
@@ -212,3 +214,134 @@ def pdf_from_exponent(A, ds, smin=0.0, noise_sigma=0.0):
     lam = 2.0 * np.pi * np.arange(A.size) / (n * ds)
     phi = np.exp(A.astype(np.complex128) - 0.5 * (lam * sigma) ** 2) * np.exp(-1j * lam * smin)
     return smin + ds * np.arange(n), np.fft.irfft(np.conj(phi), n=n)
+
+
+class OnePointMixin:
+    """HaloModel's one-point PDF (hmg_onepoint_exponent, hmg_onepoint_moments).  Every refusal happens on the host before
+    a context is touched: the *_request methods check and build host arrays (the halos and the pressure profile's rows
+    are GasProjectionMixin's _gas_halos, _pres_rowfn), _onepoint_launch is the only one that reaches the device."""
+
+    def _onepoint_request(self, ntheta, mmin, mmax, zweights):
+        """(u, w, (m_lo, m_hi), zw) of the shared tail of the one-point methods."""
+        u, w = ring_rule(ntheta)
+        ms = np.asarray(self.ms, dtype=np.float64)
+        for name, v in (("mmin", mmin), ("mmax", mmax)):
+            if v is not None and not (np.isscalar(v) and np.isfinite(v) and v > 0):
+                raise ValueError(f"{name} must be a finite positive mass or None, got {v!r}")
+        keep = np.nonzero((ms >= (ms[0] if mmin is None else mmin)) & (ms <= (ms[-1] if mmax is None else mmax)))[0]
+        if keep.size == 0:
+            raise ValueError(f"no point of the mass grid lies in mmin .. mmax = {mmin!r} .. {mmax!r}")
+        if zweights is None:
+            if self._nz < 2:
+                raise ValueError("zweights=None needs at least two redshifts (the default is a trapezoid rule over zs times "
+                                 "the comoving volume per steradian); give the weight of the one redshift")
+            zs = np.asarray(self.zs, dtype=np.float64)
+            chi = np.asarray(self.comoving_radial_distance(zs), dtype=np.float64).reshape(-1)
+            hz = np.asarray(self.hubble_parameter(zs), dtype=np.float64).reshape(-1)
+            zweights = trapz_weights(zs) * (constants.c / 1.0e3) * chi ** 2 / hz       # dz dV/dz/dOmega, comoving Mpc^3/sr
+        return u, w, (int(keep[0]), int(keep[-1]) + 1), check_zweights(zweights, self._nz)
+
+    def _profile_request(self, profiles, theta_out, ntheta, mmin, mmax, zweights):
+        u, w, window, zw = self._onepoint_request(ntheta, mmin, mmax, zweights)
+        shape = (self._nz, self._nm, u.size)
+        got = profiles.shape if isinstance(profiles, nat.DeviceArray) else np.shape(profiles)
+        if tuple(got) != shape:
+            raise ValueError(f"profiles must have shape (nz, nm, ntheta) = {shape}, got {tuple(got)}")
+        if not isinstance(profiles, nat.DeviceArray):
+            profiles = np.ascontiguousarray(profiles, dtype=np.float64)
+            if not np.all(np.isfinite(profiles)):
+                raise ValueError("profiles must be finite")
+        theta_out = np.asarray(theta_out, dtype=np.float64)
+        if theta_out.shape != shape[:2]:
+            raise ValueError(f"theta_out must have shape (nz, nm) = {shape[:2]}, got {theta_out.shape}")
+        if not np.all(np.isfinite(theta_out)) or np.any(theta_out <= 0):
+            raise ValueError("theta_out must be finite and positive")
+        area = (2.0 * np.pi * theta_out ** 2)[:, :, None] * (u * w)[None, None, :]
+        return dict(signal=profiles, amp=None, area=area, window=window, zw=zw)
+
+    def _y_request(self, truncate, fwhm, family, param_override, ntheta, mmin, mmax, zweights):
+        """The rings of every (zs, ms) halo's Compton-y profile: the arguments of the projection in scaled units, the
+        amplitudes and the solid angles, all on the host."""
+        u, w, window, zw = self._onepoint_request(ntheta, mmin, mmax, zweights)
+        if fwhm is not None and not (np.isscalar(fwhm) and np.isfinite(fwhm) and fwhm >= 0):
+            raise ValueError("fwhm must be finite and non-negative")
+        beam = float(fwhm or 0.0) / np.sqrt(8.0 * np.log(2.0))
+        rowfn = self._pres_rowfn(family, param_override)
+        Ms, halos = self._gas_halos(self.ms, None, truncate)
+        theta_out = [truncate * rvir / da + 5.0 * beam for _, da, _, rvir, _, _ in halos]
+        # (the operations of y_1h_profiles at the angles theta_out u)
+        x, alpha, eta, xcut, pref, rscale, (*_, gamma) = zip(*gasprofiles.halo_rings(
+            halos, rowfn, truncate, [tout[:, None] * u[None, :] for tout in theta_out]))
+        smooth = [da * beam / r for (_, da, *_), r in zip(halos, rscale)]
+        x, alpha, eta, xcut, smooth = (np.concatenate(a) for a in (x, alpha, eta, xcut, smooth))
+        pref, theta_out = np.stack(pref), np.stack(theta_out)
+        for name, a in (("the profile's parameters", np.concatenate([alpha, eta, xcut, pref.ravel()])), ("the ring radii", x)):
+            if not np.all(np.isfinite(a)):
+                raise ValueError(f"{name} are not finite")
+        area = (2.0 * np.pi * theta_out ** 2)[:, :, None] * (u * w)[None, None, :]
+        return dict(signal=None, proj=(x, alpha, gamma, eta, xcut, smooth if beam > 0 else None), amp=pref, area=area,
+                    window=window, zw=zw)
+
+    def _onepoint_launch(self, req, grid, per_z):
+        """The contraction of a checked request on the device; grid = (nlambda, dlambda), or None for the cumulants."""
+        ctx = self._main(needs_aux=True)
+        signal = req["signal"]
+        if signal is None:          # the profiles stay on the device
+            signal = gasprofiles.projected_gnfw_device(*req["proj"], ctx=ctx)
+        arrays = (signal, req["area"], self._d_nzm, self._d_wm(), req["zw"])
+        dims = (self._nz, self._nm, req["area"].shape[-1])
+        if grid is None:
+            out = _moments(ctx, arrays, req["amp"], dims, req["window"], per_z)
+        else:
+            out = _exponent(ctx, arrays, req["amp"], dims, req["window"], *grid, per_z)
+        self._sync_point()
+        return out
+
+    def profile_char_exponent(self, profiles, theta_out, nbins, ds, ntheta=DEFAULT_RINGS, mmin=None, mmax=None,
+                              zweights=None, per_z=False):
+        """The exponent A(lambda_j) of the characteristic function exp A of a field that is the sum of the profiles of
+        Poisson-placed halos of the model's mass function, on onepoint.lambda_grid(nbins, ds): complex (nbins / 2 + 1,),
+        or with per_z=True its rows (nz, nbins / 2 + 1).  profiles (nz, nm, ntheta), a host array or a device buffer, is
+        the profile of a halo of mass ms[m] at zs[z] at the angles theta_out[z, m] u_t [rad], u = onepoint.ring_rule(ntheta)
+        [0], and zero beyond theta_out (nz, nm) - built from kappa_1h_profiles, for instance.  zweights (nz,): the weight
+        of a redshift, default trapz_weights(zs) c chi^2 / H, the comoving volume per steradian that goes with the comoving
+        mass function; mmin, mmax: only the masses of the grid in [mmin, mmax].  onepoint.pdf_from_exponent turns the
+        result into the PDF.  Halo clustering is neglected; overlapping halos are not."""
+        grid = lambda_grid(nbins, ds)
+        req = self._profile_request(profiles, theta_out, ntheta, mmin, mmax, zweights)
+        return self._onepoint_launch(req, grid, bool(per_z))
+
+    def get_y_char_exponent(self, nbins, dy, truncate=1.0, fwhm=None, family=None, param_override=None,
+                            ntheta=DEFAULT_RINGS, mmin=None, mmax=None, zweights=None, per_z=False):
+        """profile_char_exponent of the Compton-y profile of y_1h_profiles (the Battaglia pressure profile cut at
+        truncate r_vir, Duffy concentrations; family and param_override as in add_battaglia_pres_profile) of every
+        (zs, ms) halo, on lambda_grid(nbins, dy).  The rings end at theta_out = truncate r_vir / D_A, with fwhm [rad] (the
+        beam the profile is convolved with) at 5 beam widths sigma = fwhm / sqrt(8 ln 2) beyond.  The profiles are
+        evaluated and contracted on the device."""
+        grid = lambda_grid(nbins, dy)
+        req = self._y_request(truncate, fwhm, family, param_override, ntheta, mmin, mmax, zweights)
+        return self._onepoint_launch(req, grid, bool(per_z))
+
+    def get_y_pdf(self, nbins, dy, ymin=0.0, noise_sigma=0.0, truncate=1.0, fwhm=None, family=None, param_override=None,
+                  ntheta=DEFAULT_RINGS, mmin=None, mmax=None, zweights=None, per_z=False):
+        """(ys, p): the one-point PDF of the Compton-y map in nbins bins of width dy from ymin, p the probability per bin
+        (nbins,), with Gaussian map noise of width noise_sigma - onepoint.pdf_from_exponent of get_y_char_exponent; see
+        there for the periodicity and for why noise_sigma >~ 2 dy.  per_z=True: p (nz, nbins), the PDF of each redshift's
+        halos alone."""
+        grid = lambda_grid(nbins, dy)
+        noise_sigma = check_noise(noise_sigma)
+        if not (np.isscalar(ymin) and np.isfinite(ymin)):
+            raise ValueError("ymin must be finite")
+        req = self._y_request(truncate, fwhm, family, param_override, ntheta, mmin, mmax, zweights)
+        A = self._onepoint_launch(req, grid, bool(per_z))
+        if not per_z:
+            return pdf_from_exponent(A, dy, ymin, noise_sigma)
+        rows = [pdf_from_exponent(a, dy, ymin, noise_sigma) for a in A]
+        return rows[0][0], np.stack([p for _, p in rows])
+
+    def get_y_cumulants(self, truncate=1.0, fwhm=None, family=None, param_override=None, ntheta=DEFAULT_RINGS,
+                        mmin=None, mmax=None, zweights=None, per_z=False):
+        """[<y>, kappa_2, kappa_3, kappa_4]: the mean and the second to fourth cumulant of the Compton-y map of
+        get_y_char_exponent (without noise), kappa_p = sum zw wm n a y^p; (4,), or with per_z=True (nz, 4)."""
+        req = self._y_request(truncate, fwhm, family, param_override, ntheta, mmin, mmax, zweights)
+        return self._onepoint_launch(req, None, bool(per_z))

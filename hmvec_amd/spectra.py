@@ -42,6 +42,20 @@ def resolve(name, hods, uk, pk):
     return Resolved(name, kind1, kind2, t1, t1 if kind2 == kind1 else _tensors(name, kind2, hods))
 
 
+def check_term(term, terms):
+    """Refuse a term of a request that is not one of `terms`."""
+    if term not in terms:
+        raise ValueError(f"term must be one of {terms}, got {term!r}")
+
+
+def _same_lookups(recs, what):
+    """Refuse a request of `what` that names something the 1-halo and 2-halo lookups resolve differently."""
+    for r in recs:
+        if not r.same:
+            raise ValueError(f"{what}: the 1-halo and 2-halo lookups resolve {r.name!r} differently (it names both an HOD "
+                             f"and a profile)")
+
+
 def first_name_rule(a, b):
     """Two different HOD (or two different pressure) names: the reference uses the first name's square term
     (hmvec/hmvec.py:510-513), so the spectrum depends on the order - the batched kernel computes each unordered pair

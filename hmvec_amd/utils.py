@@ -35,6 +35,12 @@ def vectorized_bisection_search(x, inv_func, ybounds, monotonicity, rtol=1e-4, v
     return mid
 
 
+def _R_from_M(M, rho, delta):
+    """hmvec/hmvec.py:627-628 for the handful of grid radii the constructor needs (host input
+    preparation; the public, device-backed R_from_M lives in functions.py)."""
+    return (3.0 * M / 4.0 / np.pi / delta / rho) ** (1.0 / 3.0)
+
+
 def interp(x, y, bounds_error=False, fill_value=0.0, **kwargs):
     """hmvec/utils.py:6-7: thin scipy wrapper used by the cosmology layer."""
     from scipy.interpolate import interp1d
