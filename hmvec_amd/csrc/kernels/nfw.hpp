@@ -26,6 +26,8 @@ constexpr int NFW_NT1 = 5;          // terms for (1+c) x <= NFW_XS1
 constexpr double NFW_XS1 = 0.1;
 constexpr int NFW_NT2 = 8;          // terms for (1+c) x <= NFW_XS2
 constexpr double NFW_XS2 = 0.8;
+constexpr int NFW_NQ = 10;          // a_1 .. a_NFW_NQ of a row with c < NFW_CQ come from quadrature (nfw_series_row)
+constexpr double NFW_CQ = 1.5;
 // With 32 terms the series stays within 3e-15 (absolute, against 50-digit arithmetic, c in [0.5, 100])
 // up to (1+c) x = 10: the band 4 < (1+c) x <= 10 - where x itself is still on the small-argument
 // branch of Si/Ci, the most expensive case of the closed form - costs 32 FMAs instead.
@@ -41,7 +43,13 @@ __device__ __forceinline__ void nfw_series_row(double c, double* __restrict__ a)
     a[NFW_NS2 + 3] = 0.0;
     a[0] = (c >= 0.5) ? 1.0 : 0.0;
     // unrolled: 1/(p-1) becomes a compile-time factor (a division here is ~15 dependent instructions in a
-    // 62-step chain); coefficients stay within 5e-15 of 80-digit arithmetic for c in [0.5, 100]
+    // 62-step chain).  The recurrence carries the rounding errors of J_0 and J_1 = m_c (up to 1.5e-16) into every J_p
+    // undamped, as (-1)^p (alpha + beta p): harmless where J_p grows with p, but below c = 1.25 the low moments, the
+    // ones that matter at (1+c) x = 10, lose up to 1.3e-13 of the row's largest term to it.  Rows with c < NFW_CQ
+    // therefore take J_3 .. J_(2 NFW_NQ + 1) from a 16-point Gauss-Legendre rule instead (a positive integrand, the
+    // pole at t = -1 far off: full double precision, checked for c in [0.5, 1.5)).  With that the coefficients stay
+    // within 5e-15 of 60-digit arithmetic for c in [0.5, 100], measured as |da_n| x^(2n) over the row's largest term
+    // at (1+c) x = 10 (worst 1.5e-15: tests/test_nfw_cpu.py).
 #pragma unroll
     for (int p = 2; p < 2 * NFW_NS2; ++p) {
         const double jp = cp * (1.0 / (double)(p - 1)) - 2.0 * jm1 - jm2;
@@ -52,6 +60,26 @@ __device__ __forceinline__ void nfw_series_row(double c, double* __restrict__ a)
         }
         jm2 = jm1;
         jm1 = jp;
+    }
+    if (c >= 0.5 && c < NFW_CQ) {
+        constexpr double GX[8] = {0.09501250983763744, 0.2816035507792589, 0.45801677765722737, 0.6178762444026438, 0.755404408355003, 0.8656312023878318, 0.9445750230732326, 0.9894009349916499};
+        constexpr double GW[8] = {0.1894506104550685, 0.18260341504492358, 0.16915651939500254, 0.14959598881657674, 0.12462897125553388, 0.09515851168249279, 0.062253523938647894, 0.027152459411754096};
+        const double h = 0.5 * c;
+        double acc[NFW_NQ];
+#pragma unroll
+        for (int n = 0; n < NFW_NQ; ++n) acc[n] = 0.0;
+#pragma unroll      // (the 16 nodes are independent chains: one thread per row, so latency is the cost)
+        for (int i = 0; i < 16; ++i) {
+            const double t = h * ((i & 1) ? -GX[i >> 1] : GX[i >> 1]) + h, d = 1.0 + t, t2 = t * t;
+            double pw = (h * GW[i >> 1]) / (d * d) * t;      // w t / (1+t)^2
+#pragma unroll
+            for (int n = 0; n < NFW_NQ; ++n) {
+                pw *= t2;
+                acc[n] += pw;                                 // J_(2n+3)
+            }
+        }
+#pragma unroll
+        for (int n = 1; n <= NFW_NQ; ++n) a[n] = ((n & 1) ? -acc[n - 1] : acc[n - 1]) * INVFACT[n] * inv_mc;
     }
 }
 __global__ void nfw_series_kernel(int rows, const double* __restrict__ cs, double* __restrict__ acoef) {

@@ -5,12 +5,16 @@ large-argument form - is hit), mass definition, mass function, feedback family, 
 the workgroup-FFT and the rocFFT route (nxs = 5000: the compile-time plan, whose first pass is pruned or not and whose
 second pass takes 3-of-5 or full butterflies depending on xmax), HOD correlation mode, miscentred centrals, pressure."""
 import os
+import sys
 
 import numpy as np
 import pytest
 import scipy.constants as sc
 
 from conftest import merged_params, power_close, rel_err
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from nfw_model import BANDS, bands  # noqa: E402  (bands: band() over arrays)
 
 pytestmark = pytest.mark.gpu
 
@@ -102,9 +106,12 @@ def test_random_configuration_against_oracle(seed, alpha_table):
 
 
 def test_fuzz_draws_cover_every_nfw_branch():
-    """The sixteen draws together must exercise all four evaluation branches of nfw_kernel."""
+    """The sixteen draws together must exercise all four evaluation branches of nfw_kernel - and, counted by the
+    kernel's own ladder (helpers/nfw_model.py), every form those branches split into that a drawn grid can reach.  Two
+    it cannot: the closed form needs c < 0.5 or (1+c) x >= 1e9, and the collapsed form with both arguments below 8 needs
+    c < 1, while the concentrations of the draws stay above 1.  tests/test_gpu_nfw_bands.py runs those."""
     import hmvec_amd as hm
-    hits = np.zeros(4)
+    hits, forms, cmin = np.zeros(4), np.zeros(len(BANDS), dtype=int), np.inf
     for seed in range(16):
         c = draw(seed)
         h = hm.HaloModel(c["zs"], c["ks"], ms=c["ms"], params=dict(c["params"]), mdef=c["mdef"],
@@ -114,4 +121,9 @@ def test_fuzz_draws_cover_every_nfw_branch():
         x = c["ks"][None, None, :] * rs[..., None] * (1 + c["zs"][:, None, None])
         xc = (1 + cs[..., None]) * x
         hits += [np.sum(xc <= 4), np.sum((xc > 4) & (xc <= 10)), np.sum((xc > 10) & (x <= 4)), np.sum(x > 4)]
+        forms += np.bincount(bands(cs[..., None], x).ravel(), minlength=len(BANDS))
+        cmin = min(cmin, float(cs.min()))
+    forms = dict(zip(BANDS, forms.tolist()))
+    print(forms, "smallest concentration", cmin)
     assert np.all(hits > 50), hits
+    assert all(forms[b] > 50 for b in BANDS if b not in ("closed", "col<8")) and cmin > 1.0, (forms, cmin)
