@@ -16,6 +16,9 @@ from .lensing import delta_sigma_nfw, sigma_nfw  # noqa: F401  (cluster lensing:
 from .gasprofiles import projected_gnfw  # noqa: F401  (projected gas and pressure profiles: Sigma_gas, tau, y)
 from .realspace import projected_from_power, xi_from_power  # noqa: F401  (xi(r) and the J0 / J2 transforms of a tabulated spectrum)
 from .angular import angular_from_power  # noqa: F401  (w(theta), gamma_t(theta), xi+-(theta): the J0 / J2 / J4 transforms at chi theta, summed over z)
+from .angcov import (angular_cov, angular_cov_spectra_device, bin_averaged_bessel, bin_averaged_bessel_device, binned_angular_from_cl,  # noqa: F401
+                     binned_angular_from_cl_device, project_cl_cov, project_cl_cov_device, real_cov_gaussian,
+                     real_cov_gaussian_device)  # (covariance of the angular correlation functions: Gaussian part, projection of (l, l') matrices)
 from .cov import (GaussianCov, bin_annuli, cl_cov_1halo, cl_cov_ssc, lensing_shape_noise, limber_samples,  # noqa: F401
                   shot_noise, sigma_b_disc)  # (covariances)
 from .bispectrum import F2, cl_bispectrum, tree_bispectrum  # noqa: F401  (bispectrum of three tracers)
@@ -23,11 +26,14 @@ from .rsd import legendre_weights, mu_rule, virial_dispersion  # noqa: F401  (re
 from .onepoint import char_exponent, cumulants, lambda_grid, pdf_from_exponent, ring_rule  # noqa: F401  (one-point PDF of a sum of halo profiles)
 from .hod_ensemble import central_differences, hod_sets, stencil  # noqa: F401  (HOD parameter ensembles: P_gg, P_gm of many sets)
 from . import hod_ensemble  # noqa: F401
-from . import angular, bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils  # noqa: F401
+from . import angcov, angular, bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils  # noqa: F401
 from .functions import __all__ as _fn_all
 
 __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "generic_profile_fft", "sigma_nfw",
            "delta_sigma_nfw", "xi_from_power", "projected_from_power", "angular_from_power", "angular",
+           "bin_averaged_bessel", "bin_averaged_bessel_device", "real_cov_gaussian", "real_cov_gaussian_device",
+           "binned_angular_from_cl", "binned_angular_from_cl_device", "project_cl_cov", "project_cl_cov_device", "angular_cov",
+           "angular_cov_spectra_device", "angcov",
            "GaussianCov", "bin_annuli", "shot_noise", "lensing_shape_noise", "cl_cov_1halo", "limber_samples", "cov",
            "cl_cov_ssc", "sigma_b_disc",
            "F2", "tree_bispectrum", "cl_bispectrum", "bispectrum",

@@ -1,0 +1,358 @@
+"""Covariance of angular correlation functions on the GPU: error bars for the real-space 3x2pt
+data vector of section 22 (``get_w_theta``, ``get_gamma_t``, ``get_xi_pm``).
+
+Flat sky and section 22's J_mu convention, xi_mu^{ab}(theta) = 1/(2 pi) int l dl J_mu(l theta) C^{ab}(l), mu in {0, 2, 4}.
+For an annulus [a, b], 0 < a < b in radians, the bin-averaged kernel is
+
+    K_mu(l; a, b) = 2 / ((b^2 - a^2) l^2) [F_mu(l b) - F_mu(l a)],
+    F_0(x) = x J1(x),   F_2(x) = -x J1(x) - 2 J0(x),   F_4(x) = (x - 24/x) J1(x) + 8 J0(x).
+
+Spectra: nf fields, C[f, g, n] symmetric in (f, g) at the nodes ells[n] (strictly increasing floats >= 1, at least two);
+C(l) is linear in l between nodes and zero outside [ells[0], ells[-1]]; noise[f] >= 0 is a white noise level per field
+(1/nbar for counts, sigma_eps^2/nbar for shear).  The multipole sum runs over the integers
+L = {ceil(ells[0]), ..., floor(ells[-1])}: a caller who passes every integer as a node gets no interpolation at all.
+A probe is (f, g, mu); with P = (a, b, mu), Q = (c, d, nu), bins from theta_edges and the survey area A = 4 pi fsky,
+
+    cov[P,i,Q,j] = 1/(2 pi A) sum_{l in L} l K_mu(l; bin i) K_nu(l; bin j) [C^^ac C^^bd + C^^ad C^^bc - NN](l)
+                 + delta_ij delta_mu,nu (delta_ac delta_bd + delta_ad delta_bc) N_a N_b / (A pi (b_i^2 - a_i^2)),
+
+C^^fg = C^fg + delta_fg N_f and NN = (delta_ac delta_bd + delta_ad delta_bc) N_a N_b.  The noise x noise product is a
+delta function in theta and its l sum does not converge: it is taken out of the sum and added in closed form
+(int l dl J_mu(l theta) J_mu(l theta') = delta(theta - theta')/theta, averaged over both bins, gives 2/(b^2 - a^2));
+for mu != nu it is dropped altogether - Cov(xi+, xi-) has no pure shape-noise term, the E- and B-mode noise cancel.
+
+The node weights R_mu[i, n] = sum_{l in L} l K_mu(l; bin i) h_n(l), h_n the hat function of node n, give the bin-averaged
+correlation function of the same discretisation, R_mu C / (2 pi), and project any (l, l') matrix M that is bilinear
+between nodes - cov.cl_cov_1halo's or cov.cl_cov_ssc's output - to real space, R_mu M R_nu^T / (4 pi^2).  The projection
+is linear and takes one matrix at a time; section 17's warning about the two measures of those matrices stays with the
+caller.  The kernels are in hmvec_amd/csrc/kernels/angcov.hpp.
+"""
+import ctypes as C_
+
+import numpy as np
+
+from . import _native as nat
+from . import realspace, spectra
+from .cosmology import _limber_device
+
+__all__ = ["bin_averaged_bessel", "bin_averaged_bessel_device", "real_cov_gaussian", "real_cov_gaussian_device",
+           "binned_angular_from_cl", "binned_angular_from_cl_device", "project_cl_cov", "project_cl_cov_device",
+           "angular_cov_spectra_device", "angular_cov"]
+
+ORDERS = (0, 2, 4)
+
+
+def chunk():
+    """Multipoles per partial sum of the contraction (HMG_ANGCOV_CHUNK of include/hmgrid.h)."""
+    return nat.DEFINES["HMG_ANGCOV_CHUNK"]
+
+
+def check_orders(orders):
+    """The orders of a request as a tuple of ints out of 0, 2, 4, and whether they were given as a sequence."""
+    seq = isinstance(orders, (tuple, list))
+    out = tuple(orders) if seq else (orders,)
+    if not out or any(isinstance(o, bool) or not isinstance(o, (int, np.integer)) or o not in ORDERS for o in out):
+        raise ValueError(f"an order must be 0, 2 or 4, got {orders!r}")
+    return tuple(int(o) for o in out), seq
+
+
+def check_edges(theta_edges):
+    """The bin edges as a float64 vector of at least two finite, positive, strictly increasing angles."""
+    e = np.asarray(theta_edges, dtype=np.float64)
+    if e.ndim != 1 or e.size < 2:
+        raise ValueError(f"theta_edges must be a vector of at least two angles, got shape {e.shape}")
+    if not np.all(np.isfinite(e)) or np.any(e <= 0) or np.any(np.diff(e) <= 0):
+        raise ValueError("theta_edges must be finite, positive and strictly increasing")
+    return np.ascontiguousarray(e)
+
+
+def check_nodes(ells):
+    """The nodes as a float64 vector (finite, >= 1, strictly increasing, at least two) and (l0, nl) of the integers
+    L = l0 .. l0 + nl - 1 between the first and the last."""
+    n = np.asarray(ells, dtype=np.float64)
+    if n.ndim != 1 or n.size < 2:
+        raise ValueError(f"ells must be a vector of at least two nodes, got shape {n.shape}")
+    if not np.all(np.isfinite(n)) or np.any(np.diff(n) <= 0):
+        raise ValueError("ells must be finite and strictly increasing")
+    if n[0] < 1:
+        raise ValueError(f"ells[0] must be at least 1, got {n[0]}")
+    l0, l1 = int(np.ceil(n[0])), int(np.floor(n[-1]))
+    if l1 < l0 or l1 >= 2 ** 31 - 1:
+        raise ValueError("ells must hold at least one integer multipole below 2^31 between its ends")
+    return np.ascontiguousarray(n), l0, l1 - l0 + 1
+
+
+def check_multipoles(ells_int):
+    """Multipoles of bin_averaged_bessel: a float64 vector of finite, positive, integer-valued numbers."""
+    l = np.asarray(ells_int, dtype=np.float64)
+    if l.ndim != 1 or not np.all(np.isfinite(l)) or np.any(l < 1) or np.any(l != np.rint(l)):
+        raise ValueError("ells_int must be a vector of integers >= 1")
+    return np.ascontiguousarray(l)
+
+
+def check_probes(probes, nf):
+    """The probes (f, g, mu) as an (np, 3) int32 array of (f, g, mu / 2)."""
+    out = []
+    for p in probes:
+        if len(p) != 3:
+            raise ValueError(f"a probe is (f, g, order), got {p!r}")
+        f, g, mu = p
+        (mu,), _ = check_orders(mu)
+        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (f, g)) or not (0 <= f < nf and 0 <= g < nf):
+            raise ValueError(f"probe {p!r} names a field outside 0 .. {nf - 1}")
+        out.append((int(f), int(g), mu // 2))
+    if not out:
+        raise ValueError("at least one probe is needed")
+    return np.ascontiguousarray(out, dtype=np.int32)
+
+
+def check_noise(noise, nf):
+    n = np.asarray(noise, dtype=np.float64)
+    if n.shape != (nf,) or not np.all(np.isfinite(n)):
+        raise ValueError(f"noise must be a finite vector of {nf} levels, got shape {n.shape}")
+    if np.any(n < 0):
+        raise ValueError("a noise level is negative")
+    return np.ascontiguousarray(n)
+
+
+def check_fsky(fsky):
+    fsky = float(fsky)
+    if not (np.isfinite(fsky) and fsky > 0):
+        raise ValueError(f"fsky must be positive, got {fsky}")
+    return fsky
+
+
+def check_spectra(C, nn):
+    """The spectra as they go to the device: a DeviceArray of shape (nf, nf, nn) as it is (its entries with f <= g are
+    the ones read), a host array checked to be finite and symmetric in the fields.  (array, nf)."""
+    if isinstance(C, nat.DeviceArray):
+        if len(C.shape) != 3 or C.shape[0] != C.shape[1] or C.shape[2] != nn or C.shape[0] < 1:
+            raise ValueError(f"C must have shape (nf, nf, {nn}), got {C.shape}")
+        return C, C.shape[0]
+    C = np.asarray(C, dtype=np.float64)
+    if C.ndim != 3 or C.shape[0] != C.shape[1] or C.shape[2] != nn or C.shape[0] < 1:
+        raise ValueError(f"C must have shape (nf, nf, {nn}), got {C.shape}")
+    if not np.all(np.isfinite(C)):
+        raise ValueError("C must be finite")
+    if not np.array_equal(C, C.transpose(1, 0, 2)):
+        raise ValueError("C must be symmetric in its two fields")
+    return np.ascontiguousarray(C), C.shape[0]
+
+
+def weights_device(ctx, d_ells, nl, edges, orders):
+    """{order: DeviceArray (nl, nt)} of K_order at nl device multipoles: one launch for all the orders."""
+    nt = edges.size - 1
+    d_edges = ctx.upload(edges)
+    K = {o: ctx.empty((nl, nt)) for o in dict.fromkeys(orders)}
+    ctx.call("hmg_angcov_weights", nl, nt, d_ells.ptr, d_edges.ptr, *(nat.ptr(K.get(o)) for o in ORDERS))
+    return K
+
+
+def _range_weights(ctx, l0, nl, edges, orders):
+    return weights_device(ctx, ctx.upload(np.arange(l0, l0 + nl, dtype=np.float64)), nl, edges, orders)
+
+
+def bin_averaged_bessel_device(ells_int, theta_edges, orders, *, ctx=None):
+    """bin_averaged_bessel with the results left on the device: a dict {order: DeviceArray (len(ells_int), ntheta)}."""
+    orders, _ = check_orders(orders)
+    ells, edges = check_multipoles(ells_int), check_edges(theta_edges)
+    ctx = nat.context_or_default(ctx)
+    if ells.size == 0:
+        return {o: ctx.empty((0, edges.size - 1)) for o in orders}
+    return weights_device(ctx, ctx.upload(ells), ells.size, edges, orders)
+
+
+def bin_averaged_bessel(ells_int, theta_edges, orders, *, ctx=None):
+    """K_order[l, i] = 2 / ((b_i^2 - a_i^2) l^2) [F_order(l b_i) - F_order(l a_i)], the average of J_order(l theta) over
+    the annulus [a_i, b_i] = theta_edges[i : i + 2] weighted with theta, at the integer multipoles ells_int (>= 1).
+
+    theta_edges: ntheta + 1 angles in radians, positive and strictly increasing.  orders: 0, 2, 4 or a sequence of
+    them.  Returns a float64 array (len(ells_int), ntheta), or a tuple of them for a sequence of orders; a value depends
+    on its multipole and its two edges alone.  Anything else raises ValueError before a launch."""
+    orders, seq = check_orders(orders)
+    K = bin_averaged_bessel_device(ells_int, theta_edges, orders, ctx=ctx)
+    outs = tuple(K[o].numpy() if K[o].size else np.empty(K[o].shape) for o in orders)
+    return outs if seq else outs[0]
+
+
+def real_cov_gaussian_device(ells, C, noise, theta_edges, probes, fsky, *, ctx=None):
+    """real_cov_gaussian with the result left on the device: a DeviceArray (nprobe, ntheta, nprobe, ntheta).  C may be a
+    DeviceArray (nf, nf, len(ells)): it is taken as it is, and of its entries those with f <= g are read."""
+    nodes, l0, nl = check_nodes(ells)
+    C, nf = check_spectra(C, nodes.size)
+    noise, edges, fsky = check_noise(noise, nf), check_edges(theta_edges), check_fsky(fsky)
+    pr = check_probes(probes, nf)
+    ctx = nat.context_or_default(ctx)
+    nt, np_ = edges.size - 1, pr.shape[0]
+    K = _range_weights(ctx, l0, nl, edges, [ORDERS[o] for o in sorted(set(pr[:, 2].tolist()))])
+    words = np_ * (np_ + 1) // 2 * ((nl - 1) // chunk() + 1) * nt * nt
+    work, cov = ctx.empty((words,)), ctx.empty((np_, nt, np_, nt))
+    d_nodes, d_C, d_noise, d_edges, d_pr = ctx.upload(nodes), nat.as_device(ctx, C), ctx.upload(noise), ctx.upload(edges), ctx.upload_int32(pr)
+    ctx.call("hmg_angcov_gaussian", nf, nodes.size, d_nodes.ptr, d_C.ptr, d_noise.ptr, l0, nl, nt, d_edges.ptr, np_,
+             pr.ctypes.data_as(C_.POINTER(C_.c_int)), d_pr.ptr, 4.0 * np.pi * fsky,
+             *(nat.ptr(K.get(o)) for o in ORDERS), words, work.ptr, cov.ptr)
+    return cov
+
+
+def real_cov_gaussian(ells, C, noise, theta_edges, probes, fsky, *, ctx=None):
+    """Gaussian covariance cov[P, i, Q, j] of the bin-averaged correlation functions xi_mu^{ab}(bin i) of the probes
+    P = (a, b, mu), shape (nprobe, ntheta, nprobe, ntheta); the definition is the module's.
+
+    ells: the nodes of the spectra, strictly increasing, ells[0] >= 1, at least two.  C: (nf, nf, len(ells)), symmetric
+    in the fields, WITHOUT noise.  noise: (nf,) white noise levels >= 0.  theta_edges: ntheta + 1 bin edges in radians,
+    positive and strictly increasing.  probes: a sequence of (f, g, mu) with fields 0 .. nf - 1 and mu in {0, 2, 4}.
+    fsky > 0: the survey covers A = 4 pi fsky.
+
+    Noise convention: the noise x noise part of the sum over l does not converge (it is a delta function in theta); it
+    is left out of the sum and added in closed form on the diagonal i = j of blocks with mu = nu,
+    (delta_ac delta_bd + delta_ad delta_bc) N_a N_b / (A pi (b_i^2 - a_i^2)), and dropped for mu != nu (Cov(xi+, xi-)
+    has no pure shape-noise term).  The signal x noise terms are in the sum.
+
+    An element depends on its own two probes, its two bins, the spectra and L alone: a call with a subset of the
+    probes or bins returns the bits of the full call, a repeat returns the same bits, cov[P,i,Q,j] == cov[Q,j,P,i]
+    and swapping (f, g) inside a probe changes nothing.  Anything invalid raises ValueError before a launch."""
+    return real_cov_gaussian_device(ells, C, noise, theta_edges, probes, fsky, ctx=ctx).numpy()
+
+
+def node_weights_device(ctx, nodes, l0, nl, edges, order, scale=1.0, by_node=False):
+    """scale * R_order as a DeviceArray (ntheta, nn), or (nn, ntheta) with by_node."""
+    nt = edges.size - 1
+    K = _range_weights(ctx, l0, nl, edges, (order,))[order]
+    R = ctx.empty((nodes.size, nt) if by_node else (nt, nodes.size))
+    ctx.call("hmg_angcov_node_weights", nodes.size, ctx.upload(nodes).ptr, l0, nl, nt, K.ptr, float(scale), int(by_node), R.ptr)
+    return R
+
+
+def _matmul(ctx, A, B):
+    """A (n, k) times B (k, m) on the device, every output one fma chain over k in index order (hmg_angular_zsum)."""
+    (n, k), m = A.shape, B.shape[1]
+    out = ctx.empty((n, m))
+    ctx.call("hmg_angular_zsum", 1, k, m, n, A.ptr, B.ptr, out.ptr)
+    return out
+
+
+def binned_angular_from_cl_device(ells, C, theta_edges, order, *, ctx=None):
+    """binned_angular_from_cl with the result left on the device: a DeviceArray (ns, ntheta) for C of shape (ns, nn) (a
+    host array or a DeviceArray)."""
+    (order,), _ = check_orders(order)
+    nodes, l0, nl = check_nodes(ells)
+    edges = check_edges(theta_edges)
+    if not isinstance(C, nat.DeviceArray):
+        C = np.asarray(C, dtype=np.float64)
+        if not np.all(np.isfinite(C)):
+            raise ValueError("C must be finite")
+    if len(C.shape) != 2 or C.shape[1] != nodes.size or C.shape[0] < 1:
+        raise ValueError(f"C must have shape (ns, {nodes.size}) with ns >= 1, got {tuple(C.shape)}")
+    ctx = nat.context_or_default(ctx)
+    R = node_weights_device(ctx, nodes, l0, nl, edges, order, 0.5 / np.pi, by_node=True)
+    return _matmul(ctx, nat.as_device(ctx, C), R)
+
+
+def binned_angular_from_cl(ells, C, theta_edges, order, *, ctx=None):
+    """Bin-averaged correlation function xi_order(bin i) = R_order[i, :] . C / (2 pi) of the spectra C[..., :] at the
+    nodes ells (C linear in l between nodes, summed over the integers L): the discretisation real_cov_gaussian is the
+    covariance of.  Arguments as for real_cov_gaussian; returns C's leading shape with ntheta last."""
+    Ch = np.asarray(C, dtype=np.float64)
+    if Ch.ndim < 1:
+        raise ValueError("C must have the nodes as its last axis")
+    flat = Ch.reshape(-1, Ch.shape[-1])
+    nt = np.size(theta_edges) - 1
+    if flat.shape[0] == 0:
+        check_orders(order), check_nodes(ells), check_edges(theta_edges)
+        return np.empty(Ch.shape[:-1] + (nt,))
+    return binned_angular_from_cl_device(ells, flat, theta_edges, order, ctx=ctx).numpy().reshape(Ch.shape[:-1] + (nt,))
+
+
+def project_cl_cov_device(M, ells, theta_edges, order1, order2, *, ctx=None):
+    """project_cl_cov with the result left on the device: a DeviceArray (ntheta, ntheta).  M: a host array or a
+    DeviceArray of shape (nn, nn)."""
+    (o1,), _ = check_orders(order1)
+    (o2,), _ = check_orders(order2)
+    nodes, l0, nl = check_nodes(ells)
+    edges = check_edges(theta_edges)
+    if not isinstance(M, nat.DeviceArray):
+        M = np.asarray(M, dtype=np.float64)
+        if not np.all(np.isfinite(M)):
+            raise ValueError("M must be finite")
+    if tuple(M.shape) != (nodes.size, nodes.size):
+        raise ValueError(f"M must have shape ({nodes.size}, {nodes.size}), got {tuple(M.shape)}")
+    ctx = nat.context_or_default(ctx)
+    R1 = node_weights_device(ctx, nodes, l0, nl, edges, o1, 0.5 / np.pi)
+    R2 = node_weights_device(ctx, nodes, l0, nl, edges, o2, 0.5 / np.pi, by_node=True)
+    return _matmul(ctx, _matmul(ctx, R1, nat.as_device(ctx, M)), R2)
+
+
+def project_cl_cov(M, ells, theta_edges, order1, order2, *, ctx=None):
+    """R_order1 M R_order2^T / (4 pi^2), shape (ntheta, ntheta): an (l, l') covariance M[n, m] given at the nodes ells
+    (bilinear between nodes; cov.cl_cov_1halo's or cov.cl_cov_ssc's output) as the covariance of the bin-averaged
+    xi_order1(bin i) and xi_order2(bin j).  Linear in M, one matrix at a time: which measure M carries (section 17) is
+    the caller's to keep track of."""
+    return project_cl_cov_device(M, ells, theta_edges, order1, order2, ctx=ctx).numpy()
+
+
+def angular_cov_spectra_device(model, fields, ells, term="total"):
+    """The spectra angular_cov contracts, for a HaloModel `model`: (labels, C, noise) with C a DeviceArray
+    (nf, nf, len(ells)), C[f, g] = model.limber_integral(ells, zs, ks, P_fg, zs, W_f, W_g, h_of_z(zs),
+    comoving_radial_distance(zs)) of the `term` ("total", "1h", "2h") of the spectrum of the two fields' tracers, and
+    noise the (nf,) host vector of the fields' noise levels.  fields: {label: (tracer name, window (nz,) in
+    limber_integral's convention, noise level)}.  The spectra of all the pairs come from one pass over the profile
+    tensors (get_power_all's) and are projected on the device; nothing of them crosses to the host, and the model's
+    cached spectra are not touched."""
+    spectra.check_term(term, model._XI_TERMS)
+    realspace.check_ks(model.ks)
+    nodes, _, _ = check_nodes(ells)
+    labels = list(fields)
+    if not labels:
+        raise ValueError("fields must name at least one field")
+    nz, nk, nf, nn = model._nz, model._nk, len(labels), nodes.size
+    names, windows, noise = [], [], []
+    for lab in labels:
+        try:
+            name, window, level = fields[lab]
+        except (TypeError, ValueError):
+            raise ValueError(f"fields[{lab!r}] must be (tracer name, window, noise)") from None
+        window = np.asarray(window, dtype=np.float64)
+        if window.shape != (nz,) or not np.all(np.isfinite(window)):
+            raise ValueError(f"the window of field {lab!r} must be a finite vector of {nz} values on the model's redshifts")
+        names.append(name), windows.append(window), noise.append(level)
+    noise = check_noise(noise, nf)
+    fg = [(f, g) for f in range(nf) for g in range(f, nf)]
+    rpairs = model._resolve_pairs([(names[f], names[g]) for f, g in fg])
+    if term != "1h":
+        model._tsz_notice(*dict.fromkeys(r for rp in rpairs for r in rp))
+    ctx, n = model._ctx(), len(fg)
+    blk = ctx.empty((2 * n, nz, nk))
+    o1 = [blk.view(i * nz * nk, (nz, nk)) for i in range(n)]
+    o2 = [blk.view((n + i) * nz * nk, (nz, nk)) for i in range(n)]
+    model._power_batch(rpairs, o1, o2)
+    rows = model._xi_rows(blk.view(0, (n * nz, nk)), blk.view(n * nz * nk, (n * nz, nk)), term)
+    zs = np.reshape(model.zs, -1)
+    hzs, chis = model.h_of_z(zs), model.comoving_radial_distance(zs)
+    Ctab = ctx.empty((nf, nf, nn))
+    for i, (f, g) in enumerate(fg):
+        out = Ctab.view((f * nf + g) * nn, (nn,))
+        _limber_device(ctx, nodes, zs, model.ks, rows.view(i * nz * nk, (nz, nk)), zs, windows[f], windows[g], hzs, chis,
+                       out=out)
+        if f != g:
+            ctx.call("hmg_memcpy_d2d", Ctab.view((g * nf + f) * nn, (nn,)).ptr, out.ptr, out.nbytes)
+    return labels, Ctab, noise
+
+
+def angular_cov(model, theta_edges, probes, fields, fsky, ells, term="total"):
+    """Gaussian covariance cov[P, i, Q, j], shape (nprobe, ntheta, nprobe, ntheta), of the bin-averaged angular
+    correlation functions of a HaloModel's tracers: the probes are (label, label2, mu), mu in {0, 2, 4}, the bins
+    theta_edges (radians), the survey's sky fraction fsky.  Bit for bit real_cov_gaussian(ells, C, noise, theta_edges,
+    probes by field index, fsky) with (labels, C, noise) = angular_cov_spectra_device(model, fields, ells, term).
+    fields: {label: (tracer name, window (nz,) in limber_integral's convention, noise level)}; ells: the nodes the
+    spectra are projected on (strictly increasing, >= 1).  The noise x noise term is added in closed form on the
+    diagonal of blocks with mu = nu and dropped for mu != nu (real_cov_gaussian's convention).  A function of the
+    model, like cov.cl_cov_1halo and cov.cl_cov_ssc: the attribute surface of HaloModel is pinned
+    (tests/test_facade_cpu.py) and stays as it is."""
+    labels, Ctab, noise = angular_cov_spectra_device(model, fields, ells, term)
+    index = {lab: i for i, lab in enumerate(labels)}
+    pr = []
+    for p in probes:
+        if len(p) != 3 or p[0] not in index or p[1] not in index:
+            raise ValueError(f"probe {p!r} must be (label, label2, order) with labels out of {labels}")
+        pr.append((index[p[0]], index[p[1]], p[2]))
+    return real_cov_gaussian_device(ells, Ctab, noise, theta_edges, pr, fsky, ctx=model._ctx()).numpy()

@@ -688,6 +688,11 @@ def _cached_upload(ctx, arr):
 
 
 def _limber(ctx, ells, zs, ks, Pzks, gzs, Wz1s, Wz2s, hzs, chis):
+    return _limber_device(ctx, ells, zs, ks, Pzks, gzs, Wz1s, Wz2s, hzs, chis).numpy().reshape(np.shape(ells))
+
+
+def _limber_device(ctx, ells, zs, ks, Pzks, gzs, Wz1s, Wz2s, hzs, chis, out=None):
+    """_limber with C_ell left on the device: a DeviceArray (nells,), `out` if one is given."""
     ells = np.ascontiguousarray(ells, dtype=np.float64)
     zs = np.atleast_1d(np.asarray(zs, dtype=np.float64))
     ks = np.asarray(ks, dtype=np.float64)
@@ -710,7 +715,7 @@ def _limber(ctx, ells, zs, ks, Pzks, gzs, Wz1s, Wz2s, hzs, chis):
     # small inputs (multipoles, grids, window products) are kept on the device between calls: a Limber
     # projection of device-resident spectra then costs one launch and one small copy back
     d = [_cached_upload(ctx, a) for a in (ells, zs, ks, gzs, pref, chis + 0.0 * gzs, wz)]
-    out = ctx.empty((ells.size,))
+    out = ctx.empty((ells.size,)) if out is None else out
     ctx.call("hmg_limber", ells.size, d[0].ptr, zs.size, ks.size, d[1].ptr, d[2].ptr, dP.ptr, nat.ptr(dP2),
              gzs.size, d[3].ptr, d[4].ptr, d[5].ptr, d[6].ptr, out.ptr)
-    return out.numpy().reshape(np.shape(ells))
+    return out

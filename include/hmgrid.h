@@ -690,6 +690,44 @@ int hmg_angular_transform(hmg_ctx* ctx, int n, int nz, int nk, int nt, const dou
 int hmg_angular_zsum(hmg_ctx* ctx, int n, int nz, int nt, int nw, const double* d_zw, const double* d_w,
                      double* d_out);
 
+/* ---- covariance of angular correlation functions -------------------------------------------
+ * Flat sky, section 22's J_mu convention; mu = 0, 2, 4 is named by its index o = mu / 2.  For the annulus [a, b],
+ *   K_mu(l; a, b) = 2 / ((b^2 - a^2) l^2) [F_mu(l b) - F_mu(l a)],
+ *   F_0(x) = x J1(x),   F_2(x) = -x J1(x) - 2 J0(x),   F_4(x) = (x - 24/x) J1(x) + 8 J0(x),
+ * the bin average of J_mu(l theta).  Spectra: d_C (nf, nf, nn), symmetric in the fields (the entry with f <= g is the
+ * one read), at the nodes d_nodes (nn >= 2, strictly increasing, >= 1); C(l) is linear in l between nodes; d_noise (nf)
+ * white noise levels >= 0.  The multipoles are the integers L = l0 .. l0 + nl - 1, which the caller keeps inside
+ * [nodes[0], nodes[nn-1]].  Multipoles per partial sum and bins per workgroup tile:                               */
+#define HMG_ANGCOV_CHUNK 1024
+#define HMG_ANGCOV_TILE 32
+/* hmg_angcov_weights: d_k0, d_k2, d_k4 (nl, nt), kN[l, i] = K_N(ells[l]; edges[i], edges[i+1]); d_ells (nl) positive,
+ *   d_edges (nt + 1) positive and strictly increasing, in radians.  Any output may be NULL, not all three.  J0 and J1
+ *   are evaluated once per (l, edge); a value depends on its l and its two edges alone.
+ * hmg_angcov_gaussian: d_cov (np, nt, np, nt).  h_probes (np, 3) holds (f, g, o) per probe and d_probes the same ints on
+ *   the device; with P = (a, b, mu), Q = (c, d, nu), C^^fg = C^fg + delta_fg N_f and area = 4 pi fsky,
+ *     cov[P,i,Q,j] = 1/(2 pi area) sum_{l in L} l K_mu(l; i) K_nu(l; j) [C^^ac C^^bd + C^^ad C^^bc - NN](l)
+ *                  + delta_ij delta_mu,nu (delta_ac delta_bd + delta_ad delta_bc) N_a N_b / (area pi (b_i^2 - a_i^2)),
+ *   NN = (delta_ac delta_bd + delta_ad delta_bc) N_a N_b: the noise x noise product, a delta function in theta whose l
+ *   sum does not converge, is left out of the sum and added in closed form, and dropped for mu != nu.  d_k0 / d_k2 /
+ *   d_k4 are hmg_angcov_weights' outputs on L and d_edges (an order no probe names may be NULL); d_work holds
+ *   work_words >= np (np + 1) / 2 * ceil(nl / HMG_ANGCOV_CHUNK) * nt^2 doubles.  The sum runs per pair P <= Q over
+ *   chunks of HMG_ANGCOV_CHUNK multipoles counted from l0, each in l order from 0.0, and the chunks' sums are added in
+ *   chunk order; Q < P is the transpose.  The Python layer checks values; this checks shapes, the probes' fields and
+ *   orders and the size of the work buffer.
+ * hmg_angcov_node_weights: d_r (nt, nn), or (nn, nt) if by_node, r[i, n] = scale * sum_{l in L} l K(l; i) h_n(l), h_n
+ *   the hat function of node n and d_k (nl, nt) one order's weights on L; the same chunks and order of summation.
+ * fp64, no atomics: bit-identical on repeat; an element of d_cov depends on its two probes, its two bins, the spectra
+ * and L alone - not on the other probes or bins of the call, not on the order the probes or a probe's fields are
+ * given in - and cov[P,i,Q,j] and cov[Q,j,P,i] are the same bits.                                                  */
+int hmg_angcov_weights(hmg_ctx* ctx, int nl, int nt, const double* d_ells, const double* d_edges, double* d_k0,
+                       double* d_k2, double* d_k4);
+int hmg_angcov_gaussian(hmg_ctx* ctx, int nf, int nn, const double* d_nodes, const double* d_C, const double* d_noise,
+                        int l0, int nl, int nt, const double* d_edges, int np, const int* h_probes, const int* d_probes,
+                        double area, const double* d_k0, const double* d_k2, const double* d_k4, size_t work_words,
+                        double* d_work, double* d_cov);
+int hmg_angcov_node_weights(hmg_ctx* ctx, int nn, const double* d_nodes, int l0, int nl, int nt, const double* d_k,
+                            double scale, int by_node, double* d_r);
+
 /* ---- 1-halo trispectrum of two spectra -----------------------------------------------------
  * hmg_trispectrum_1h: d_T (nz, n, n),
  *   T[z,i,j] = sum_m wm[m] nzm[z,m] s_ab[z,m,i] s_cd[z,m,j],
