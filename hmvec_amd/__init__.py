@@ -23,10 +23,11 @@ from .cov import (GaussianCov, bin_annuli, cl_cov_1halo, cl_cov_ssc, lensing_sha
                   shot_noise, sigma_b_disc)  # (covariances)
 from .bispectrum import F2, cl_bispectrum, tree_bispectrum  # noqa: F401  (bispectrum of three tracers)
 from .rsd import legendre_weights, mu_rule, virial_dispersion  # noqa: F401  (redshift-space wedges and multipoles)
+from .xipoles import get_xi_multipoles, xi_multipoles_device, xi_multipoles_from_power  # noqa: F401  (redshift-space correlation multipoles xi_0, xi_2, xi_4(s): the j_0 / j_2 / j_4 transforms of P_0, P_2, P_4, of plain arrays and of a model)
 from .onepoint import char_exponent, cumulants, lambda_grid, pdf_from_exponent, ring_rule  # noqa: F401  (one-point PDF of a sum of halo profiles)
 from .hod_ensemble import central_differences, hod_sets, stencil  # noqa: F401  (HOD parameter ensembles: P_gg, P_gm of many sets)
 from . import hod_ensemble  # noqa: F401
-from . import angcov, angular, bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils  # noqa: F401
+from . import angcov, angular, bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils, xipoles  # noqa: F401
 from .functions import __all__ as _fn_all
 
 __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "generic_profile_fft", "sigma_nfw",
@@ -38,7 +39,7 @@ __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "ge
            "cl_cov_ssc", "sigma_b_disc",
            "F2", "tree_bispectrum", "cl_bispectrum", "bispectrum",
            "projected_gnfw", "gasprofiles",
-           "virial_dispersion", "mu_rule", "legendre_weights", "rsd",
+           "virial_dispersion", "mu_rule", "legendre_weights", "rsd", "xi_multipoles_from_power", "xi_multipoles_device", "get_xi_multipoles", "xipoles",
            "char_exponent", "cumulants", "pdf_from_exponent", "lambda_grid", "ring_rule", "onepoint",
            "hod_sets", "stencil", "central_differences", "hod_ensemble",
            "fft", "tinker", "utils", "cosmology", "params"] + list(_fn_all)

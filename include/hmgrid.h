@@ -690,6 +690,22 @@ int hmg_angular_transform(hmg_ctx* ctx, int n, int nz, int nk, int nt, const dou
 int hmg_angular_zsum(hmg_ctx* ctx, int n, int nz, int nt, int nw, const double* d_zw, const double* d_w,
                      double* d_out);
 
+/* ---- redshift-space correlation multipoles of tabulated multipole spectra -------------------
+ * hmg_xi_multipoles: d_xi0, d_xi2 and d_xi4 (rows, ns), xiL[row, j] = xi_L(ss[j]) of the row of P_L,
+ *   xi_L(s) = i^L / (2 pi^2) int k f~(k) j_L(k s) dk,   L = 0, 2, 4   (i^L = +1, -1, +1),
+ * f~ the piecewise-linear interpolant of f_i = ks[i] P_L[i] on [ks[0], ks[nk-1]] and zero outside (hmg_xi_transform's),
+ * the integral exact panel by panel.  Each order reads its own rows, element i of row r at
+ * d_PL[r * row_stride + i * node_stride] (node_stride >= 1, row_stride >= (nk - 1) * node_stride + 1): contiguous rows
+ * have (nk, 1); the (2, nz, n, 3) block of hmg_rsd_multipoles is read in place with (3 n, 3) and the bases d_out,
+ * d_out + 1, d_out + 2.  An order is computed when its output pointer is non-NULL - its input pointer must then be
+ * non-NULL too - and at least one is.  d_ks (nk >= 2) positive and strictly increasing, d_ss (ns) positive, shared by
+ * all rows; the Python layer checks values, this checks shapes and strides.  xi_0 is bit for bit hmg_xi_transform of
+ * the same row at r = s.  fp64, no atomics: bit-identical on repeat, a result depends on nk, ks, its row and its s
+ * alone, not on which other outputs were asked for nor on the strides.                                             */
+int hmg_xi_multipoles(hmg_ctx* ctx, int rows, int nk, int ns, const double* d_ks, const double* d_P0,
+                      const double* d_P2, const double* d_P4, long long row_stride, long long node_stride,
+                      const double* d_ss, double* d_xi0, double* d_xi2, double* d_xi4);
+
 /* ---- covariance of angular correlation functions -------------------------------------------
  * Flat sky, section 22's J_mu convention; mu = 0, 2, 4 is named by its index o = mu / 2.  For the annulus [a, b],
  *   K_mu(l; a, b) = 2 / ((b^2 - a^2) l^2) [F_mu(l b) - F_mu(l a)],

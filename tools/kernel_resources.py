@@ -57,6 +57,13 @@ KERNELS = [   # (label, regex on the mangled name)
     ("angular_transform_kernel<256,4,false,true,true>  (W_2 and W_4; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb1ELb1EE"),
     ("angular_transform_kernel<256,4,true,true,true>  (all three orders; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb1ELb1EE"),
     ("angular_zsum_kernel  (the z sum of the angular transforms, angular.hip)", r"19angular_zsum_kernelE"),
+    ("xi_multipole_kernel<256,4,true,false,false>  (xi_0; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb0ELb0EE"),
+    ("xi_multipole_kernel<256,4,false,true,false>  (xi_2; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb0ELb1ELb0EE"),
+    ("xi_multipole_kernel<256,4,true,true,false>  (xi_0 and xi_2; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb1ELb0EE"),
+    ("xi_multipole_kernel<256,4,false,false,true>  (xi_4; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb0ELb0ELb1EE"),
+    ("xi_multipole_kernel<256,4,true,false,true>  (xi_0 and xi_4; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb0ELb1EE"),
+    ("xi_multipole_kernel<256,4,false,true,true>  (xi_2 and xi_4; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb0ELb1ELb1EE"),
+    ("xi_multipole_kernel<256,4,true,true,true>  (all three multipoles; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb1ELb1EE"),
     ("angcov_weights_kernel  (bin-averaged Bessel weights K_0, K_2, K_4; angcov.hip)", r"21angcov_weights_kernelE"),
     ("angcov_gaussian_kernel  (Gaussian covariance of angular correlation functions, 32 x 32 bins per wavefront; angcov.hip)", r"22angcov_gaussian_kernelE"),
     ("angcov_combine_kernel  (its chunks' sums in order, the transpose and the noise term; angcov.hip)", r"21angcov_combine_kernelE"),
@@ -94,7 +101,7 @@ KERNELS = [   # (label, regex on the mangled name)
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "angular", "angcov", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "sampled")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "angular", "xipoles", "angcov", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
