@@ -27,7 +27,9 @@ from .xipoles import get_xi_multipoles, xi_multipoles_device, xi_multipoles_from
 from .onepoint import char_exponent, cumulants, lambda_grid, pdf_from_exponent, ring_rule  # noqa: F401  (one-point PDF of a sum of halo profiles)
 from .hod_ensemble import central_differences, hod_sets, stencil  # noqa: F401  (HOD parameter ensembles: P_gg, P_gm of many sets)
 from . import hod_ensemble  # noqa: F401
-from . import angcov, angular, bispectrum, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils, xipoles  # noqa: F401
+from .clusters import (cluster_abundance_device, cluster_cl_cov, cluster_counts_cov, cluster_selection, get_cluster_abundance,  # noqa: F401
+                       get_cluster_counts, powerlaw_lnobs, scatter_rule, sz_lnobs)  # (cluster number counts N(z, q) and their covariance: functions of a model)
+from . import angcov, angular, bispectrum, clusters, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils, xipoles  # noqa: F401
 from .functions import __all__ as _fn_all
 
 __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "generic_profile_fft", "sigma_nfw",
@@ -42,4 +44,6 @@ __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "ge
            "virial_dispersion", "mu_rule", "legendre_weights", "rsd", "xi_multipoles_from_power", "xi_multipoles_device", "get_xi_multipoles", "xipoles",
            "char_exponent", "cumulants", "pdf_from_exponent", "lambda_grid", "ring_rule", "onepoint",
            "hod_sets", "stencil", "central_differences", "hod_ensemble",
+           "cluster_selection", "scatter_rule", "cluster_abundance_device", "get_cluster_abundance", "get_cluster_counts",
+           "cluster_counts_cov", "cluster_cl_cov", "sz_lnobs", "powerlaw_lnobs", "clusters",
            "fft", "tinker", "utils", "cosmology", "params"] + list(_fn_all)

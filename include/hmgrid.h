@@ -945,6 +945,27 @@ int hmg_hod_ensemble_power(hmg_ctx* ctx, int S, int nz, int nm, int nk, int n, c
                            const double* d_damp /*[n]*/, double* d_out /*[4][S][nz][n]*/,
                            double* d_parts /*[3][S][nz][n] or NULL*/);
 
+/* ---- cluster number counts: the survey selection in bins of significance, summed over the mass function (section 25) --
+ * A halo (z, m) has the mean log-observable mu = d_lnobs[z][m] and the log-normal scatter sg = d_sigln[z][m]; tile tau of
+ * the survey has the solid angle d_area[tau] and the noise exp(d_lnnoise[tau]); the nq bins are [d_edges[a], d_edges[a+1]).
+ * kind 0 (gaussian): with the rule (d_t, d_w) of G nodes for the unit normal,
+ *     S_a[z][m] = sum_tau sum_g (area[tau] w[g]) P_a(q),  q = exp((mu + sg t[g]) - lnnoise[tau]),
+ *     P_a(q) = 1/2 [erfc(ua) - erfc(ub)],  ua = (e_a - q) / sqrt 2,  ub = (e_a+1 - q) / sqrt 2,
+ *   formed as 1/2 [erfc(-ub) - erfc(-ua)] where (e_a - q) + (e_a+1 - q) < 0; erfc of a negative argument is 2 - erfc of its
+ *   magnitude, so every edge costs one erfc.  The edges may be -inf and +inf.
+ * kind 1 (none): S_a[z][m] = sum_tau area[tau] P_a with ua = (ln e_a - xi) / (sqrt 2 sg), xi = mu - lnnoise[tau], the
+ *   same two forms; d_t, d_w and G are not read (G >= 1), sg must be positive and the edges not negative.
+ * d_n[z][a] = sum_m d_wm[m] (d_nzm[z][m] S_a), d_bn[z][a] = sum_m (d_wm[m] (d_nzm[z][m] S_a)) d_bh[z][m] over the window
+ * m_lo <= m < m_hi (0 <= m_lo < m_hi <= nm).  d_S (nz, nm, nq), or NULL: S_a itself, zero outside the window; with NULL
+ * nothing of that size exists.  No term is skipped.  fp64 on the vector units, no atomics, the order of every sum fixed
+ * (kernels/clusters.hpp): bit-identical on repeat, and an element depends on its own (z, bin) only - not on the other bins
+ * or redshifts of the call.  Launch-only (one temporary block of 2 nz ceil(nm / 64) nq doubles from the context).        */
+int hmg_cluster_selection(hmg_ctx* ctx, int nz, int nm, int T, int G, int nq, int kind, const double* d_lnobs /*[nz][nm]*/,
+                          const double* d_sigln /*[nz][nm]*/, const double* d_lnnoise /*[T]*/, const double* d_area /*[T]*/,
+                          const double* d_t /*[G]*/, const double* d_w /*[G]*/, const double* d_edges /*[nq+1]*/, int m_lo,
+                          int m_hi, const double* d_nzm, const double* d_bh, const double* d_wm, double* d_n /*[nz][nq]*/,
+                          double* d_bn /*[nz][nq]*/, double* d_S /*[nz][nm][nq] or NULL*/);
+
 /* ---- z-slab gather over RCCL/xGMI-------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */

@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, angular.hip, angcov.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, angular.hip, angcov.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -91,6 +91,8 @@ KERNELS = [   # (label, regex on the mangled name)
     ("hodens_lmstar_kernel  (the SHMR inversion, once per (z, m), hodens.hip)", r"20hodens_lmstar_kernelE"),
     ("hodens_side_kernel  (the side data of the mass bins, hodens.hip)", r"18hodens_side_kernelE"),
     ("hodens_check_kernel  (the check of a node list, hodens.hip)", r"19hodens_check_kernelE"),
+    ("cluster_selection_kernel  (cluster counts: the selection of a 64-mass tile in up to 8 bins and its mass sum, clusters.hip)", r"24cluster_selection_kernelE"),
+    ("cluster_finish_kernel  (the tiles' sums in order, clusters.hip)", r"21cluster_finish_kernelE"),
     ("leg_prepass_kernel  (leg prepass of the bispectrum and the response: I, C, b, J, P, D, k at the samples, sampled.hip)", r"18leg_prepass_kernelE"),
     ("leg_sums_kernel  (C, C0, b of a leg, for the response and the redshift-space spectra, sampled.hip)", r"15leg_sums_kernelE"),
     ("zsum_kernel  (the z sum of the trispectrum and the bispectrum, sampled.hip)", r"11zsum_kernelE"),
@@ -101,7 +103,7 @@ KERNELS = [   # (label, regex on the mangled name)
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "angular", "xipoles", "angcov", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "sampled")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "angular", "xipoles", "angcov", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "clusters", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
