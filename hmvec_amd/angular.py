@@ -9,7 +9,7 @@ with W_n^(z)(R) = 1/(2 pi) int k P~(k, z) J_n(k R) dk the exact panel-by-panel t
 (``projected_from_power``'s P~, linear in k^2 between the grid points and zero outside the grid) and zw the z measure
 times the two windows (``Cosmology.angular_weights``).  n = 0 gives w(theta) and xi+, n = 2 gamma_t, n = 4 xi-.
 ``angular_from_power`` stands behind ``HaloModel.get_angular``, ``get_w_theta``, ``get_gamma_t``, ``get_xi_pm`` and
-``get_angular_all``.  The kernels are in hmvec_amd/csrc/kernels/angular.hpp.
+``get_angular_all``.  The kernels are in hmvec_amd/csrc/kernels/hankel.hpp.
 """
 import numpy as np
 

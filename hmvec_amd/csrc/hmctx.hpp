@@ -10,6 +10,7 @@
 #include <map>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hmgrid.h"
@@ -210,6 +211,15 @@ static inline void prefix_drop_block(hmg_ctx* c, void* p, size_t bytes) {
 int series_ensure_whole(hmg_ctx* c, const void* p);
 void series_forget(hmg_ctx* c, const void* p);
 static inline dim3 grid1d(size_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
+// Run-time flags as template arguments: with_flags(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{},
+// ...), so that a generic lambda picks the instantiation a set of nullable output pointers asks for.
+template <class F>
+static inline void with_flags(F f) { f(); }
+template <class F, class... Rest>
+static inline void with_flags(F f, bool first, Rest... rest) {
+    if (first) with_flags([&](auto... bs) { f(std::true_type{}, bs...); }, rest...);
+    else with_flags([&](auto... bs) { f(std::false_type{}, bs...); }, rest...);
+}
 // every tensor of the tracers a call reads, whole (an NFW tensor with deferred series tiles is filled first)
 static inline int tracers_ensure_whole(hmg_ctx* c, const hmg_tracer* t, int count) {      // (a contiguous array)
     for (int i = 0; i < count; ++i)

@@ -24,13 +24,7 @@
 // The first part of this file is plain C++ (the F functions given J0 and J1): tests/cpp/angcov_host.cpp builds it with a
 // host compiler.  The kernels follow under __HIPCC__.
 #pragma once
-#include <cmath>
-
-#if defined(__HIPCC__)
-#define HMG_AC_FN __host__ __device__ __forceinline__
-#else
-#define HMG_AC_FN inline
-#endif
+#include "bessel_g4.hpp"
 
 namespace hmg {
 
@@ -40,15 +34,16 @@ namespace hmg {
 // nested through k = AC_SERIES_N.  G_2's closed form subtracts x J1 from 2 (1 - J0): at x = 1 the two are 0.47 and 0.44
 // and leave 0.030 (a loss of 30), at x = 2 a loss of 6.8, at x = 3 2.52 and 1.02 leave 1.50 (2.4).  Its series at x = 3
 // (y = 2.25) has terms 2.53, 1.27, 0.27, ... against the sum 1.50 (2.7): the two sides meet at 3, and the first term
-// left out there (k = 16) is below 1e-22 of the first.  G_4 is F1 of kernels/angular.hpp, with that header's switch
-// at 5 (losses 3.4 and 6.7 on the two sides) and its 15 nested terms; the analysis is section 22's.
+// left out there (k = 16) is below 1e-22 of the first.  G_4 is bessel_g4 (bessel_g4.hpp), the function that gives W_4
+// its end terms, with its switch at 5 (losses 3.4 and 6.7 on the two sides) and its 15 nested terms; the analysis is
+// section 22's.
 constexpr double AC_SERIES_X2 = 3.0;
-constexpr double AC_SERIES_X4 = 5.0;
+constexpr double AC_SERIES_X4 = G4_SERIES_X;
 constexpr int AC_SERIES_N = 15;
 
-HMG_AC_FN double angcov_g0(double x, double j0, double j1) { return x * j1; }
+HMG_HD_FN double angcov_g0(double x, double j0, double j1) { return x * j1; }
 
-HMG_AC_FN double angcov_g2(double x, double j0, double j1) {
+HMG_HD_FN double angcov_g2(double x, double j0, double j1) {
     const double y = 0.25 * x * x;
     double s = 1.0;
 #pragma unroll
@@ -56,23 +51,13 @@ HMG_AC_FN double angcov_g2(double x, double j0, double j1) {
     return x < AC_SERIES_X2 ? y * y * 0.5 * s : std::fma(-x, j1, 2.0 * (1.0 - j0));
 }
 
-HMG_AC_FN double angcov_g4(double x, double j0, double j1) {
-    const double y = 0.25 * x * x;
-    double s = 1.0;
-#pragma unroll
-    for (int k = AC_SERIES_N; k >= 1; --k) s = std::fma(-y * ((k + 2.0) / ((k + 3.0) * k * (k + 4.0))), s, 1.0);
-    const bool series = x < AC_SERIES_X4;
-    const double d = series ? 1.0 : x;            // (the closed form is not used below the switch)
-    return series ? y * y * y * (1.0 / 36.0) * s : std::fma(x, j1, std::fma(8.0, j0, 4.0)) - 24.0 * j1 / d;
-}
-
 // G_mu by order index o = mu / 2
-HMG_AC_FN double angcov_g(int o, double x, double j0, double j1) {
-    return o == 0 ? angcov_g0(x, j0, j1) : o == 1 ? angcov_g2(x, j0, j1) : angcov_g4(x, j0, j1);
+HMG_HD_FN double angcov_g(int o, double x, double j0, double j1) {
+    return o == 0 ? angcov_g0(x, j0, j1) : o == 1 ? angcov_g2(x, j0, j1) : bessel_g4(x, j0, j1);
 }
 
 // K_mu(l; a, b) from G_mu at the two edges: pre = 2 / ((b - a)(b + a)), one division by l^2
-HMG_AC_FN double angcov_weight(double ga, double gb, double pre, double l) { return (gb - ga) * (pre / (l * l)); }
+HMG_HD_FN double angcov_weight(double ga, double gb, double pre, double l) { return (gb - ga) * (pre / (l * l)); }
 
 }  // namespace hmg
 
@@ -107,13 +92,13 @@ __global__ __launch_bounds__(256) void angcov_weights_kernel(int nl, int nt, con
     const double ell = ells[l];
     double a = edges[0], j0, j1;
     bessel_j01(ell * a, j0, j1);
-    double g0 = angcov_g0(ell * a, j0, j1), g2 = angcov_g2(ell * a, j0, j1), g4 = angcov_g4(ell * a, j0, j1);
+    double g0 = angcov_g0(ell * a, j0, j1), g2 = angcov_g2(ell * a, j0, j1), g4 = bessel_g4(ell * a, j0, j1);
     const size_t row = (size_t)l * nt;
 #pragma unroll 1
     for (int i = 0; i < nt; ++i) {
         const double b = edges[i + 1], x = ell * b;
         bessel_j01(x, j0, j1);
-        const double h0 = angcov_g0(x, j0, j1), h2 = angcov_g2(x, j0, j1), h4 = angcov_g4(x, j0, j1);
+        const double h0 = angcov_g0(x, j0, j1), h2 = angcov_g2(x, j0, j1), h4 = bessel_g4(x, j0, j1);
         const double pre = 2.0 / ((b - a) * (b + a));
         if (k0) k0[row + i] = angcov_weight(g0, h0, pre, ell);
         if (k2) k2[row + i] = angcov_weight(g2, h2, pre, ell);

@@ -1,21 +1,37 @@
-// Correlation function xi(r) of a tabulated spectrum.  Compiled in realspace.hip, a translation
-// unit of its own (kept out of the power-path units).
+// Correlation function xi(r) of a tabulated spectrum and redshift-space correlation multipoles
+// xi_0, xi_2, xi_4(s) of tabulated multipole spectra (section 24).  One kernel serves both: xi(r) is its order 0 alone.
+// Compiled in realspace.hip, the only unit that holds it.
 //
-// With f_i = k_i P_i and f~ the piecewise-linear interpolant of f on [k_0, k_{nk-1}] (zero outside),
-//   xi(r) = 1/(2 pi^2 r) int f~(k) sin(k r) dk,
-// the integral taken exactly, panel by panel.  For a panel [a, b]: h = b - a, m = (a + b)/2, f_m = (f_a + f_b)/2,
-// theta = r h / 2, and the panel integral is
+// With f_i = k_i P_l,i and f~ the piecewise-linear interpolant of f on [k_0, k_{nk-1}] (zero outside),
+//   xi_l(s) = i^l / (2 pi^2) int k f~(k) j_l(k s) dk,      l = 0, 2, 4,
+// the integral taken exactly, panel by panel.
+//
+// Order 0, k j_0(k s) = sin(k s)/s:  xi(r) = 1/(2 pi^2 r) int f~(k) sin(k r) dk.  For a panel [a, b]: h = b - a,
+// m = (a + b)/2, f_m = (f_a + f_b)/2, theta = r h / 2, and the panel integral is
 //   h f_m sin(m r) S(theta) + (f_b - f_a) h^2 r / 12 cos(m r) G(theta),
 //   S = sin(theta)/theta,  G = 3 (sin(theta) - theta cos(theta)) / theta^3      (both -> 1 as theta -> 0):
 // the two terms are the even and the odd part of f~ about the panel's midpoint, so nothing cancels inside a panel.
+//
+// Orders 2 and 4 are summed by parts (f~ is continuous, so the end terms of adjacent panels telescope), x = k s,
+// sigma_i = (f_{i+1} - f_i)/(k_{i+1} - k_i):
+//   int k f~ j_l(k s) dk = [f A_l(k s)]/s^2 - (1/s^3) sum_i sigma_i (B_l(x_{i+1}) - B_l(x_i)),
+//   A_2 = 2 + cos x - 3 sin x / x                                          = int_0^x t j_2    (-> x^4/60),
+//   B_2 = 2 x + sin x - 3 Si(x)                                            = int_0^x A_2      (-> x^5/300),
+//   A_4 = 8/3 - cos x + 10 sin x / x + 35 cos x / x^2 - 35 sin x / x^3     = int_0^x t j_4    (-> x^6/5670),
+//   B_4 = 8 x/3 - sin x - (15/2) Si(x) + (35/2) (sin x - x cos x) / x^2    = int_0^x A_4      (-> x^7/39690),
+// the antiderivatives that vanish at 0.  The 2 and 8/3 of A_l and the 2 x and 8 x/3 of B_l cancel between the end term
+// and the sum ((1/s^3) sum_i sigma_i 2 (x_{i+1} - x_i) = 2 [f]/s^2); they are left in and telescope, as the smooth
+// parts of kernels/hankel.hpp do: the series below the switch hold them implicitly, so taking them out of the closed
+// forms alone would break the telescoping at the node where the branch changes, and taking them out of both would leave
+// -2 x to swamp x^5/300.
 #pragma once
-#include "../j01.hpp"
 #include "../sici.hpp"
+#include "panels.hpp"
 
 namespace hmg {
 
 constexpr int XI_THREADS = 256;
-constexpr int XI_TILE = 4;                    // radii per workgroup
+constexpr int XI_TILE = 4;                    // separations per workgroup
 // Below this theta S and G come from their even power series.  The closed form of G subtracts two terms of size theta
 // that leave theta^3/3: it loses a factor 3/theta^2 (12 at the switch, 3.6 bits), which the gate of section 13 has room
 // for; the series truncated after theta^12 is off by less than theta^14/15! (S) and 48 theta^14/17! (G), 5e-17 and
@@ -55,171 +71,179 @@ __device__ __forceinline__ void xi_panel_factors(double th, double& S, double& G
     G = series ? pg : 3.0 * (s - d * c) / (d * d * d);
 }
 
-// out[row, j] = xi(rs[j]) of the row P[row, :] on the grid ks.  One workgroup per (row, tile of TR radii).  A thread owns
-// the panels i = tid, tid + NT, ...: it forms h, m, f_m and f_b - f_a of a panel once, adds the panel's integral for
-// every radius of the tile to its own LDS word of that radius (in panel order), and a fixed LDS tree sums the NT words
-// of each radius.  No atomics; a result depends on nk, ks, its row and its radius alone - not on the other rows or
-// radii of the launch - and is the same bits on every call.
-template <int NT, int TR>
-__global__ __launch_bounds__(NT) void xi_transform_kernel(int nk, int nr, const double* __restrict__ ks,
-                                                          const double* __restrict__ P,
-                                                          const double* __restrict__ rs, double* __restrict__ out) {
-    __shared__ double red[TR][NT];
-    const int row = blockIdx.x, j0 = blockIdx.y * TR, tid = threadIdx.x;
-    const int nt = nr - j0 < TR ? nr - j0 : TR;             // radii of this tile (>= 1 by the launch geometry)
-    const double* Pr = P + (size_t)row * nk;
-#pragma unroll
-    for (int t = 0; t < TR; ++t) red[t][tid] = 0.0;
-    for (int i = tid; i + 1 < nk; i += NT) {
-        const double a = ks[i], b = ks[i + 1];
-        const double fa = a * Pr[i], fb = b * Pr[i + 1];
-        const double h = b - a, m = 0.5 * (a + b), fm = 0.5 * (fa + fb), df = fb - fa;
-#pragma unroll 1
-        for (int t = 0; t < nt; ++t) {
-            const double r = rs[j0 + t], th = 0.5 * r * h;
-            double sm, cm, S, G;
-            xi_sincos(m * r, sm, cm);
-            xi_panel_factors(th, S, G);
-            red[t][tid] += h * (fm * sm * S + df * (th * (1.0 / 6.0)) * cm * G);      // h^2 r / 12 = h theta / 6
-        }
+// Below these x the functions of orders 2 and 4 come from their power series in y = x^2, nested,
+//   A_l = x^(l+2)/((l+2)(2l+1)!!) (1 - r_1 (1 - r_2 (1 - ...))),     r_m = y (l+2m) / ((l+2m+2) 2m (2l+2m+1))
+//   B_l = x^(l+3)/((l+2)(l+3)(2l+1)!!) (1 - r_1 (1 - ...)),          r_m = y (l+2m)(l+2m+1) / ((l+2m+2)(l+2m+3) 2m (2l+2m+1))
+// through m = XP_SERIES_N.  The closed forms add terms of size 2 x + 3 Si (B_2) and 8 x/3 + 7.5 Si + 17.5/x (B_4) that
+// leave x^5/300 and x^7/39690: B_2 loses 105 at x = 2, 21 at 3 and 7.3 at 4; B_4 loses 113 at x = 4, 30 at 5 and 11.7 at
+// 6 (A_2: 2.6 at 4; A_4: 2.9 at 6) - the 12 that section 14 accepts is reached at 4 and at 6.  A higher switch costs
+// digits inside the series: at x = 4 the series of B_2 and A_2 lose 3.0 and 4.6 (absolute term sum over the sum) and at
+// x = 5 5.5 and 11; at x = 6 those of B_4 and A_4 lose 6.7 and 11.8 and at x = 7 13 and 30.  At the switch the first
+// omitted term (m = 15 and m = 17) is below 1e-17 of the sum.  x = 4 is also where sici_fast changes from the
+// rational in x^2 to the auxiliary functions.  Both branches are evaluated and selected.
+constexpr double XP_SERIES_X2 = 4.0;
+constexpr double XP_SERIES_X4 = 6.0;
+constexpr int XP_SERIES_N2 = 14;
+constexpr int XP_SERIES_N4 = 16;
+
+// sin x, cos x, 1/x and Si(x) at a node, shared by both orders; below the order-2 switch, where no closed form is read,
+// the reciprocal is that of 1 (no 0/0 at x = 0)
+struct XpTrig { double s, c, r, si; };
+__device__ __forceinline__ XpTrig xp_trig(const SiciTable* __restrict__ T, double x, bool want_si) {
+    XpTrig t;
+    xi_sincos(x, t.s, t.c);
+    t.r = rcp_fast(x < XP_SERIES_X2 ? 1.0 : x);
+    t.si = 0.0;
+    if (want_si) {
+        double ci;
+        bool small;
+        sici_fast(T, x, t.s, t.c, t.r * t.r, t.si, ci, small);
     }
-    __syncthreads();
+    return t;
+}
+
+// B_2(x) and B_4(x): the node functions of the sums
+template <bool X2, bool X4>
+__device__ __forceinline__ void xp_node(const SiciTable* __restrict__ T, double x, double& b2, double& b4) {
+    const XpTrig t = xp_trig(T, x, true);
+    const double y = x * x;
+    if (X2) {
+        double s = 1.0;
 #pragma unroll
-    for (int s = NT / 2; s >= 1; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int t = 0; t < TR; ++t) red[t][tid] += red[t][tid + s];
-        }
-        __syncthreads();
+        for (int m = XP_SERIES_N2; m >= 1; --m)
+            s = fma(-y * ((2.0 + 2 * m) * (3.0 + 2 * m) / ((4.0 + 2 * m) * (5.0 + 2 * m) * (2.0 * m) * (5.0 + 2 * m))), s, 1.0);
+        b2 = x < XP_SERIES_X2 ? x * y * y * (1.0 / 300.0) * s : fma(2.0, x, fma(-3.0, t.si, t.s));
     }
-    if (tid < nt) out[(size_t)row * nr + j0 + tid] = red[tid][0] * (0.5 / (M_PI * M_PI)) / rs[j0 + tid];
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Hankel transforms of orders 0 and 2 of a tabulated spectrum: w_p, Sigma and Delta Sigma.
-//
-// With P~ the interpolant of P that is linear in k^2 on each panel of [k_0, k_{nk-1}] (zero outside),
-// P~ = P_a + B (k^2 - a^2), B = (P_b - P_a) / ((b - a)(b + a)) on [a, b],
-//   W_0(R) = 1/(2 pi) int k P~ J0(k R) dk,   W_2(R) = 1/(2 pi) int k P~ J2(k R) dk,
-// the integrals exact.  Summed by parts (P~ is continuous, so the end terms of the panels telescope), x = k R:
-//   2 pi W_0 = [P k J1(x)]/R   - (2/R^4) sum_i B_i (g(x_{i+1}) - g(x_i)),    g  = x^2 J2                 = int_0^x t^2 J1
-//   2 pi W_2 = [P H1(x)]/R^2   - (2/R^4) sum_i B_i (H2(x_{i+1}) - H2(x_i)),  H1 = 2 (1 - J0) - x J1      = int_0^x t J2
-//                                                                            H2 = x^2 - 2 x J1 - x^2 J2  = int_0^x t H1
-// H1 and H2 are the antiderivatives that vanish at 0: no constant is left to cancel against the sum at small k R.
-constexpr int HK_THREADS = 256;
-constexpr int HK_TILE = 4;                    // radii per workgroup
-// Below this x the node functions come from their power series in y = x^2/4,
-//   g  = 2 y^2 (1 - y/(1*3) (1 - y/(2*4) (1 - ...))),                    ratio of terms j-1 -> j:  y / (j (j+2))
-//   H1 = y^2/2 (1 - 2y/(1*9) (1 - 3y/(2*16) (1 - ...))),                                       y (j+1) / (j (j+2)^2)
-//   H2 = y^3/3 (1 - 2y/(1*3*4) (1 - 3y/(2*4*5) (1 - ...))),                                    y (j+1) / (j (j+2) (j+3))
-// nested through j = HK_SERIES_N.  The closed forms subtract terms of size x^2 that leave x^4/8 (g), x^4/32 (H1) and
-// x^6/192 (H2): they lose 8/x^2, 16/x^2 and 192/x^4 - 2, 4 and 12 at the switch, what section 13 accepts for G.  A lower
-// switch would cost digits as x^-2 and x^-4.  A higher one would cost them inside the series: up to y = 1 its terms fall
-// from the first (the second is at most 1/3 of it), so nothing cancels; beyond, they grow before they fall.  At the
-// switch the first omitted terms are 8.0e-18 (g), 1.2e-18 (H1) and 2.7e-19 (H2) of the leading one.  Both branches are
-// evaluated and selected.
-constexpr double HK_SERIES_X = 2.0;
-constexpr int HK_SERIES_N = 10;
-
-// g(x) = x^2 J2(x) and H2(x) given J0(x) and J1(x); the closed forms without a division: x^2 J2 = x (2 J1 - x J0)
-template <bool W0, bool W2>
-__device__ __forceinline__ void hankel_node_j(double x, double j0, double j1, double& g, double& h2) {
-    const double y = 0.25 * x * x;
-    const bool series = x < HK_SERIES_X;
-    const double gc = x * fma(-x, j0, 2.0 * j1);
-    double sg = 1.0, sh = 1.0;
+    if (X4) {
+        double s = 1.0;
 #pragma unroll
-    for (int j = HK_SERIES_N; j >= 1; --j) {
-        if (W0) sg = fma(-y * (1.0 / (j * (j + 2.0))), sg, 1.0);
-        if (W2) sh = fma(-y * ((j + 1.0) / (j * (j + 2.0) * (j + 3.0))), sh, 1.0);
+        for (int m = XP_SERIES_N4; m >= 1; --m)
+            s = fma(-y * ((4.0 + 2 * m) * (5.0 + 2 * m) / ((6.0 + 2 * m) * (7.0 + 2 * m) * (2.0 * m) * (9.0 + 2 * m))), s, 1.0);
+        const double osc = fma(17.5 * (t.r * t.r), fma(-x, t.c, t.s), fma(-7.5, t.si, -t.s));
+        b4 = x < XP_SERIES_X4 ? x * y * y * y * (1.0 / 39690.0) * s : fma(8.0 / 3.0, x, osc);
     }
-    g = series ? 2.0 * y * y * sg : gc;
-    h2 = series ? y * y * y * (1.0 / 3.0) * sh : fma(x, fma(-2.0, j1, x), -gc);
 }
 
-// the same at a node whose J0 and J1 the caller does not need (the angular kernel of kernels/angular.hpp does)
-template <bool W0, bool W2>
-__device__ __forceinline__ void hankel_node(double x, double& g, double& h2) {
-    double j0, j1;
-    bessel_j01(x, j0, j1);
-    hankel_node_j<W0, W2>(x, j0, j1, g, h2);
-}
-
-// H1(x) given J0(x) and J1(x): the end terms of W_2
-__device__ __forceinline__ double hankel_h1(double x, double j0, double j1) {
-    const double y = 0.25 * x * x;
-    double s = 1.0;
+// A_2(x) and A_4(x): the end terms
+template <bool X2, bool X4>
+__device__ __forceinline__ void xp_ends(double x, double& a2, double& a4) {
+    const XpTrig t = xp_trig(nullptr, x, false);
+    const double y = x * x, sr = t.s * t.r;
+    if (X2) {
+        double s = 1.0;
 #pragma unroll
-    for (int j = HK_SERIES_N; j >= 1; --j) s = fma(-y * ((j + 1.0) / (j * (j + 2.0) * (j + 2.0))), s, 1.0);
-    return x < HK_SERIES_X ? 0.5 * y * y * s : fma(-x, j1, 2.0 * (1.0 - j0));
+        for (int m = XP_SERIES_N2; m >= 1; --m)
+            s = fma(-y * ((2.0 + 2 * m) / ((4.0 + 2 * m) * (2.0 * m) * (5.0 + 2 * m))), s, 1.0);
+        a2 = x < XP_SERIES_X2 ? y * y * (1.0 / 60.0) * s : fma(-3.0, sr, 2.0 + t.c);
+    }
+    if (X4) {
+        double s = 1.0;
+#pragma unroll
+        for (int m = XP_SERIES_N4; m >= 1; --m)
+            s = fma(-y * ((4.0 + 2 * m) / ((6.0 + 2 * m) * (2.0 * m) * (9.0 + 2 * m))), s, 1.0);
+        a4 = x < XP_SERIES_X4 ? y * y * y * (1.0 / 5670.0) * s
+                              : fma(35.0 * (t.r * t.r), t.c - sr, fma(10.0, sr, 8.0 / 3.0 - t.c));
+    }
 }
 
-// out0[row, j] = W_0(rs[j]) and out2[row, j] = W_2(rs[j]) of the row P[row, :] on the grid ks (W0 / W2: which of the two
-// this instantiation writes).  One workgroup per (row, tile of TR radii).  A thread owns a contiguous run of
-// c = ceil((nk-1)/NT) panels, i = tid c ... min((tid+1) c, nk-1) - 1 (the last owners' runs are short or empty): it
-// evaluates the node functions once at the left end of its run and then once per panel, at the panel's right node, which
-// it carries to the next panel as the left one - (nk-1) + (owners) evaluations per radius instead of 2 (nk-1).  The price
-// is in the loads: a thread reads c + 1 consecutive ks and P values, so the 64 lanes of a load are c words apart
-// (uncoalesced: 64 cache lines per wavefront load, re-used over the c steps of the run from L1); a row is at most 32 KB
-// and comes from L2 once per tile.  The radii of a tile are taken one after the other (the run is re-read from L1), each
-// partial sum goes to the thread's LDS word of that radius and output, and a fixed LDS tree sums the NT words.  The two
-// end terms are formed by the thread that writes the result.  No atomics; a result depends on nk, ks, its row and its
-// radius alone and is the same bits on every call, alone or in a batch, with or without the other output.
-template <int NT, int TR, bool W0, bool W2>
-__global__ __launch_bounds__(NT) void hankel_transform_kernel(int nk, int nr, const double* __restrict__ ks,
-                                                              const double* __restrict__ P,
-                                                              const double* __restrict__ rs, double* __restrict__ out0,
-                                                              double* __restrict__ out2) {
-    constexpr int NO = (W0 ? 1 : 0) + (W2 ? 1 : 0);
+// outL[row, j] = xi_L(ss[j]) of the row PL[row row_stride + i node_stride], i < nk, on the grid ks, L = 0, 2, 4 (X0 / X2 /
+// X4: which of them this instantiation writes; each order reads its own rows).  One workgroup per (row, tile of TR
+// separations).  Order 0: a thread owns the panels tid, tid + NT, ...: it forms h, m, f_m and f_b - f_a of a panel once
+// and adds the panel's closed-form integral for every separation of the tile to its LDS word of that separation, in
+// panel order; hmg_xi_transform is this order alone on contiguous rows.  Orders 2 and 4: contiguous-run ownership
+// (panels.hpp) - c = ceil((nk-1)/NT) panels per thread, the node functions once at the left end of the run and once per
+// panel at the right node, carried; one sincos and one Si per node serve both orders.  One LDS word per (thread, output,
+// separation), the fixed tree, explicit fma; the writing thread forms the end terms.  No atomics; a result depends on
+// nk, ks, its row and its separation alone and is the same bits on every call, alone or in a batch, with or without the
+// other outputs, from strided or contiguous rows.  UNIT: the launch promises node_stride == 1 (hmg_xi_transform), so
+// that the two nodes of a panel come from one 16-byte load and no index is multiplied; the arithmetic is the same.
+template <int NT, int TR, bool X0, bool X2, bool X4, bool UNIT = false>
+__global__ __launch_bounds__(NT) void xi_multipole_kernel(int nk, int ns, const double* __restrict__ ks,
+                                                          const double* __restrict__ P0, const double* __restrict__ P2,
+                                                          const double* __restrict__ P4, long long row_stride,
+                                                          long long node_stride_arg, const double* __restrict__ ss,
+                                                          const SiciTable* __restrict__ T, double* __restrict__ out0,
+                                                          double* __restrict__ out2, double* __restrict__ out4) {
+    constexpr int S2 = X0 ? 1 : 0, S4 = S2 + (X2 ? 1 : 0), NO = S4 + (X4 ? 1 : 0);
     __shared__ double red[NO * TR][NT];
     const int row = blockIdx.x, j0 = blockIdx.y * TR, tid = threadIdx.x;
-    const int nt = nr - j0 < TR ? nr - j0 : TR;             // radii of this tile (>= 1 by the launch geometry)
-    const double* Pr = P + (size_t)row * nk;
-    const int np = nk - 1, c = (np - 1) / NT + 1;
-    const int lo = tid * c < np ? tid * c : np, hi = lo + c < np ? lo + c : np;
+    const int nt = tile_count<TR>(ns, j0);
+    const int np = nk - 1;
+    const long long node_stride = UNIT ? 1 : node_stride_arg;
+    if (X0) {
+        const double* Pr = P0 + (size_t)row * row_stride;
+#pragma unroll
+        for (int t = 0; t < TR; ++t) red[t][tid] = 0.0;
+        for (int i = tid; i + 1 < nk; i += NT) {
+            const double a = ks[i], b = ks[i + 1];
+            const size_t o = (size_t)i * node_stride;       // (one 64-bit product per panel, not one per node)
+            const double fa = a * Pr[o], fb = b * Pr[o + node_stride];
+            const double h = b - a, m = 0.5 * (a + b), fm = 0.5 * (fa + fb), df = fb - fa;
 #pragma unroll 1
-    for (int t = 0; t < TR; ++t) {
-        double s0 = 0.0, s2 = 0.0;
-        if (t < nt && lo < hi) {
-            const double R = rs[j0 + t];
-            double a = ks[lo], Pa = Pr[lo], gl, hl;
-            hankel_node<W0, W2>(a * R, gl, hl);
-#pragma unroll 1
-            for (int i = lo; i < hi; ++i) {
-                const double b = ks[i + 1], Pb = Pr[i + 1];
-                double gr, hr;
-                hankel_node<W0, W2>(b * R, gr, hr);
-                const double B = (Pb - Pa) / ((b - a) * (b + a));
-                if (W0) s0 = fma(B, gr - gl, s0);
-                if (W2) s2 = fma(B, hr - hl, s2);
-                a = b, Pa = Pb, gl = gr, hl = hr;
+            for (int t = 0; t < nt; ++t) {
+                const double r = ss[j0 + t], th = 0.5 * r * h;
+                double sm, cm, S, G;
+                xi_sincos(m * r, sm, cm);
+                xi_panel_factors(th, S, G);
+                red[t][tid] += h * (fm * sm * S + df * (th * (1.0 / 6.0)) * cm * G);      // h^2 r / 12 = h theta / 6
             }
         }
-        if (W0) red[t][tid] = s0;
-        if (W2) red[(NO - 1) * TR + t][tid] = s2;
     }
-    __syncthreads();
-#pragma unroll
-    for (int s = NT / 2; s >= 1; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int t = 0; t < NO * TR; ++t) red[t][tid] += red[t][tid + s];
+    if (X2 || X4) {
+        const double* Pr2 = X2 ? P2 + (size_t)row * row_stride : nullptr;
+        const double* Pr4 = X4 ? P4 + (size_t)row * row_stride : nullptr;
+        const PanelRun run = panel_run<NT>(tid, np);
+#pragma unroll 1
+        for (int t = 0; t < TR; ++t) {
+            double s2 = 0.0, s4 = 0.0;
+            if (t < nt && run.lo < run.hi) {
+                const double s = ss[j0 + t];
+                double a = ks[run.lo], fa2 = 0.0, fa4 = 0.0, bl2 = 0.0, bl4 = 0.0;
+                if (X2) fa2 = a * Pr2[(size_t)run.lo * node_stride];
+                if (X4) fa4 = a * Pr4[(size_t)run.lo * node_stride];
+                xp_node<X2, X4>(T, a * s, bl2, bl4);
+#pragma unroll 1
+                for (int i = run.lo; i < run.hi; ++i) {
+                    const double b = ks[i + 1], ih = 1.0 / (b - a);
+                    double br2 = 0.0, br4 = 0.0;
+                    xp_node<X2, X4>(T, b * s, br2, br4);
+                    if (X2) {
+                        const double fb = b * Pr2[(size_t)(i + 1) * node_stride];
+                        s2 = fma((fb - fa2) * ih, br2 - bl2, s2);
+                        fa2 = fb;
+                    }
+                    if (X4) {
+                        const double fb = b * Pr4[(size_t)(i + 1) * node_stride];
+                        s4 = fma((fb - fa4) * ih, br4 - bl4, s4);
+                        fa4 = fb;
+                    }
+                    a = b, bl2 = br2, bl4 = br4;
+                }
+            }
+            if (X2) red[S2 * TR + t][tid] = s2;
+            if (X4) red[S4 * TR + t][tid] = s4;
         }
-        __syncthreads();
     }
+    panel_tree_sum(red, tid);
     if (tid < nt) {
-        const double R = rs[j0 + tid], iR = 1.0 / R, iR2 = iR * iR, iR4 = iR2 * iR2;
-        const double ka = ks[0], kb = ks[np], Pa = Pr[0], Pb = Pr[np];
-        double a0, a1, b0, b1;
-        bessel_j01(ka * R, a0, a1);
-        bessel_j01(kb * R, b0, b1);
-        if (W0) {
-            const double ends = fma(Pb * kb, b1, -(Pa * ka * a1));
-            out0[(size_t)row * nr + j0 + tid] = fma(-2.0 * iR4, red[tid][0], ends * iR) * (0.5 / M_PI);
-        }
-        if (W2) {
-            const double ends = fma(Pb, hankel_h1(kb * R, b0, b1), -(Pa * hankel_h1(ka * R, a0, a1)));
-            out2[(size_t)row * nr + j0 + tid] = fma(-2.0 * iR4, red[(NO - 1) * TR + tid][0], ends * iR2) * (0.5 / M_PI);
+        const size_t o = (size_t)row * ns + j0 + tid;
+        if (X0) out0[o] = red[tid][0] * (0.5 / (M_PI * M_PI)) / ss[j0 + tid];
+        if (X2 || X4) {
+            const double s = ss[j0 + tid], is = 1.0 / s, is2 = is * is, is3 = is2 * is;
+            const double ka = ks[0], kb = ks[np];
+            double aa2 = 0.0, aa4 = 0.0, ab2 = 0.0, ab4 = 0.0;
+            xp_ends<X2, X4>(ka * s, aa2, aa4);
+            xp_ends<X2, X4>(kb * s, ab2, ab4);
+            if (X2) {
+                const double* Pr = P2 + (size_t)row * row_stride;
+                const double ends = fma(kb * Pr[(size_t)np * node_stride], ab2, -(ka * Pr[0] * aa2));
+                out2[o] = fma(-is3, red[S2 * TR + tid][0], ends * is2) * (-0.5 / (M_PI * M_PI));
+            }
+            if (X4) {
+                const double* Pr = P4 + (size_t)row * row_stride;
+                const double ends = fma(kb * Pr[(size_t)np * node_stride], ab4, -(ka * Pr[0] * aa4));
+                out4[o] = fma(-is3, red[S4 * TR + tid][0], ends * is2) * (0.5 / (M_PI * M_PI));
+            }
         }
     }
 }

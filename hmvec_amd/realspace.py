@@ -14,7 +14,8 @@ with P~ the interpolant of P that is linear in k^2 on each panel of [ks[0], ks[-
 
 again exact panel by panel.  W_0 of P_gg is w_p(r_p) with pi_max -> infinity; rho_m0 W_0 and rho_m0 W_2 of P_gm are
 Sigma(R) and Delta Sigma(R).  It stands behind ``HaloModel.get_wp``, ``get_surface_density``,
-``get_excess_surface_density`` and their ``_all`` forms.  The kernels are in hmvec_amd/csrc/kernels/realspace.hpp.
+``get_excess_surface_density`` and their ``_all`` forms.  The kernels are in hmvec_amd/csrc/kernels/realspace.hpp
+(xi) and hmvec_amd/csrc/kernels/hankel.hpp (the projected statistics).
 """
 import numpy as np
 

@@ -11,7 +11,7 @@ row, bit for bit.  ``xi_multipoles_from_power`` transforms tabulated rows; ``xi_
 ``get_xi_multipoles(model, ...)`` transform a HaloModel's own multipoles where ``multipoles_device`` left them.  They
 are functions of the model, as section 23's ``angular_cov(model, ...)`` is, not methods: the attribute surface of the
 class is a recorded fixture (tests/golden/facade_surface.json) that this section leaves as it is.  The kernel is in
-hmvec_amd/csrc/kernels/xipoles.hpp.
+hmvec_amd/csrc/kernels/realspace.hpp.
 """
 import numpy as np
 

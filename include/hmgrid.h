@@ -680,8 +680,9 @@ int hmg_hankel_transform(hmg_ctx* ctx, int rows, int nk, int nr, const double* d
  * P~ as for hmg_hankel_transform, the integrals exact panel by panel.  d_P (n * nz, nk): n blocks of nz rows, row z of
  * every block at the distance d_chis[z] (nz, positive); d_thetas (nt) positive, in radians.  Any output pointer may be
  * NULL (that order is not computed), not all three.  W_0 and W_2 are bit for bit what hmg_hankel_transform gives at
- * the radius R.  fp64, no atomics: bit-identical on repeat, a result depends on nk, ks, its row and its R alone, and
- * an output does not depend on which others were asked for.
+ * the radius R: both entry points launch one kernel, with the rule for R as a template argument.  fp64, no atomics:
+ * bit-identical on repeat, a result depends on nk, ks, its row and its R alone, and an output does not depend on which
+ * others were asked for.
  * hmg_angular_zsum: d_out (n, nw, nt), out[i, w, j] = sum_z zw[w, z] W[i * nz + z, j], d_zw (nw, nz), d_w (n * nz, nt):
  * one fused multiply-add chain over z in index order from 0.0 per output (a single z of weight 1.0 returns W's bits);
  * no atomics, no dependence on the launch shape.  d_out must not overlap d_w.                                       */
@@ -700,8 +701,9 @@ int hmg_angular_zsum(hmg_ctx* ctx, int n, int nz, int nt, int nw, const double* 
  * d_out + 1, d_out + 2.  An order is computed when its output pointer is non-NULL - its input pointer must then be
  * non-NULL too - and at least one is.  d_ks (nk >= 2) positive and strictly increasing, d_ss (ns) positive, shared by
  * all rows; the Python layer checks values, this checks shapes and strides.  xi_0 is bit for bit hmg_xi_transform of
- * the same row at r = s.  fp64, no atomics: bit-identical on repeat, a result depends on nk, ks, its row and its s
- * alone, not on which other outputs were asked for nor on the strides.                                             */
+ * the same row at r = s: that entry point launches this kernel with order 0 alone and the strides (nk, 1).  fp64, no
+ * atomics: bit-identical on repeat, a result depends on nk, ks, its row and its s alone, not on which other outputs
+ * were asked for nor on the strides.                                                                               */
 int hmg_xi_multipoles(hmg_ctx* ctx, int rows, int nk, int ns, const double* d_ks, const double* d_P0,
                       const double* d_P2, const double* d_P4, long long row_stride, long long node_stride,
                       const double* d_ss, double* d_xi0, double* d_xi2, double* d_xi4);

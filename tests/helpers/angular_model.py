@@ -3,7 +3,7 @@ tests/test_gpu_angular.py share.  With P~ and W_0, W_2 of projected_model.py (se
 W_4(R) = 1/(2 pi) int k P~ J4(k R) dk:
 
 * ``f1_fn``, ``f2_fn``: F1 = int_0^x t J4 dt and F2 = int_0^x t F1 dt as the kernel forms them, series below the switch;
-* ``w4_numpy``: a numpy restatement of the by-parts sum the kernel evaluates (hmvec_amd/csrc/kernels/angular.hpp);
+* ``w4_numpy``: a numpy restatement of the by-parts sum the kernel evaluates (hmvec_amd/csrc/kernels/hankel.hpp);
 * ``w4_mpmath``: a 40-digit evaluation of the per-panel antiderivatives A Phi1/R^2 + B Phi3/R^4 with
   Phi1 = int_0^x t J4 = x^6/2304 1F2(3; 4, 5; -x^2/4) and Phi3 = int_0^x t^3 J4 = x^8/3072 1F2(4; 5, 5; -x^2/4) - an
   independent form (no summation by parts, no F2, no closed form in J0 and J1);

@@ -2,7 +2,7 @@
 tests/test_gpu_projected.py share.  With P~ linear in k^2 on each panel [a, b] of the grid and zero outside,
 P~ = P_a + B (k^2 - a^2), B = (P_b - P_a)/((b - a)(b + a)), and W_n(R) = 1/(2 pi) int k P~ J_n(k R) dk:
 
-* ``hankel_numpy``: a numpy restatement of the by-parts sum the kernel evaluates (hmvec_amd/csrc/kernels/realspace.hpp)
+* ``hankel_numpy``: a numpy restatement of the by-parts sum the kernel evaluates (hmvec_amd/csrc/kernels/hankel.hpp)
   with scipy's j0, j1 and jv(2, .), for sizes where mpmath is slow;
 * ``hankel_mpmath``: a 40-digit evaluation of the per-panel antiderivatives - an independent algebraic form (A and B of
   each panel against x J1, J0, x^3 J1 - 2 x^2 J2 and x^3 J3; no summation by parts, no H1 or H2);

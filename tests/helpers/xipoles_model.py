@@ -3,7 +3,7 @@ tests/test_gpu_xipoles.py share.  With f_i = k_i P_l,i, f~ section 13's interpol
 the grid) and xi_l(s) = i^l/(2 pi^2) int k f~(k) j_l(k s) dk:
 
 * ``a_fn``, ``b_fn``: A_l = int_0^x t j_l dt and B_l = int_0^x A_l dt, l = 2, 4, as the kernel forms them
-  (hmvec_amd/csrc/kernels/xipoles.hpp): power series below the switch, closed forms with Si above;
+  (hmvec_amd/csrc/kernels/realspace.hpp): power series below the switch, closed forms with Si above;
 * ``xil_numpy``: a numpy restatement of the by-parts sum the kernel evaluates (order 0: realspace_model.xi_numpy);
 * ``xil_mpmath``: a 40-digit evaluation of the per-panel antiderivatives alpha Phi1/s^2 + sigma Phi2/s^3 with
   Phi1 = int_0^x t j_l and Phi2 = int_0^x t^2 j_l from their 1F2 forms - no summation by parts, no B_l, no Si;

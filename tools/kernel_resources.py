@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, angular.hip, angcov.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, hankel.hip, angcov.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -45,25 +45,25 @@ KERNELS = [   # (label, regex on the mangled name)
     ("ksz_nvv_shared_kernel  (N_vv, one k_S integral per z, ksz.hip)", r"21ksz_nvv_shared_kernelE"),
     ("ksz_nvv_rows_kernel  (N_vv, photo-z / per-row, ksz.hip)", r"19ksz_nvv_rows_kernelE"),
     ("ksz_limber_cl_kernel  (kSZ C_ell, ksz.hip)", r"20ksz_limber_cl_kernelE"),
-    ("xi_transform_kernel<256,4>  (correlation function, realspace.hip)", r"19xi_transform_kernelILi256ELi4EE"),
-    ("hankel_transform_kernel<256,4,true,false>  (W_0: w_p, Sigma; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb1ELb0EE"),
-    ("hankel_transform_kernel<256,4,false,true>  (W_2: Delta Sigma; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb0ELb1EE"),
-    ("hankel_transform_kernel<256,4,true,true>  (W_0 and W_2 from one pass; realspace.hip)", r"23hankel_transform_kernelILi256ELi4ELb1ELb1EE"),
-    ("angular_transform_kernel<256,4,true,false,false>  (W_0: w(theta), xi+; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb0ELb0EE"),
-    ("angular_transform_kernel<256,4,false,true,false>  (W_2: gamma_t; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb1ELb0EE"),
-    ("angular_transform_kernel<256,4,true,true,false>  (W_0 and W_2; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb1ELb0EE"),
-    ("angular_transform_kernel<256,4,false,false,true>  (W_4: xi-; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb0ELb1EE"),
-    ("angular_transform_kernel<256,4,true,false,true>  (W_0 and W_4: xi+ and xi-; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb0ELb1EE"),
-    ("angular_transform_kernel<256,4,false,true,true>  (W_2 and W_4; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb1ELb1EE"),
-    ("angular_transform_kernel<256,4,true,true,true>  (all three orders; angular.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb1ELb1EE"),
-    ("angular_zsum_kernel  (the z sum of the angular transforms, angular.hip)", r"19angular_zsum_kernelE"),
-    ("xi_multipole_kernel<256,4,true,false,false>  (xi_0; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb0ELb0EE"),
-    ("xi_multipole_kernel<256,4,false,true,false>  (xi_2; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb0ELb1ELb0EE"),
-    ("xi_multipole_kernel<256,4,true,true,false>  (xi_0 and xi_2; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb1ELb0EE"),
-    ("xi_multipole_kernel<256,4,false,false,true>  (xi_4; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb0ELb0ELb1EE"),
-    ("xi_multipole_kernel<256,4,true,false,true>  (xi_0 and xi_4; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb0ELb1EE"),
-    ("xi_multipole_kernel<256,4,false,true,true>  (xi_2 and xi_4; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb0ELb1ELb1EE"),
-    ("xi_multipole_kernel<256,4,true,true,true>  (all three multipoles; xipoles.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb1ELb1EE"),
+    ("xi_multipole_kernel<256,4,true,false,false,true>  (xi(r): hmg_xi_transform, order 0 with node_stride 1 at compile time; realspace.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb0ELb0ELb1EE"),
+    ("xi_multipole_kernel<256,4,true,false,false,false>  (xi_0; realspace.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb0ELb0ELb0EE"),
+    ("xi_multipole_kernel<256,4,false,true,false,false>  (xi_2; realspace.hip)", r"19xi_multipole_kernelILi256ELi4ELb0ELb1ELb0ELb0EE"),
+    ("xi_multipole_kernel<256,4,true,true,false,false>  (xi_0 and xi_2; realspace.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb1ELb0ELb0EE"),
+    ("xi_multipole_kernel<256,4,false,false,true,false>  (xi_4; realspace.hip)", r"19xi_multipole_kernelILi256ELi4ELb0ELb0ELb1ELb0EE"),
+    ("xi_multipole_kernel<256,4,true,false,true,false>  (xi_0 and xi_4; realspace.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb0ELb1ELb0EE"),
+    ("xi_multipole_kernel<256,4,false,true,true,false>  (xi_2 and xi_4; realspace.hip)", r"19xi_multipole_kernelILi256ELi4ELb0ELb1ELb1ELb0EE"),
+    ("xi_multipole_kernel<256,4,true,true,true,false>  (all three multipoles; realspace.hip)", r"19xi_multipole_kernelILi256ELi4ELb1ELb1ELb1ELb0EE"),
+    ("angular_transform_kernel<256,4,true,false,false,PlainRadius>  (W_0: w_p, Sigma at given radii, hmg_hankel_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb0ELb0ENS_11PlainRadiusEE"),
+    ("angular_transform_kernel<256,4,false,true,false,PlainRadius>  (W_2: Delta Sigma at given radii, hmg_hankel_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb1ELb0ENS_11PlainRadiusEE"),
+    ("angular_transform_kernel<256,4,true,true,false,PlainRadius>  (W_0 and W_2 from one pass at given radii, hmg_hankel_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb1ELb0ENS_11PlainRadiusEE"),
+    ("angular_transform_kernel<256,4,true,false,false,ChiThetaRadius>  (W_0: w(theta), xi+, hmg_angular_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb0ELb0ENS_14ChiThetaRadiusEE"),
+    ("angular_transform_kernel<256,4,false,true,false,ChiThetaRadius>  (W_2: gamma_t, hmg_angular_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb1ELb0ENS_14ChiThetaRadiusEE"),
+    ("angular_transform_kernel<256,4,true,true,false,ChiThetaRadius>  (W_0 and W_2, hmg_angular_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb1ELb0ENS_14ChiThetaRadiusEE"),
+    ("angular_transform_kernel<256,4,false,false,true,ChiThetaRadius>  (W_4: xi-, hmg_angular_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb0ELb1ENS_14ChiThetaRadiusEE"),
+    ("angular_transform_kernel<256,4,true,false,true,ChiThetaRadius>  (W_0 and W_4: xi+ and xi-, hmg_angular_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb0ELb1ENS_14ChiThetaRadiusEE"),
+    ("angular_transform_kernel<256,4,false,true,true,ChiThetaRadius>  (W_2 and W_4, hmg_angular_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb0ELb1ELb1ENS_14ChiThetaRadiusEE"),
+    ("angular_transform_kernel<256,4,true,true,true,ChiThetaRadius>  (all three orders, hmg_angular_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb1ELb1ENS_14ChiThetaRadiusEE"),
+    ("angular_zsum_kernel  (the z sum of the angular transforms, hankel.hip)", r"19angular_zsum_kernelE"),
     ("angcov_weights_kernel  (bin-averaged Bessel weights K_0, K_2, K_4; angcov.hip)", r"21angcov_weights_kernelE"),
     ("angcov_gaussian_kernel  (Gaussian covariance of angular correlation functions, 32 x 32 bins per wavefront; angcov.hip)", r"22angcov_gaussian_kernelE"),
     ("angcov_combine_kernel  (its chunks' sums in order, the transpose and the noise term; angcov.hip)", r"21angcov_combine_kernelE"),
@@ -103,7 +103,7 @@ KERNELS = [   # (label, regex on the mangled name)
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "angular", "xipoles", "angcov", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "clusters", "sampled")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "hankel", "angcov", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "clusters", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
