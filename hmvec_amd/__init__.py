@@ -29,7 +29,9 @@ from .hod_ensemble import central_differences, hod_sets, stencil  # noqa: F401  
 from . import hod_ensemble  # noqa: F401
 from .clusters import (cluster_abundance_device, cluster_cl_cov, cluster_counts_cov, cluster_selection, get_cluster_abundance,  # noqa: F401
                        get_cluster_counts, powerlaw_lnobs, scatter_rule, sz_lnobs)  # (cluster number counts N(z, q) and their covariance: functions of a model)
-from . import angcov, angular, bispectrum, clusters, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils, xipoles  # noqa: F401
+from .cib import (cib_defaults, cib_luminosities, cib_sed, cl_cib, emission_power_device, emission_tables, get_power_cib,  # noqa: F401
+                  register_emission, sed_break, sub_rule)  # (the CIB halo model: multi-frequency spectra, crosses and C_ell: functions of a model)
+from . import angcov, angular, bispectrum, cib, clusters, cosmology, cov, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils, xipoles  # noqa: F401
 from .functions import __all__ as _fn_all
 
 __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "generic_profile_fft", "sigma_nfw",
@@ -46,4 +48,6 @@ __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "ge
            "hod_sets", "stencil", "central_differences", "hod_ensemble",
            "cluster_selection", "scatter_rule", "cluster_abundance_device", "get_cluster_abundance", "get_cluster_counts",
            "cluster_counts_cov", "cluster_cl_cov", "sz_lnobs", "powerlaw_lnobs", "clusters",
+           "cib_defaults", "sed_break", "cib_sed", "sub_rule", "cib_luminosities", "emission_tables", "emission_power_device",
+           "get_power_cib", "cl_cib", "register_emission", "cib",
            "fft", "tinker", "utils", "cosmology", "params"] + list(_fn_all)

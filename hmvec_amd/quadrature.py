@@ -60,6 +60,14 @@ def gauss_legendre_unit(n):
     return 0.5 * (x + 1.0), 0.5 * w
 
 
+def sub_rule(nsub):
+    """(t, w): the nsub-node Gauss-Legendre rule on [0, 1] for the subhalo integral of the CIB model (hmvec_amd.cib), nodes
+    ascending; a row maps it to its own interval ln M_min .. ln M.  nsub must be an integer >= 2."""
+    if isinstance(nsub, bool) or not isinstance(nsub, (int, np.integer)) or nsub < 2:
+        raise ValueError(f"nsub must be an integer >= 2, got {nsub!r}")
+    return gauss_legendre_unit(nsub)
+
+
 def gradient_is_uniform(x):
     """np.gradient switches to its uniform-spacing stencil when every diff is bit-equal."""
     d = np.diff(np.asarray(x, dtype=np.float64))

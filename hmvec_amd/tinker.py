@@ -52,7 +52,11 @@ def simple_f_nu(nu, delta=200.0):
 
 
 def NlnMsub(Msubs, Mhosts):
-    raise NotImplementedError("NlnMsub (hmvec/tinker.py:81-) is not on the accelerated path")
+    """dN / dln M_sub of Tinker & Wetzel 2010, eq. 12 of the published version (hmvec/tinker.py:81-90): 1-D Msubs and
+    Mhosts, a 2-D array (Msubs, Mhosts).  The host formula; the CIB model integrates the same function on the device
+    (hmvec_amd.cib, csrc/kernels/cib.hpp)."""
+    r = np.divide.outer(np.asarray(Msubs, dtype=np.float64), np.asarray(Mhosts, dtype=np.float64))
+    return 0.3 * r ** -0.7 * np.exp(-9.9 * r ** 2.5)
 
 
 __all__ = ["bias", "f_nu", "simple_f_nu", "NlnMsub", "constants", "default_params"]

@@ -968,6 +968,43 @@ int hmg_cluster_selection(hmg_ctx* ctx, int nz, int nm, int T, int G, int nq, in
                           int m_hi, const double* d_nzm, const double* d_bh, const double* d_wm, double* d_n /*[nz][nq]*/,
                           double* d_bn /*[nz][nq]*/, double* d_S /*[nz][nm][nq] or NULL*/);
 
+/* ---- the CIB halo model: luminosities and the spectra of every pair of frequencies -------------
+ * hmg_cib_luminosity: d_Lc, d_Ls (F, nz, nm), the emissivity weights of the centrals and the satellites of a Shang et al.
+ *   (2012) model at the observed frequencies d_nus [GHz], F <= HMG_CIB_FMAX.  h_par = (alpha, T0 [K], beta, gamma, delta,
+ *   z_p, log10 M_eff, sigma2, M_min, L0, x0); x0 is the root of x / (1 - exp(-x)) = 3 + beta + gamma.  With
+ *     L(M, z; nu) = L0 Phi(z) Sigma(M) Theta((1+z) nu, T0 (1+z)^alpha),   Phi = min(1+z, 1+z_p)^delta,
+ *     Sigma(M) = M (2 pi sigma2)^-1/2 exp(-(log10 M - log10 M_eff)^2 / (2 sigma2)),   nu0 = x0 k T / h,
+ *     Theta = (nu/nu0)^(3+beta) expm1(x0) / expm1(h nu / k T) below nu0, (nu/nu0)^-gamma from nu0 on,
+ *   L_c = L(ms[m]) / 4 pi where ms[m] >= M_min, else 0;  L_s = sum_g (w[g] hw) N(q_g) L(m_g) / 4 pi, g ascending, over
+ *   the rule (d_t, d_w) of nsub nodes on [0, 1] mapped to ln m in [ln M_min, ln ms[m]]: hw = ln(ms[m] / M_min),
+ *   m_g = M_min exp(hw t[g]), q = m_g / ms[m], N = 0.3 q^-0.7 exp(-9.9 q^2.5); 0 where ms[m] <= M_min.  d_scut (F), or
+ *   NULL: a source - a central, or a subhalo node - with L / (4 pi (1+z) chi^2) > d_scut[f] is masked (its L is 0);
+ *   d_chis (nz) [Mpc].  The order of every operation is written down in kernels/cib.hpp.  Launch-only, no temporaries.
+ * hmg_emission_power: the mass integrals of the emissivity tracers a_f = L_c[f] + L_s[f] u_s at n columns, the nodes
+ *   d_kindex (n) of the k grid or, with d_kindex NULL, the whole grid (n = nk), as hmg_hod_ensemble_power takes them.
+ *   With w = wm nzm, t_f = L_s[f] u_s:
+ *     d_P1h[pair][z][col] = damp sum_m w (L_c[f] t_g + L_c[g] t_f + t_f t_g),  pair = f F - f (f - 1) / 2 + (g - f), f <= g;
+ *     d_I[f][z][col]      = sum_m (w bh) a_f        (the 2-halo leg: P2h_fg = Pzk I_f I_g, no consistency term);
+ *     d_X1h[p][f][z][col] = damp sum_m w a_f c_p prof_p   for the NP <= 2 partners h_partners[p]: matter (c = m / rho_m0)
+ *       or pressure (c = 1) tracers; any other kind is refused.  A partner's hints are not read: a tensor with a pending
+ *       left fill is filled by the caller first (hmg_prefix_fill).  NP = 0: h_partners and d_X1h may be NULL.
+ *   The pair term is never formed as a_f a_g - L_c[f] L_c[g].  fp64 on the vector units, no atomics, one FMA chain over
+ *   m per element: bit-identical on repeat, and an element does not depend on which other frequencies, pairs, partners,
+ *   nodes or redshifts the call holds (in a pair, f is the frequency that comes first).  d_us and a partner tensor equal
+ *   to it are loaded once.  A given d_kindex is checked on the device first and the host waits for that answer (not in a
+ *   captured step).  Temporaries: one block of 8 nz nm (2 Fpad + 4) + 64 bytes from the context, Fpad = F rounded up to 4. */
+#define HMG_CIB_FMAX 16
+#define HMG_CIB_NPAR 11
+int hmg_cib_luminosity(hmg_ctx* ctx, int F, int nz, int nm, int nsub, const double* d_nus /*[F]*/, const double* d_zs,
+                       const double* d_ms, const double* d_chis /*[nz]*/, const double* d_scut /*[F] or NULL*/,
+                       const double* d_t /*[nsub]*/, const double* d_w /*[nsub]*/, const double h_par[HMG_CIB_NPAR],
+                       double* d_Lc /*[F][nz][nm]*/, double* d_Ls /*[F][nz][nm]*/);
+int hmg_emission_power(hmg_ctx* ctx, int F, int nz, int nm, int nk, int n, const double* d_us, const double* d_Lc,
+                       const double* d_Ls, int NP, const hmg_tracer* h_partners /*[NP] or NULL*/, const double* d_nzm,
+                       const double* d_bh, const double* d_ms, const double* d_wm, double rho_m0,
+                       const int* d_kindex /*[n] or NULL*/, const double* d_damp /*[n]*/, double* d_P1h /*[npair][nz][n]*/,
+                       double* d_I /*[F][nz][n]*/, double* d_X1h /*[NP][F][nz][n] or NULL*/);
+
 /* ---- z-slab gather over RCCL/xGMI-------------------------------------------------
  * One communicator per context.  The 128-byte id comes from hmg_comm_unique_id on rank 0
  * and is distributed by the caller (file, socket, MPI, ...).                                     */

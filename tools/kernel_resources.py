@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, hankel.hip, angcov.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, hankel.hip, angcov.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip, cib.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -93,6 +93,12 @@ KERNELS = [   # (label, regex on the mangled name)
     ("hodens_check_kernel  (the check of a node list, hodens.hip)", r"19hodens_check_kernelE"),
     ("cluster_selection_kernel  (cluster counts: the selection of a 64-mass tile in up to 8 bins and its mass sum, clusters.hip)", r"24cluster_selection_kernelE"),
     ("cluster_finish_kernel  (the tiles' sums in order, clusters.hip)", r"21cluster_finish_kernelE"),
+    ("cib_luminosity_kernel  (CIB: L_c and L_s of a halo at every frequency, one wavefront per (z, m), cib.hip)", r"21cib_luminosity_kernelE"),
+    ("emission_power_kernel<0>  (CIB contraction, a 4 x 4 tile of frequency pairs per thread, no partner, cib.hip)", r"21emission_power_kernelILi0EE"),
+    ("emission_power_kernel<1>  (the same with one partner, cib.hip)", r"21emission_power_kernelILi1EE"),
+    ("emission_power_kernel<2>  (the same with two partners, cib.hip)", r"21emission_power_kernelILi2EE"),
+    ("emission_prep_kernel  (the frequency-padded coefficients and the side data of the mass bins, cib.hip)", r"20emission_prep_kernelE"),
+    ("emission_check_kernel  (the check of a node list, cib.hip)", r"21emission_check_kernelE"),
     ("leg_prepass_kernel  (leg prepass of the bispectrum and the response: I, C, b, J, P, D, k at the samples, sampled.hip)", r"18leg_prepass_kernelE"),
     ("leg_sums_kernel  (C, C0, b of a leg, for the response and the redshift-space spectra, sampled.hip)", r"15leg_sums_kernelE"),
     ("zsum_kernel  (the z sum of the trispectrum and the bispectrum, sampled.hip)", r"11zsum_kernelE"),
@@ -103,19 +109,19 @@ KERNELS = [   # (label, regex on the mangled name)
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "hankel", "angcov", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "clusters", "sampled")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "hankel", "angcov", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "clusters", "cib", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
     print(f"# kernel sources {kernel_source_sha16()}  (hipcc -O3 --offload-arch=gfx950 -mllvm -disable-machine-licm; make asm)")
-    print("# columns: SGPRs VGPRs | reserved scratch B/lane | occupancy waves/SIMD | SGPR spills, VGPR spills (compiler summary) |")
+    print("# columns: SGPRs VGPRs | LDS B/workgroup | reserved scratch B/lane | occupancy waves/SIMD | SGPR spills, VGPR spills (compiler summary) |")
     print("#          scratch_* instructions in the ISA | v_writelane/v_readlane (SGPR spills live in VGPR lanes, not in memory)")
     for label, pat in KERNELS:
-        m = re.search(r"Function Name: (_ZN3hmg\d*" + pat + r"\S*)(.*?)LDS Size", res, re.S)
+        m = re.search(r"Function Name: (_ZN3hmg\d*" + pat + r"\S*)(.*?)LDS Size \[bytes/block\]: (\d+)", res, re.S)
         if not m:
             print(f"{label}: not found")
             continue
-        name, block = m.group(1), m.group(2)
+        name, block, lds = m.group(1), m.group(2), m.group(3)
         g = lambda key: re.search(key + r": (\d+)", block).group(1)      # noqa: E731
         body = asm[asm.index("\n" + name + ":"):]
         body = body[:body.index(".Lfunc_end")]
@@ -125,7 +131,7 @@ def main():
         rl = sum(1 for l in lines if re.match(r"\s*v_readlane", l))
         scratch, occ = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]")
         where = (", at lines " + ",".join(map(str, scr))) if scr else ""
-        print(f"{label}\n    SGPRs {g('TotalSGPRs')}  VGPRs {g('VGPRs')} | scratch {scratch} B | occupancy {occ} | spills: SGPR "
+        print(f"{label}\n    SGPRs {g('TotalSGPRs')}  VGPRs {g('VGPRs')} | LDS {lds} B | scratch {scratch} B | occupancy {occ} | spills: SGPR "
               f"{g('SGPRs Spill')}, VGPR {g('VGPRs Spill')} | scratch instructions {len(scr)} (of {len(lines)} lines{where}) | "
               f"lane moves {wl}/{rl}")
 
