@@ -166,10 +166,13 @@ __device__ __forceinline__ int angcov_compare(const int* __restrict__ probes, in
 // staged (the first already times l G) and every thread adds the stage to its 4 x 4 accumulators with one fma per
 // element and multipole.  Multipoles past the chunk's end and bins past nt are staged as 0: fma(0, 0, s) = s.
 // An accumulator sees its own two probes, its two bins and the chunk's multipoles in order, nothing else.
+// CURVED: the measure is l + 1/2 instead of l, a probe's third entry names one of the four
+// curved-sky kinds and k6 holds the fourth kind's weights (kernels/curvedsky.hpp); the flat form never reads k6.
+template <bool CURVED>
 __global__ __launch_bounds__(AC_THREADS) void angcov_gaussian_kernel(
     int nf, int nn, const double* __restrict__ nodes, const double* __restrict__ C, const double* __restrict__ N, int l0,
     int nl, int nt, int np, const int* __restrict__ probes, const double* __restrict__ k0, const double* __restrict__ k2,
-    const double* __restrict__ k4, double* __restrict__ partial) {
+    const double* __restrict__ k4, const double* __restrict__ k6, double* __restrict__ partial) {
     __shared__ double sw[AC_STAGE];
     __shared__ __attribute__((aligned(16))) double sa[AC_STAGE][AC_TILE];
     __shared__ __attribute__((aligned(16))) double sb[AC_STAGE][AC_TILE];
@@ -183,8 +186,8 @@ __global__ __launch_bounds__(AC_THREADS) void angcov_gaussian_kernel(
     }
     const int a = probes[3 * P], b = probes[3 * P + 1], c = probes[3 * Q], d = probes[3 * Q + 1];
     const int oa = probes[3 * P + 2], ob = probes[3 * Q + 2];
-    const double* ka = oa == 0 ? k0 : oa == 1 ? k2 : k4;
-    const double* kb = ob == 0 ? k0 : ob == 1 ? k2 : k4;
+    const double* ka = oa == 0 ? k0 : oa == 1 ? k2 : !CURVED || oa == 2 ? k4 : k6;
+    const double* kb = ob == 0 ? k0 : ob == 1 ? k2 : !CURVED || ob == 2 ? k4 : k6;
     const int la = chunk * AC_CHUNK, lb = nl - la < AC_CHUNK ? nl : la + AC_CHUNK;
     const int ti = 4 * (tid / 8), tj = 4 * (tid % 8);
     double acc[4][4] = {};
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(AC_THREADS) void angcov_gaussian_kernel(
                 int n;
                 double t;
                 angcov_panel(nodes, nn, l, n, t);
-                w = l * angcov_gpq(C, N, nf, nn, a, b, c, d, n, t);
+                w = (CURVED ? l + 0.5 : l) * angcov_gpq(C, N, nf, nn, a, b, c, d, n, t);
             }
             sw[tid] = w;
         }
@@ -235,6 +238,9 @@ __global__ __launch_bounds__(AC_THREADS) void angcov_gaussian_kernel(
 // cov[P, i, Q, j] = pref * (the chunks' partial sums added in chunk order from 0.0) + the closed-form noise term.
 // One thread per element: it finds where its value lies in partial - the pair's block, oriented by angcov_compare, and
 // for two probes of one key the (smaller bin, larger bin) entry - so cov[P,i,Q,j] and cov[Q,j,P,i] read the same words.
+// CURVED: `edges` holds cos a_i - cos b_i per bin instead of the edges, and the noise term's denominator is
+// area 2 pi (cos a_i - cos b_i).
+template <bool CURVED>
 __global__ __launch_bounds__(256) void angcov_combine_kernel(int nchunks, int nt, int np, size_t total,
                                                              const int* __restrict__ probes,
                                                              const double* __restrict__ N,
@@ -259,8 +265,12 @@ __global__ __launch_bounds__(256) void angcov_combine_kernel(int nchunks, int nt
     const int* q = probes + 3 * Q;
     if (i == j && p[2] == q[2]) {
         const double cnt = (p[0] == q[0] && p[1] == q[1] ? 1.0 : 0.0) + (p[0] == q[1] && p[1] == q[0] ? 1.0 : 0.0);
-        const double ea = edges[i], eb = edges[i + 1];
-        noise = (cnt * (N[p[0]] * N[p[1]])) / (area_pi * ((eb - ea) * (eb + ea)));
+        if (CURVED) {
+            noise = (cnt * (N[p[0]] * N[p[1]])) / (area_pi * (2.0 * edges[i]));
+        } else {
+            const double ea = edges[i], eb = edges[i + 1];
+            noise = (cnt * (N[p[0]] * N[p[1]])) / (area_pi * ((eb - ea) * (eb + ea)));
+        }
     }
     cov[e] = fma(s, pref, noise);
 }
@@ -269,6 +279,8 @@ __global__ __launch_bounds__(256) void angcov_combine_kernel(int nchunks, int nt
 // and 1 - t on the panel above, t and the panel as angcov_panel gives them.  One thread per (n, i) walks the node's own
 // support in l order; the partial sum of every AC_CHUNK-aligned chunk of L starts at 0.0 and the chunks' sums are added
 // in chunk order, the order of summation of the Gaussian contraction.  by_node: R is written (nn, nt), else (nt, nn).
+// CURVED: the measure is l + 1/2.
+template <bool CURVED>
 __global__ __launch_bounds__(256) void angcov_node_weights_kernel(int nn, const double* __restrict__ nodes, int l0, int nl,
                                                                   int nt, const double* __restrict__ K, double scale,
                                                                   int by_node, double* __restrict__ R) {
@@ -290,7 +302,7 @@ __global__ __launch_bounds__(256) void angcov_node_weights_kernel(int nn, const 
             const bool rising = l < en || n == nn - 1;
             const double e0 = rising ? nodes[n - (n > 0)] : en, e1 = rising ? en : nodes[n + 1];
             const double t = (l - e0) / (e1 - e0), h = rising ? t : 1.0 - t;
-            p = fma(l * h, K[(size_t)(li - l0) * nt + i], p);
+            p = fma((CURVED ? l + 0.5 : l) * h, K[(size_t)(li - l0) * nt + i], p);
         }
         s = s + p;
     }

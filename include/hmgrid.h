@@ -746,6 +746,42 @@ int hmg_angcov_gaussian(hmg_ctx* ctx, int nf, int nn, const double* d_nodes, con
 int hmg_angcov_node_weights(hmg_ctx* ctx, int nn, const double* d_nodes, int l0, int nl, int nt, const double* d_k,
                             double scale, int by_node, double* d_r);
 
+/* ---- curved-sky angular correlation functions and their covariance -----------------------
+ * The four kinds 0 .. 3 = w, gammat, xip, xim are the Wigner functions d^l = P_l, d^l_{0,2}, d^l_{2,2}, d^l_{2,-2} of
+ * theta; xi_kind^{ab}(theta) = sum_l (2l + 1)/(4 pi) C_l^{ab} d_kind^l(theta).  For the annulus [a, b], 0 < a < b <= pi,
+ *   K_kind(l; a, b) = [G_kind(l; b) - G_kind(l; a)] / (cos a - cos b),   G_kind(l; theta) = int_0^theta sin d_kind^l,
+ * and a spin-2 kind (gammat, xip, xim) is exactly 0 below l = 2.  Spectra, nodes, noise levels and L = l0 .. l0 + nl - 1
+ * are hmg_angcov_gaussian's.  d_cosdiff (nt) holds cos a_i - cos b_i of the bins, formed as 2 sin((a+b)/2) sin((b-a)/2)
+ * by the caller: the weights and the noise term divide by the same numbers.
+ * hmg_curvedsky_weights: d_kw, d_kg, d_kp, d_km (nl, nt), k[l - l0, i] = K_kind(l; edges[i], edges[i+1]); d_edges
+ *   (nt + 1) in (0, pi], strictly increasing.  Any output may be NULL, not all four.  One thread per edge walks the
+ *   three-term recurrences from l = 0; a value depends on its l and its two edges alone.
+ * hmg_curvedsky_gaussian: d_cov (np, nt, np, nt); h_probes / d_probes (np, 3) hold (f, g, kind).  With area = 4 pi fsky,
+ *     cov[P,i,Q,j] = 1/(4 pi area) sum_{l in L} (2l + 1) K_kind(l; i) K_kind'(l; j) [C^^ac C^^bd + C^^ad C^^bc - NN](l)
+ *                  + delta_ij delta_kind,kind' (delta_ac delta_bd + delta_ad delta_bc) N_a N_b / (area 2 pi cosdiff[i]):
+ *   hmg_angcov_gaussian's sum with the measure l + 1/2, the same kernels, chunks, order of summation, work buffer
+ *   (work_words >= np (np + 1) / 2 * ceil(nl / HMG_ANGCOV_CHUNK) * nt^2) and bit-identities.  A kind no probe names may
+ *   have a NULL weight pointer.
+ * hmg_curvedsky_node_weights: hmg_angcov_node_weights with the measure l + 1/2,
+ *   r[i, n] = scale * sum_{l in L} (l + 1/2) K(l; i) h_n(l).
+ * hmg_curvedsky_scale_spectra: d_C (nf, nf, nn) in place, C[f, g, n] *= f(nodes[n])^(number of spin-2 fields among f
+ *   and g), f(l) = sqrt((l + 2)(l - 1) / (l (l + 1))) (f^2 is formed as the ratio, without the root): convergence
+ *   spectra to E-mode spectra.  h_spins / d_spins (nf) hold 0 or 2 per field, on the host and on the device.
+ * This checks shapes, kinds, spins, l0 >= 1 and the size of the work buffer; the Python layer checks values.  fp64, no
+ * atomics, bit-identical on repeat.  The largest multipole hmg_curvedsky_weights walks to (every workgroup steps its
+ * recurrence from l = 0: 2^24 steps are a few tenths of a second):                                                  */
+#define HMG_CURVEDSKY_LMAX 16777216
+int hmg_curvedsky_weights(hmg_ctx* ctx, int l0, int nl, int nt, const double* d_edges, const double* d_cosdiff,
+                          double* d_kw, double* d_kg, double* d_kp, double* d_km);
+int hmg_curvedsky_gaussian(hmg_ctx* ctx, int nf, int nn, const double* d_nodes, const double* d_C, const double* d_noise,
+                           int l0, int nl, int nt, const double* d_cosdiff, int np, const int* h_probes,
+                           const int* d_probes, double area, const double* d_kw, const double* d_kg, const double* d_kp,
+                           const double* d_km, size_t work_words, double* d_work, double* d_cov);
+int hmg_curvedsky_node_weights(hmg_ctx* ctx, int nn, const double* d_nodes, int l0, int nl, int nt, const double* d_k,
+                               double scale, int by_node, double* d_r);
+int hmg_curvedsky_scale_spectra(hmg_ctx* ctx, int nf, int nn, const double* d_nodes, const int* h_spins,
+                                const int* d_spins, double* d_C);
+
 /* ---- 1-halo trispectrum of two spectra -----------------------------------------------------
  * hmg_trispectrum_1h: d_T (nz, n, n),
  *   T[z,i,j] = sum_m wm[m] nzm[z,m] s_ab[z,m,i] s_cd[z,m,j],

@@ -1,0 +1,405 @@
+"""Host models of the curved-sky angular correlation functions and their covariance that
+tests/test_curvedsky_cpu.py and tests/test_gpu_curvedsky.py share.
+
+Kinds "w", "gammat", "xip", "xim": d_kind^l(theta) = P_l, d^l_{0,2}, d^l_{2,2}, d^l_{2,-2}; with x = cos theta,
+s = sin^2(theta/2), t = 2 s, G_kind(l; theta) = int_0^theta sin d_kind^l and K = [G(b) - G(a)] / (cos a - cos b).
+
+* ``g_numpy`` / ``weights_numpy``: the numpy restatement of the scheme of hmvec_amd/csrc/kernels/curvedsky.hpp - the
+  difference recurrence in t (E_l = (l+1)(P_{l+1} - P_l)), P' by its own recurrence, the closed forms in Q_l = int_x^1 P_l
+  above the switches in M s (M = l (l+1)) and the integrated terminating series in s below them;
+* ``g_mpmath`` / ``weights_mpmath``: the same integrals from the closed forms TAKEN LITERALLY (the textbook
+  antiderivatives, nothing rewritten) on 90-digit recurrences, rounded to 40 digits' worth and then to float64;
+  ``g_quad`` is the quadrature of the definition (Jacobi polynomials) that checks them;
+* ``cov_numpy`` / ``cov_mpmath``, ``node_weights_numpy``, ``binned_mpmath``: section 23's with l -> l + 1/2 and
+  pi (b^2 - a^2) -> 2 pi (cos a - cos b);
+* the gates.  u = 2^-53.  dG = C2 u |G| + (the closed form's coefficients) x (the bounds of what the recurrences carry),
+      dP_l  = CR u (l + 1) eP,                 eP  = min(1, sqrt(2 / (pi (l + 1/2) sin theta)))      (Bernstein)
+      dD_l  = CR u (l + 1) min((l + 1) t, 2 sin(theta/2) eP),        D_l = P_{l+1} - P_l
+      dP'_l = CR u (l + 1) min(M / 2, (l + 1) eP / max(sin theta, 1/(l + 1))):
+  a rounding count (CR per step) times u times the envelope of the carried quantity, growing linearly in l, never a floor;
+  a series reads nothing of the recurrences and its bound is C2 u |G| alone.  A weight's bound is
+  [dG(l; b) + dG(l; a)] / (cos a - cos b); the covariance's is section 23's per-term bound with l -> l + 1/2.
+"""
+import functools
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import angcov_model as acm  # noqa: E402
+
+U = 2.0 ** -53
+C1, C2, CR = 16.0, 16.0, 1.0
+KINDS = ("w", "gammat", "xip", "xim")
+SPIN2 = {"w": (0, 0), "gammat": (0, 2), "xip": (2, 2), "xim": (2, 2)}       # the spins of a kind's two fields
+SWITCH = {"w": 0.0, "gammat": 2.25, "xip": 2.25, "xim": 6.25}               # series below M s < SWITCH (CS_SWITCH_*)
+SERIES_N = 15
+ARCMIN = np.pi / 10800.0
+
+
+def half_angle(theta):
+    """(s, t, x) = (sin^2(theta/2), 2 s, 1 - t) as the header forms them."""
+    sh = np.sin(0.5 * np.asarray(theta, dtype=np.float64))
+    s = sh * sh
+    t = 2.0 * s
+    return s, t, 1.0 - t
+
+
+def cosdiff(a, b):
+    """cos a - cos b = 2 sin((a + b)/2) sin((b - a)/2)."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return 2.0 * (np.sin(0.5 * (a + b)) * np.sin(0.5 * (b - a)))
+
+
+# ---------------------------------------------------------------- the numpy restatement of the header
+def tables(lmax, theta):
+    """P_l, D_l, P'_l for l = 0 .. lmax at the angles theta: three (lmax + 1, n) arrays."""
+    _, t, _ = half_angle(theta)
+    n = t.size
+    P, D, dP = np.empty((lmax + 1, n)), np.empty((lmax + 1, n)), np.empty((lmax + 1, n))
+    p, e, dp, dpm = np.ones(n), -t, np.zeros(n), np.zeros(n)
+    for l in range(lmax + 1):
+        r = 1.0 / (l + 1.0)
+        P[l], D[l], dP[l] = p, e * r, dp
+        pn = e * r + p                                  # (an fma on the device: one rounding less, inside the gate)
+        e = e - ((2.0 * l + 3.0) * t) * pn
+        dp, dpm = (2.0 * l + 1.0) * p + dpm, dp
+        p = pn
+    return P, D, dP
+
+
+def _nested(first, s, ratio, weight):
+    h = weight(SERIES_N) * np.ones_like(s)
+    for k in range(SERIES_N, 0, -1):
+        h = (ratio(k) * s) * h + weight(k - 1)
+    return first * h
+
+
+def g_numpy(ells, theta, kind):
+    """G_kind[l, e] at the integer multipoles ells (>= 1) and the angles theta, as the header forms it."""
+    ells = np.asarray(ells, dtype=np.float64)
+    theta = np.atleast_1d(np.asarray(theta, dtype=np.float64))
+    li = ells.astype(int)
+    P, D, dP = tables(int(li.max()), theta)
+    s, t, x = half_angle(theta)
+    l = ells[:, None]
+    M = l * (l + 1.0)
+    p, pm, d, dm, dp, dpm = P[li], P[li - 1], D[li], D[li - 1], dP[li], dP[li - 1]
+    Q = -(d + dm) * (1.0 / (2.0 * l + 1.0))
+    if kind == "w":
+        return Q
+    S = s[None, :] * np.ones_like(M)
+    N4 = M - 2.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if kind == "gammat":
+            root = np.sqrt(M * N4)
+            closed = (2.0 * (1.0 - x * p) - (M + 2.0) * Q) * (1.0 / root)
+            ser = _nested(root * S * S, S, lambda k: -(N4 - k * (k + 3.0)) * (1.0 / (k * (k + 2.0))),
+                          lambda k: 1.0 / (k + 2.0) - S * (1.0 / (k + 3.0)))
+        else:
+            inv_n = 2.0 / (M * N4)
+            a = 0.5 * l * (l - 1.0)
+            A = -(a * (M + 2.0)) * Q - (2.0 * a) * (x * p) - (M + 2.0) * pm + 4.0 * dp + 2.0 * (x * dpm)
+            B = 2.0 * (l * l - l + 1.0) * p - 2.0 * (x * dp) - 4.0 * dpm
+            if kind == "xip":
+                closed = (-A - B) * inv_n
+                ser = _nested(2.0 * S, S, lambda k: -(N4 - k * (k + 3.0)) * (1.0 / (k * k)),
+                              lambda k: 1.0 / (k + 1.0) - S * (2.0 / (k + 2.0) - S * (1.0 / (k + 3.0))))
+            else:
+                closed = (2.0 * N4 - A + B) * inv_n
+                ser = _nested((M * N4) * (1.0 / 12.0) * (S * S * S), S,
+                              lambda k: -(N4 - k * (k + 3.0)) * (1.0 / (k * (k + 4.0))), lambda k: 1.0 / (k + 3.0))
+    out = np.where(M * S < SWITCH[kind], ser, closed)
+    return np.where(l < 2.0, 0.0, out)
+
+
+def weights_numpy(ells, edges, kind):
+    """K_kind[l, i] of the bins edges[i : i + 2] at the integer multipoles ells: (nl, nt)."""
+    edges = np.asarray(edges, dtype=np.float64)
+    G = g_numpy(ells, edges, kind)
+    return (G[:, 1:] - G[:, :-1]) * (1.0 / cosdiff(edges[:-1], edges[1:]))[None, :]
+
+
+# ---------------------------------------------------------------- 40-digit references
+def _mp_tables(lmax, theta, mp):
+    """[(P, P', x)] per angle, P and P' lists over l = 0 .. lmax + 1 in the working precision (the t recurrence)."""
+    out = []
+    for th in theta:
+        th = mp.mpf(float(th))
+        t = 2 * mp.sin(th / 2) ** 2
+        P, D, dP = [mp.mpf(1)], -t, [mp.mpf(0), mp.mpf(1)]
+        for l in range(lmax + 1):
+            P.append(P[l] + D)
+            D = ((l + 1) * D - (2 * l + 3) * t * P[l + 1]) / (l + 2)
+            if l >= 1:
+                dP.append(dP[l - 1] + (2 * l + 1) * P[l])
+        out.append((P, dP, 1 - t))
+    return out
+
+
+def _g_literal(l, P, dP, x, kind, mp):
+    """int_x^1 d_kind^l from the textbook antiderivatives, nothing rewritten."""
+    Q = (P[l - 1] - P[l + 1]) / (2 * l + 1)
+    if kind == "w":
+        return Q
+    if l < 2:
+        return mp.mpf(0)
+    if kind == "gammat":
+        return (2 * (1 - x * P[l]) - (l * (l + 1) + 2) * Q) / mp.sqrt(mp.mpf((l - 1) * l * (l + 1) * (l + 2)))
+    sign = 1 if kind == "xip" else -1
+
+    def F(Pm, P0, Pp, d0, dm, xx):
+        return (-(mp.mpf(l * (l - 1)) / 2) * (l + mp.mpf(2) / (2 * l + 1)) * Pm - (mp.mpf(l * (l - 1) * (2 - l)) / 2) * xx * P0
+                + (mp.mpf(l * (l - 1)) / (2 * l + 1)) * Pp + (4 - l) * d0 + (l + 2) * (xx * dm - Pm)
+                + sign * (2 * (l - 1) * (xx * d0 - P0) - 2 * (l + 2) * dm))
+    one = mp.mpf(1)
+    at1 = F(one, one, one, mp.mpf(l * (l + 1)) / 2, mp.mpf(l * (l - 1)) / 2, one)
+    return (at1 - F(P[l - 1], P[l], P[l + 1], dP[l], dP[l - 1], x)) * 2 / ((l - 1) * l * (l + 1) * (l + 2))
+
+
+def g_mpmath(ells, theta, kind, as_float=True, dps=90):
+    """G_kind[l, e] in dps digits (the literal closed forms lose up to (l theta)^-6 to cancellation: 90 digits leave
+    more than 40 at l theta = 1e-4) on the exact float64 angles."""
+    import mpmath as mp
+    li = [int(v) for v in np.asarray(ells)]
+    with mp.workdps(dps):
+        tabs = _mp_tables(max(li), np.atleast_1d(theta), mp)
+        out = [[_g_literal(l, P, dP, x, kind, mp) for (P, dP, x) in tabs] for l in li]
+        return np.array([[float(v) for v in row] for row in out]) if as_float else out
+
+
+def weights_mpmath(ells, edges, kind, as_float=True, dps=90):
+    import mpmath as mp
+    with mp.workdps(dps):
+        G = g_mpmath(ells, edges, kind, as_float=False, dps=dps)
+        e = [mp.mpf(float(v)) for v in edges]
+        den = [mp.cos(e[i]) - mp.cos(e[i + 1]) for i in range(len(e) - 1)]
+        out = [[(row[i + 1] - row[i]) / den[i] for i in range(len(den))] for row in G]
+        return np.array([[float(v) for v in row] for row in out]) if as_float else out
+
+
+def d_mpmath(l, theta, kind, mp):
+    """d_kind^l(theta) of the definition, in Jacobi form."""
+    x, s = mp.cos(theta), mp.sin(theta / 2) ** 2
+    if kind == "w":
+        return mp.legendre(l, x)
+    if l < 2:
+        return mp.mpf(0)
+    if kind == "gammat":
+        return mp.sqrt(mp.mpf((l + 1) * (l + 2)) / (l * (l - 1))) * s * (1 - s) * mp.jacobi(l - 2, 2, 2, x)
+    return (1 - s) ** 2 * mp.jacobi(l - 2, 0, 4, x) if kind == "xip" else s ** 2 * mp.jacobi(l - 2, 4, 0, x)
+
+
+def g_quad(l, theta, kind, dps=40):
+    """int_0^theta sin d_kind^l by mpmath quadrature."""
+    import mpmath as mp
+    with mp.workdps(dps):
+        th = mp.mpf(float(theta))
+        pieces = max(2, int(l * th / 3) + 2)
+        return mp.quad(lambda v: mp.sin(v) * d_mpmath(l, v, kind, mp), mp.linspace(0, th, pieces))
+
+
+# ---------------------------------------------------------------- the gates
+def carried_bounds(l, theta):
+    """(dP, dD, dP') of the docstring at multipoles l (nl, 1) and angles theta (n,)."""
+    sn, sh = np.abs(np.sin(theta))[None, :], np.abs(np.sin(0.5 * theta))[None, :]
+    with np.errstate(divide="ignore"):
+        eP = np.minimum(1.0, np.sqrt(2.0 / (np.pi * (l + 0.5) * sn)))
+    step = CR * U * (l + 1.0)
+    M = l * (l + 1.0)
+    return (step * eP, step * np.minimum((l + 1.0) * 2.0 * sh * sh, 2.0 * sh * eP),
+            step * np.minimum(0.5 * M, (l + 1.0) * eP / np.maximum(sn, 1.0 / (l + 1.0))))
+
+
+def dG(ells, theta, kind):
+    """The bound of the absolute error of G_kind[l, e] (see the module's docstring)."""
+    ells = np.asarray(ells, dtype=np.float64)
+    theta = np.atleast_1d(np.asarray(theta, dtype=np.float64))
+    l = ells[:, None]
+    M = l * (l + 1.0)
+    s, _, x = half_angle(theta)
+    ax = np.abs(x)[None, :]
+    dP, dD, dPp = carried_bounds(l, theta)
+    dQ = 2.0 * dD / (2.0 * l + 1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if kind == "w":
+            rec = dQ
+        elif kind == "gammat":
+            rec = (2.0 * ax * dP + (M + 2.0) * dQ) / np.sqrt(M * (M - 2.0))
+        else:
+            a = 0.5 * l * (l - 1.0)
+            rec = (a * (M + 2.0) * dQ + (2.0 * a * ax + (M + 2.0) + 2.0 * (l * l - l + 1.0)) * dP
+                   + (8.0 + 4.0 * ax) * dPp) * 2.0 / (M * (M - 2.0))
+    rec = np.where(M * s[None, :] < SWITCH[kind], 0.0, rec)
+    out = C2 * U * np.abs(g_numpy(ells, theta, kind)) + rec
+    return np.where((l < 2.0) & (kind != "w"), 0.0, out)
+
+
+def weights_gate(ells, edges, kind):
+    edges = np.asarray(edges, dtype=np.float64)
+    d = dG(ells, edges, kind)
+    return (d[:, 1:] + d[:, :-1]) / cosdiff(edges[:-1], edges[1:])[None, :]
+
+
+# ---------------------------------------------------------------- the points of the weight checks
+# a = 1 arcmin with b/a = 1 + 2e-6, 1.001, 1.2 and 10, then out to pi: l theta from 2.9e-4 (l = 1) to 6e4 (l = 20000);
+# per switch (M s = 2.25 and 6.25) and l = 3, 40, 1000 a pair of edges 1e-6 either side of it.
+POINT_ELLS = np.array([1.0, 2.0, 3.0, 9.0, 40.0, 1000.0, 20000.0])
+_E = ARCMIN * np.cumprod([1.0, 1.0 + 2e-6, 1.001, 1.2, 10.0])
+POINT_EDGES = {"arcmin": np.concatenate([_E, [0.05, 1.0, np.pi * (1.0 - 1e-6), np.pi]])}
+
+
+def switch_angle(l, z):
+    return 2.0 * np.arcsin(np.sqrt(z / (l * (l + 1.0))))
+
+
+for _l in (3, 40, 1000):
+    POINT_EDGES[f"switch{_l}"] = np.array([switch_angle(_l, z) * f for z in (2.25, 6.25) for f in (1.0 - 1e-6, 1.0 + 1e-6)])
+
+
+def point_ells(name):
+    return POINT_ELLS if name == "arcmin" else np.array([float(name[6:])])
+
+
+@functools.lru_cache(maxsize=None)
+def point_reference(name):
+    """{kind: (nl, nt) mpmath weights} at point_ells(name) and POINT_EDGES[name]."""
+    return {k: weights_mpmath(point_ells(name), POINT_EDGES[name], k) for k in KINDS}
+
+
+# ---------------------------------------------------------------- covariance, node weights, binned xi
+def shear_factor(ells):
+    l = np.asarray(ells, dtype=np.float64)
+    return np.sqrt(((l + 2.0) * (l - 1.0)) / (l * (l + 1.0)))
+
+
+def noise_term(N, cd, P, Q, i, j, fsky):
+    """The closed-form noise x noise term of cov[P, i, Q, j], operation for operation as the kernel forms it; cd: the
+    bins' cos a - cos b (cosdiff of the whole edge vector, as the library forms it)."""
+    if i != j or P[2] != Q[2]:
+        return 0.0
+    cnt = np.float64((P[0] == Q[0] and P[1] == Q[1]) + (P[0] == Q[1] and P[1] == Q[0]))
+    area_pi = np.float64(4.0 * np.pi * fsky) * np.float64(np.pi)
+    return (cnt * (np.float64(N[P[0]]) * np.float64(N[P[1]]))) / (area_pi * (2.0 * cd[i]))
+
+
+def noise_matrix(N, edges, probes, fsky):
+    edges = np.asarray(edges, dtype=np.float64)
+    nt = len(edges) - 1
+    cd = cosdiff(edges[:-1], edges[1:])
+    out = np.zeros((len(probes), nt, len(probes), nt))
+    for p, P in enumerate(probes):
+        for q, Q in enumerate(probes):
+            for i in range(nt):
+                out[p, i, q, i] = noise_term(N, cd, P, Q, i, i, fsky)
+    return out
+
+
+def cov_numpy(nodes, C, N, edges, probes, fsky, with_gate=False):
+    """cov[P, i, Q, j] of the definition as an einsum over L, measure l + 1/2; with_gate: (cov, gate)."""
+    L = acm.multipoles(nodes)
+    Cl = acm.interp(nodes, C, L)
+    K = {k: weights_numpy(L, edges, k) for k in {p[2] for p in probes}}
+    D = {k: weights_gate(L, edges, k) for k in K} if with_gate else None
+    A = 4.0 * np.pi * fsky
+    cov = noise_matrix(N, edges, probes, fsky)
+    gate = 4.0 * U * np.abs(cov)
+    gam = L.size * U / (1.0 - L.size * U)
+    W = L + 0.5
+    for p, P in enumerate(probes):
+        for q, Q in enumerate(probes):
+            G, _ = acm.g_pq(Cl, N, P, Q)
+            Ki, Kj = K[P[2]], K[Q[2]]
+            cov[p, :, q, :] += np.einsum("l,li,lj->ij", W * G, Ki, Kj) / (2.0 * np.pi * A)
+            if with_gate:
+                w = W * np.abs(G)
+                Di, Dj, aKi, aKj = D[P[2]], D[Q[2]], np.abs(Ki), np.abs(Kj)
+                g = np.einsum("l,li,lj->ij", w, Di, aKj) + np.einsum("l,li,lj->ij", w, aKi, Dj) + \
+                    np.einsum("l,li,lj->ij", w, Di, Dj) + (C1 * U + gam) * np.einsum("l,li,lj->ij", w, aKi, aKj)
+                gate[p, :, q, :] += g / (2.0 * np.pi * A)
+    return (cov, gate) if with_gate else cov
+
+
+def cov_mpmath(nodes, C, N, edges, probes, fsky, dps=40):
+    """The definition, literally: 1/(4 pi A) sum (2 l + 1) K K (C^^ C^^ + C^^ C^^ - NN) plus the closed-form noise term."""
+    import mpmath as mp
+    L = acm.multipoles(nodes)
+    nt = len(edges) - 1
+    with mp.workdps(dps):
+        K = {k: weights_mpmath(L, edges, k, as_float=False) for k in {p[2] for p in probes}}
+        nd = [mp.mpf(float(v)) for v in nodes]
+        Nm = [mp.mpf(float(v)) for v in N]
+        e = [mp.mpf(float(v)) for v in edges]
+        A = 4 * mp.pi * mp.mpf(float(fsky))
+        npan, _ = acm.panels(nodes, L)
+        out = np.zeros((len(probes), nt, len(probes), nt))
+        for p, P in enumerate(probes):
+            for q, Q in enumerate(probes):
+                a, b, c, d = P[0], P[1], Q[0], Q[1]
+                kron = (a == c and b == d) + (a == d and b == c)
+                acc = [[mp.mpf(0)] * nt for _ in range(nt)]
+                for li, l in enumerate(L):
+                    n = int(npan[li])
+                    t = (mp.mpf(float(l)) - nd[n]) / (nd[n + 1] - nd[n])
+
+                    def hat(f, g):
+                        v = (1 - t) * mp.mpf(float(C[f][g][n])) + t * mp.mpf(float(C[f][g][n + 1]))
+                        return v + (Nm[f] if f == g else 0)
+                    G = hat(a, c) * hat(b, d) + hat(a, d) * hat(b, c) - kron * Nm[a] * Nm[b]
+                    for i in range(nt):
+                        for j in range(nt):
+                            acc[i][j] += (2 * mp.mpf(float(l)) + 1) * K[P[2]][li][i] * K[Q[2]][li][j] * G
+                for i in range(nt):
+                    for j in range(nt):
+                        v = acc[i][j] / (4 * mp.pi * A)
+                        if i == j and P[2] == Q[2]:
+                            v += kron * Nm[a] * Nm[b] / (A * 2 * mp.pi * (mp.cos(e[i]) - mp.cos(e[i + 1])))
+                        out[p, i, q, j] = float(v)
+    return out
+
+
+def node_weights_numpy(nodes, edges, kind, with_gate=False):
+    """R_kind[i, n] = sum_l (l + 1/2) K(l; i) h_n(l); with_gate: (R, gate)."""
+    L = acm.multipoles(nodes)
+    H = acm.hats(nodes, L)
+    K = weights_numpy(L, edges, kind)
+    W = (L + 0.5)[:, None]
+    R = (W * K).T @ H
+    if not with_gate:
+        return R
+    gam = L.size * U / (1.0 - L.size * U)
+    return R, (W * weights_gate(L, edges, kind)).T @ H + (6.0 * U + gam) * (W * np.abs(K)).T @ H
+
+
+def binned_mpmath(nodes, Cn, edges, kind, dps=40):
+    """xi_kind(bin i) = sum_{l in L} (2 l + 1)/(4 pi) K(l; i) C(l) in dps digits."""
+    import mpmath as mp
+    L = acm.multipoles(nodes)
+    npan, _ = acm.panels(nodes, L)
+    with mp.workdps(dps):
+        K = weights_mpmath(L, edges, kind, as_float=False)
+        nd = [mp.mpf(float(v)) for v in nodes]
+        out = []
+        for i in range(len(edges) - 1):
+            sm = mp.mpf(0)
+            for li, l in enumerate(L):
+                n = int(npan[li])
+                t = (mp.mpf(float(l)) - nd[n]) / (nd[n + 1] - nd[n])
+                sm += (2 * mp.mpf(float(l)) + 1) * K[li][i] * ((1 - t) * mp.mpf(float(Cn[n])) + t * mp.mpf(float(Cn[n + 1])))
+            out.append(float(sm / (4 * mp.pi)))
+    return np.array(out)
+
+
+def binned_gate(nodes, Cn, edges, kind):
+    R, gR = node_weights_numpy(nodes, edges, kind, with_gate=True)
+    nn = np.size(nodes)
+    return (gR @ np.abs(Cn) + (nn + 8.0) * U * (np.abs(R) @ np.abs(Cn))) / (2.0 * np.pi)
+
+
+# ---------------------------------------------------------------- the shapes of the covariance checks
+SPINS = (0, 2, 2)            # of angcov_model.three_fields' fields: a lens sample and two source bins
+# every probe the spins allow is here once or more: the ten kind pairs (w, gammat, xip, xim among themselves);
+# (1, 0, gammat) is (0, 1, gammat) written the other way round
+PROBES = [(0, 0, "w"), (0, 1, "gammat"), (0, 2, "gammat"), (1, 1, "xip"), (1, 1, "xim"), (2, 1, "xip"), (2, 2, "xim"),
+          (1, 0, "gammat")]

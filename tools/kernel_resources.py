@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, hankel.hip, angcov.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip, cib.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, hankel.hip, angcov.hip, curvedsky.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip, cib.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -65,9 +65,14 @@ KERNELS = [   # (label, regex on the mangled name)
     ("angular_transform_kernel<256,4,true,true,true,ChiThetaRadius>  (all three orders, hmg_angular_transform; hankel.hip)", r"24angular_transform_kernelILi256ELi4ELb1ELb1ELb1ENS_14ChiThetaRadiusEE"),
     ("angular_zsum_kernel  (the z sum of the angular transforms, hankel.hip)", r"19angular_zsum_kernelE"),
     ("angcov_weights_kernel  (bin-averaged Bessel weights K_0, K_2, K_4; angcov.hip)", r"21angcov_weights_kernelE"),
-    ("angcov_gaussian_kernel  (Gaussian covariance of angular correlation functions, 32 x 32 bins per wavefront; angcov.hip)", r"22angcov_gaussian_kernelE"),
-    ("angcov_combine_kernel  (its chunks' sums in order, the transpose and the noise term; angcov.hip)", r"21angcov_combine_kernelE"),
-    ("angcov_node_weights_kernel  (node weights R_mu; angcov.hip)", r"26angcov_node_weights_kernelE"),
+    ("angcov_gaussian_kernel<false>  (Gaussian covariance of angular correlation functions, 32 x 32 bins per wavefront; angcov.hip)", r"22angcov_gaussian_kernelILb0EE"),
+    ("angcov_combine_kernel<false>  (its chunks' sums in order, the transpose and the noise term; angcov.hip)", r"21angcov_combine_kernelILb0EE"),
+    ("angcov_node_weights_kernel<false>  (node weights R_mu; angcov.hip)", r"26angcov_node_weights_kernelILb0EE"),
+    ("angcov_gaussian_kernel<true>  (the same contraction with the curved-sky measure l + 1/2 and four kinds; angcov.hip)", r"22angcov_gaussian_kernelILb1EE"),
+    ("angcov_combine_kernel<true>  (its combine with the spherical noise term; angcov.hip)", r"21angcov_combine_kernelILb1EE"),
+    ("angcov_node_weights_kernel<true>  (curved-sky node weights R_kind; angcov.hip)", r"26angcov_node_weights_kernelILb1EE"),
+    ("curvedsky_weights_kernel  (bin-averaged Wigner-d weights of four kinds, one thread per edge; curvedsky.hip)", r"24curvedsky_weights_kernelE"),
+    ("curvedsky_scale_kernel  (shear factors of a node table; curvedsky.hip)", r"22curvedsky_scale_kernelE"),
     ("trispectrum_1h_kernel  (1-halo trispectrum, 64 x 64 tile, trispectrum.hip)", r"21trispectrum_1h_kernelE"),
     ("bispectrum_kernel  (bispectrum of three tracers, 1024 triangles per workgroup, bispectrum.hip)", r"17bispectrum_kernelE"),
     ("bispectrum_check_kernel  (its table and triangle check, bispectrum.hip)", r"23bispectrum_check_kernelE"),
@@ -109,7 +114,7 @@ KERNELS = [   # (label, regex on the mangled name)
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "hankel", "angcov", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "clusters", "cib", "sampled")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "hankel", "angcov", "curvedsky", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "clusters", "cib", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
