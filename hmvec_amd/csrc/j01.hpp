@@ -7,7 +7,11 @@
 // subtractions of j0.hpp and j1.hpp are), and its sine and cosine come from sincos_fast (sici.hpp: < 1 ulp of the result
 // + 2e-16 absolute) below 2^30 and from the library's full-range reduction beyond; both are scaled by
 // sqrt(2/(pi x)) <= 0.36 here, so the absolute error of J0 and J1 stays that of the Cephes forms (a few 1e-16) plus half
-// an ulp of x radians of phase, which the callers' gates carry as their phase term.
+// an ulp of x radians of phase, which the callers' gates carry as their phase term.  Measured on the device against
+// 50-digit arithmetic (tests/test_gpu_math_probe.py: zeros and their neighbours, both sides of 5 and of chi = 2^30, x to
+// 1e15), with u = 2^-53 and s = 1 for J0, min(1, x) for J1: |error| <= 8 u s + [x > 5] sqrt(2/(pi x)) (spacing(x)/2 +
+// 2e-16) everywhere; up to 5 the worst is 2.8 u (J0) and 1.7 u s (J1), above it the phase term is reached to 0.94 (J0)
+// and 0.97 (J1).  bessel_j0, bessel_j1 and bessel_j2 of j0.hpp and j1.hpp meet the same bound on both signs.
 #pragma once
 #include "j1.hpp"
 #include "sici.hpp"

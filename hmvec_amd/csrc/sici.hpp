@@ -20,7 +20,9 @@ constexpr double HALF_PI = 1.57079632679489661923;
 // Implementation notes:
 //  * the Horner chains contract to FMAs and the two quotients of each branch share one
 //    reciprocal (differs from sici_pos by a few ulp, |delta| < 1e-15 on Si/Ci, far inside
-//    the 1e-12 absolute gate on u(k));
+//    the 1e-12 absolute gate on u(k); on the device against 50-digit Si and Ci from 1e-8 to 1e8,
+//    tests/test_gpu_math_probe.py: 0.58 and 0.90 of 1e-15 + an ulp of the result + the share
+//    of the sine and cosine);
 //  * the 88 coefficients are read from a table in global memory at wave-uniform addresses,
 //    so they arrive in SGPRs through the scalar cache and feed the FMAs directly.  As
 //    compile-time constants they become 64-bit literals, which gfx950's VOP3 cannot encode:
@@ -60,8 +62,9 @@ __device__ __forceinline__ double horner1_s(double x, const double* __restrict__
     return a;
 }
 
-// 1/x to ~1 ulp: hardware estimate + two Newton steps (5 VALU ops instead of the ~10 of an
-// IEEE-exact division).  x must be finite, non-zero and normal.
+// 1/x to 1 ulp (measured on the device across the exponent range: 0.5 ulp, tests/test_gpu_math_probe.py;
+// with one Newton step it is 8.7 ulp): hardware estimate + two Newton steps (5 VALU ops instead of the
+// ~10 of an IEEE-exact division).  x must be finite, non-zero and normal.
 __device__ __forceinline__ double rcp_fast(double x) {
     double r = __builtin_amdgcn_rcp(x);
     double e = fma(-x, r, 1.0);
@@ -72,7 +75,12 @@ __device__ __forceinline__ double rcp_fast(double x) {
 
 // sin and cos of 0 <= x < 2^30 by a three-term Cody-Waite reduction (exact products under
 // FMA) and the fdlibm kernel polynomials on [-pi/4, pi/4]; |error| < 1 ulp of the result plus
-// 2e-16 absolute from the reduction.  About 30 VALU ops for both values.
+// the reduction's: the first step is exact, the other two round once each at the size of the
+// reduced argument r, so at most min(2e-16, 2 spacings of r) - next to a multiple of pi/2, where
+// the third term carries the leading digits, the result stays good to an ulp of ITSELF.  Measured
+// on the device against 50-digit arithmetic (tests/test_gpu_math_probe.py; the set holds the
+// doubles within 1.5e-15 of k pi/2 up to k = 5.8e8): 0.85 of that bound.  About 30 VALU ops for
+// both values.
 __device__ __forceinline__ void sincos_fast(double x, double& s, double& c) {
     const double kd = rint(x * 0.63661977236758134308);
     double r = fma(-kd, 1.5707963267948966, x);
@@ -164,7 +172,10 @@ __device__ __forceinline__ void sici_fast(const SiciTable* __restrict__ T, doubl
 // For x >= 64 the divergent asymptotic series
 //     x f(x) ~ sum_n (-1)^n (2n)! / x^(2n),     x^2 g(x) ~ sum_n (-1)^n (2n+1)! / x^(2n)
 // are at full double precision after 8 and 9 terms (first omitted terms 16!/64^16 = 2.6e-16 and
-// 19!/64^18 = 3.7e-16 of the sums; checked against 40-digit arithmetic on [64, 256]: 2.5e-16 and 4.2e-16):
+// 19!/64^18 = 3.7e-16 of the sums; checked against 40-digit arithmetic on [64, 256]: 2.5e-16 and 4.2e-16; as the
+// device evaluates them, with z = rcp_fast(x)^2, against 50 digits on [64, 1e8]: 3.9e-16 (f, at x = 4.8e5: the roundings
+// of z and of x z, not the truncation) and 3.9e-16 (g, at 64) - tests/test_gpu_math_probe.py, which also holds the
+// rationals below 64 to 8 x 2^-52 relative):
 // 17 FMAs and no division instead of the 35 FMAs and one reciprocal of the two rationals.
 constexpr double SICI_ASYM_X = 64.0;
 template <bool WANT_F>
