@@ -23,6 +23,9 @@ from .curvedsky import (bin_averaged_wigner, bin_averaged_wigner_device, curved_
                         curved_angular_cov, curved_angular_cov_device, curved_angular_spectra_device, curved_binned_from_cl,
                         curved_binned_from_cl_device, curved_cov_gaussian, curved_cov_gaussian_device, curved_project_cl_cov,
                         curved_project_cl_cov_device, shear_factor)  # (curved-sky bin-averaged correlation functions and their covariance: Wigner-d weights over integer l)
+from .nonlimber import (nonlimber_cl, nonlimber_cl_device, nonlimber_k_rule, nonlimber_transfer,  # noqa: F401
+                        nonlimber_transfer_device, refine_gzs, spherical_bessel,
+                        spherical_bessel_device)  # (non-Limber angular power spectra of separable sources: spherical Bessel transfer functions per field and their k sum)
 from .cov import (GaussianCov, bin_annuli, cl_cov_1halo, cl_cov_ssc, lensing_shape_noise, limber_samples,  # noqa: F401
                   shot_noise, sigma_b_disc)  # (covariances)
 from .bispectrum import F2, cl_bispectrum, tree_bispectrum  # noqa: F401  (bispectrum of three tracers)
@@ -35,7 +38,7 @@ from .clusters import (cluster_abundance_device, cluster_cl_cov, cluster_counts_
                        get_cluster_counts, powerlaw_lnobs, scatter_rule, sz_lnobs)  # (cluster number counts N(z, q) and their covariance: functions of a model)
 from .cib import (cib_defaults, cib_luminosities, cib_sed, cl_cib, emission_power_device, emission_tables, get_power_cib,  # noqa: F401
                   register_emission, sed_break, sub_rule)  # (the CIB halo model: multi-frequency spectra, crosses and C_ell: functions of a model)
-from . import angcov, angular, bispectrum, cib, clusters, cosmology, cov, curvedsky, fft, functions, gasprofiles, ksz, lensing, onepoint, params, quadrature, realspace, rsd, tinker, utils, xipoles  # noqa: F401
+from . import angcov, angular, bispectrum, cib, clusters, cosmology, cov, curvedsky, fft, functions, gasprofiles, ksz, lensing, nonlimber, onepoint, params, quadrature, realspace, rsd, tinker, utils, xipoles  # noqa: F401
 from .functions import __all__ as _fn_all
 
 __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "generic_profile_fft", "sigma_nfw",
@@ -47,6 +50,8 @@ __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "ge
            "curved_binned_from_cl", "curved_binned_from_cl_device", "curved_project_cl_cov", "curved_project_cl_cov_device",
            "shear_factor", "curved_angular_spectra_device", "curved_angular_cov", "curved_angular_cov_device",
            "curved_angular_binned", "curved_angular_binned_device", "curvedsky",
+           "spherical_bessel", "spherical_bessel_device", "nonlimber_transfer", "nonlimber_transfer_device", "nonlimber_cl",
+           "nonlimber_cl_device", "refine_gzs", "nonlimber_k_rule", "nonlimber",
            "GaussianCov", "bin_annuli", "shot_noise", "lensing_shape_noise", "cl_cov_1halo", "limber_samples", "cov",
            "cl_cov_ssc", "sigma_b_disc",
            "F2", "tree_bispectrum", "cl_bispectrum", "bispectrum",

@@ -77,7 +77,7 @@ def kernel_source_sha16():
     names = ["hmgrid.hip", "longgrid.hip", "longgrid.hpp", "rowdev.hpp", "sici.hpp", "ldsfft.hpp", "fastmath.hpp", "Makefile",
              "lensing.hip", "j0.hpp", "j1.hpp", "ksz.hip", "realspace.hip", "j01.hpp", "trispectrum.hip", "bispectrum.hip",
              "response.hip", "gasproj.hip", "i0e.hpp", "rsd.hip", "gauss_moments.hpp", "onepoint.hip",
-             "hodens.hip", "hankel.hip", "angcov.hip", "clusters.hip", "cib.hip", "curvedsky.hip"]
+             "hodens.hip", "hankel.hip", "angcov.hip", "clusters.hip", "cib.hip", "curvedsky.hip", "nonlimber.hip", "sphbessel.hpp"]
     names += sorted(os.path.join("kernels", n) for n in os.listdir(os.path.join(csrc, "kernels")) if n.endswith(".hpp"))
     for name in names:          # (runtime.hip / comm.hip / hmctx.hpp hold no device code: not part of the kernel identity)
         with open(os.path.join(csrc, name), "rb") as f:

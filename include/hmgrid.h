@@ -782,6 +782,34 @@ int hmg_curvedsky_node_weights(hmg_ctx* ctx, int nn, const double* d_nodes, int 
 int hmg_curvedsky_scale_spectra(hmg_ctx* ctx, int nf, int nn, const double* d_nodes, const int* h_spins,
                                 const int* d_spins, double* d_C);
 
+/* ---- non-Limber angular power spectra of separable sources -----------------------------------
+ * A spectrum that is separable between two lines of sight, P(z, z', k) = S_a(z, k) S_b(z', k) - the two-halo term
+ * P_lin L_a L_b is, with S = L sqrt(P_lin) - projects exactly through one transfer function per field:
+ *   T_l^f(kq_i) = sum_g src[f, g, i] j_l(kq_i chi_g),       src = (weights of the chi rule) x (window) x S_f(z_g, kq_i),
+ *   C_l^{ab} = (2/pi) sum_i wk_i kq_i^2 T_l^a(kq_i) T_l^b(kq_i),        l = 0 .. lmax.
+ * hmg_sph_bessel: d_out (lmax + 1, nx), out[l, n] = j_l(xs[n]) by the walk of hmvec_amd/csrc/sphbessel.hpp: upwards for
+ *   x >= lmax, Miller's downward recurrence from a start order that depends on lmax alone otherwise; a value below the
+ *   fp64 range is 0, never NaN.  A value depends on its x and on lmax (through the branch and the start order).
+ * hmg_nonlimber_transfer: d_out (F, lmax + 1, nkq) = T of d_src (F, ngz, nkq).  1 <= F <= HMG_NONLIMBER_FMAX per launch:
+ *   the walk at a point (kq_i, chi_g) runs once for all fields.  One workgroup of HMG_NONLIMBER_THREADS lanes per k node
+ *   walks the chi nodes in chunks of its width, orders in tiles of HMG_NONLIMBER_TILE through LDS; the sum over g has a
+ *   fixed order.
+ * hmg_nonlimber_cl: d_out (np, lmax + 1) = C_l of the pairs h_pairs / d_pairs (np, 2) of fields of d_T (F, lmax + 1, nkq).
+ * Contract: fp64, no atomics, every sum in a fixed order, bit-identical on repeat.  An element of T depends on its
+ * field's source column, its k node, the chi nodes and lmax alone - not on the other fields or the other k nodes of the
+ * call; it DOES depend on lmax (the branch x >= lmax and the start order): T_l of a call to lmax + 2 is not bit for bit
+ * T_l of a call to lmax.  C[P] does not depend on the other pairs, and C[(a, b)] and C[(b, a)] are the same bits.  This
+ * checks shapes and field indices; the Python layer checks values (positive increasing nodes, kq chi >= 1e-100).      */
+#define HMG_NONLIMBER_FMAX 16
+#define HMG_NONLIMBER_THREADS 256
+#define HMG_NONLIMBER_TILE 16
+#define HMG_NONLIMBER_LMAX 16384
+int hmg_sph_bessel(hmg_ctx* ctx, int lmax, int nx, const double* d_xs, double* d_out);
+int hmg_nonlimber_transfer(hmg_ctx* ctx, int F, int ngz, int nkq, int lmax, const double* d_kq, const double* d_chis,
+                           const double* d_src, double* d_out);
+int hmg_nonlimber_cl(hmg_ctx* ctx, int F, int nkq, int lmax, int np, const int* h_pairs, const int* d_pairs,
+                     const double* d_kq, const double* d_wk, const double* d_T, double* d_out);
+
 /* ---- 1-halo trispectrum of two spectra -----------------------------------------------------
  * hmg_trispectrum_1h: d_T (nz, n, n),
  *   T[z,i,j] = sum_m wm[m] nzm[z,m] s_ab[z,m,i] s_cd[z,m,j],

@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, hankel.hip, angcov.hip, curvedsky.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip, cib.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, hankel.hip, angcov.hip, curvedsky.hip, nonlimber.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip, cib.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -73,6 +73,9 @@ KERNELS = [   # (label, regex on the mangled name)
     ("angcov_node_weights_kernel<true>  (curved-sky node weights R_kind; angcov.hip)", r"26angcov_node_weights_kernelILb1EE"),
     ("curvedsky_weights_kernel  (bin-averaged Wigner-d weights of four kinds, one thread per edge; curvedsky.hip)", r"24curvedsky_weights_kernelE"),
     ("curvedsky_scale_kernel  (shear factors of a node table; curvedsky.hip)", r"22curvedsky_scale_kernelE"),
+    ("nonlimber_transfer_kernel  (non-Limber transfer functions: one k node per workgroup, 256 chi nodes per chunk, tiles of 16 orders through LDS; nonlimber.hip)", r"25nonlimber_transfer_kernelE"),
+    ("sph_bessel_kernel  (j_0 .. j_lmax at one argument per thread; nonlimber.hip)", r"17sph_bessel_kernelE"),
+    ("nonlimber_cl_kernel  (the k sum, one wavefront per (pair, l); nonlimber.hip)", r"19nonlimber_cl_kernelE"),
     ("trispectrum_1h_kernel  (1-halo trispectrum, 64 x 64 tile, trispectrum.hip)", r"21trispectrum_1h_kernelE"),
     ("bispectrum_kernel  (bispectrum of three tracers, 1024 triangles per workgroup, bispectrum.hip)", r"17bispectrum_kernelE"),
     ("bispectrum_check_kernel  (its table and triangle check, bispectrum.hip)", r"23bispectrum_check_kernelE"),
@@ -114,7 +117,7 @@ KERNELS = [   # (label, regex on the mangled name)
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "hankel", "angcov", "curvedsky", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "clusters", "cib", "sampled")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "hankel", "angcov", "curvedsky", "nonlimber", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "clusters", "cib", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
