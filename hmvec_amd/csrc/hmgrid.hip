@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "hmctx.hpp"
 #include "fastmath.hpp"
@@ -506,10 +507,18 @@ static int launch_group(hmg_ctx* c, const FusedArgs& A, int rows, const FftRider
             const NfwArgs none{};
             const NfwArgs& N = R.N ? *R.N : none;
             const size_t nfw_blocks = R.N ? R.nfw_blocks : 0;
-            REQUIRE((size_t)rows + R.nchain + nfw_blocks <= 2147483647u, "bad grid");
-            return launch_lds(tensor_group_kernel<B, P, M>, dim3((unsigned)(rows + R.nchain + nfw_blocks)), dim3(FUSED_NT),
-                              lds, c->stream, C, A, R.nchain, rows, N.T, N.acoef, N.ktile, N.nm, N.nk, N.cs, N.rss, N.zs,
-                              N.ks, N.uk, N.nser);
+            REQUIRE(nfw_blocks <= 2147483647u && (size_t)rows + R.nchain + nfw_blocks <= 2147483647u, "bad grid");
+            // the NFW role's workgroups take NR blocks each (nfw_row_group): HMG_NFW_ROWS_PER_WG on a grid that fills
+            // the chip many times over, one on a thin slab - there the longer workgroups lengthen the tail of the launch
+            auto go = [&](auto nr) {
+                constexpr int NR = decltype(nr)::value;
+                const size_t nfw_wgs = (nfw_blocks + NR - 1) / NR;
+                return launch_lds(tensor_group_kernel<B, P, M, NR>, dim3((unsigned)(rows + R.nchain + nfw_wgs)),
+                                  dim3(FUSED_NT), lds, c->stream, C, A, R.nchain, rows, N.T, N.acoef, N.ktile, N.nm, N.nk,
+                                  N.cs, N.rss, N.zs, N.ks, N.uk, N.nser, (int)nfw_blocks);
+            };
+            if (nfw_blocks >= (size_t)HMG_NFW_GROUP_MIN_PER_CU * c->num_cu) return go(std::integral_constant<int, HMG_NFW_ROWS_PER_WG>{});
+            return go(std::integral_constant<int, 1>{});
         } else {
             REQUIRE(false, "internal: the tensor group is compiled for compile-time plans only");
         }

@@ -184,11 +184,14 @@ __global__ __launch_bounds__(512, (fused_occ<MAXB, SPECM>())) void profile_group
 // rows group, a launch of its own in front of this one: ~11 us of a 0.1 ms thin-slab step).  The two kinds of rows are
 // both bound by fp64 issue and take the sum of their times, one kernel boundary less.  Profile rows first: measured
 // against alternating rows and NFW rows first on MI355X (0.308 / 0.324 / 0.321 ms at nz = 32).
-template <int MAXB, int MAXP, int SPECM>
+// NR: rows of the NFW role per workgroup (nfw_row_group); the NFW part of the grid is ceil(nfw_blocks / NR) workgroups.
+// The launch code takes HMG_NFW_ROWS_PER_WG on full grids and 1 on thin slabs (launch_group in hmgrid.hip).
+template <int MAXB, int MAXP, int SPECM, int NR = 1>
 __global__ __launch_bounds__(512, (fused_occ<MAXB, SPECM>())) void tensor_group_kernel(
     ChainArgs C, FusedArgs A, int nchain, int nprof, const SiciTable* __restrict__ T, const double* __restrict__ acoef,
     int ktile, int nm, int nk, const double* __restrict__ cs, const double* __restrict__ rss,
-    const double* __restrict__ zs, const double* __restrict__ ks, double* __restrict__ uk, int* __restrict__ nser) {
+    const double* __restrict__ zs, const double* __restrict__ ks, double* __restrict__ uk, int* __restrict__ nser,
+    int nfw_blocks) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     int b = blockIdx.x;
     if (b < nchain) {
@@ -197,7 +200,8 @@ __global__ __launch_bounds__(512, (fused_occ<MAXB, SPECM>())) void tensor_group_
     }
     b -= nchain;
     if (b < nprof) profile_fused_row<512, MAXB, MAXP, SPECM, false, true>(A, row_order(b, A.nm), smem);
-    else nfw_rows(T, acoef, ktile, nm, nk, cs, rss, zs, ks, uk, b - nprof, 512, threadIdx.x, nser);      // (nser: series deferral)
+    else      // (nser: series deferral)
+        nfw_row_group<512, NR>(T, acoef, ktile, nm, nk, cs, rss, zs, ks, uk, b - nprof, nfw_blocks, nser);
 }
 
 }  // namespace hmg

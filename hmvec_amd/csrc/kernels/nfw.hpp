@@ -161,9 +161,11 @@ __device__ __forceinline__ void nfw_rows(const SiciTable* __restrict__ T, const 
                                          const double* __restrict__ rss, const double* __restrict__ zs,
                                          const double* __restrict__ ks, double* __restrict__ uk, int blk, int nthr,
                                          int tid, int* __restrict__ nser = nullptr) {
-    // one (z,m) row per workgroup, the whole k axis in one tile: measured against two rows per workgroup
-    // (+4 %), half tiles (+40 %) and 128 threads per row (+-0): a workgroup's fixed cost is the latency of
-    // its scalar loads (row constants, series coefficients), not instructions
+    // one (z,m) row per nthr threads, the whole k axis in one tile.  Measured on whole rows of 4096 wavenumbers, 256
+    // threads: two rows per workgroup +4 %, half tiles +40 %, 128 threads per row +-0 - a workgroup's fixed cost is
+    // the latency of its scalar loads (row constants, series coefficients), not instructions.  Under series deferral a
+    // row is about 1600 wavenumbers and often none: there every wavefront's prologue counts, and the tensor group
+    // gives a row 256 of its 512 threads on full grids (nfw_row_group; profiles/r12/nfw_rows_per_wg_ab.txt)
     const int ktiles = (nk + ktile - 1) / ktile;
     const int brow = blk / ktiles;
     const int row = row_order(brow, nm);  // z*nm + m
@@ -268,6 +270,41 @@ __device__ __forceinline__ void nfw_rows(const SiciTable* __restrict__ T, const 
         const double scx = s2 * c1 - c2 * s1;  // sin(c x) = sin((1+c)x - x)
         // sin(cx)/((1+c)x) = scx * xc / xc^2
         __builtin_nontemporal_store((s1 * (si2 - si1) - scx * (xc * zc) + c1 * dci) * inv_mc, &dst[k]);
+    }
+}
+// Rows of the NFW role per workgroup of the tensor group (1, 2 or 4: NT / NR stays a multiple of the wavefront), and
+// the number of rows per compute unit from which the launch takes that form (below it: one row per workgroup).
+// Measured on MI355X at nm = 512, nk = 4096 against one row per workgroup (ms_per_step, medians of four alternating
+// runs; profiles/r12/nfw_rows_per_wg_ab.txt): two rows -14 us at nz = 32 (0.432 -> 0.418, every run faster than every
+// run before), -10 at nz = 24, -5 at 16, -3 at 12, +-0 at 8, +1.3 at nz = 4 (8 rows per unit: the launch is two rounds
+// of workgroups there and the longer NFW workgroups lengthen its tail); four rows 2 us better than two at nz = 32 and
+// worse than one from nz = 12 down.  Hence two rows from 24 rows per unit (nz = 12 on that grid) and one below.
+#ifndef HMG_NFW_ROWS_PER_WG
+#define HMG_NFW_ROWS_PER_WG 2
+#endif
+#ifndef HMG_NFW_GROUP_MIN_PER_CU
+#define HMG_NFW_GROUP_MIN_PER_CU 24
+#endif
+// The NFW role of a grouped launch whose workgroups have NT threads: workgroup q of the role serves NR consecutive
+// blocks of nfw_rows (positions of the heavy-first order), NT / NR threads each.  The sub-group index is
+// wave-uniform and goes through readfirstlane, so the row and everything derived from it stay in SGPRs and the
+// row's constants still arrive by scalar loads.  No barrier, no LDS: a sub-group past the last block returns.
+// nblk: blocks of the role.  NR == 1 is nfw_rows on the workgroup, instruction for instruction.
+template <int NT, int NR>
+__device__ __forceinline__ void nfw_row_group(const SiciTable* __restrict__ T, const double* __restrict__ acoef,
+                                              int ktile, int nm, int nk, const double* __restrict__ cs,
+                                              const double* __restrict__ rss, const double* __restrict__ zs,
+                                              const double* __restrict__ ks, double* __restrict__ uk, int q, int nblk,
+                                              int* __restrict__ nser) {
+    static_assert(NR >= 1 && NT % (64 * NR) == 0, "a sub-group is whole wavefronts");
+    if constexpr (NR == 1) {
+        nfw_rows(T, acoef, ktile, nm, nk, cs, rss, zs, ks, uk, q, NT, threadIdx.x, nser);
+    } else {
+        constexpr int nthr = NT / NR;
+        const int sub = __builtin_amdgcn_readfirstlane((int)threadIdx.x / nthr);
+        const int blk = q * NR + sub;
+        if (blk >= nblk) return;
+        nfw_rows(T, acoef, ktile, nm, nk, cs, rss, zs, ks, uk, blk, nthr, (int)threadIdx.x % nthr, nser);
     }
 }
 __global__ __launch_bounds__(256, HMG_NFW_OCC) void nfw_kernel(const SiciTable* __restrict__ T,

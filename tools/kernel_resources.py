@@ -13,7 +13,8 @@ sys.path.insert(0, HERE)
 KERNELS = [   # (label, regex on the mangled name)
     ("front_group_kernel<2>  (nz > 16)", r"front_group_kernelILi2E"),
     ("front_group_kernel<1>  (nz <= 16)", r"front_group_kernelILi1E"),
-    ("tensor_group_kernel<2,3,2500>  (nxs = 5000: chain | profile rows | NFW rows, the launch of a pass)", r"tensor_group_kernelILi2ELi3ELi2500E"),
+    ("tensor_group_kernel<2,3,2500,2>  (nxs = 5000: chain | profile rows | NFW rows two per workgroup, the launch of a pass on a full grid)", r"tensor_group_kernelILi2ELi3ELi2500ELi2EE"),
+    ("tensor_group_kernel<2,3,2500,1>  (the same with one NFW row per workgroup: thin slabs)", r"tensor_group_kernelILi2ELi3ELi2500ELi1EE"),
     ("rows_group_kernel  (HMG_NO_TENSOR_GROUP=1, and passes without a profile transform)", r"17rows_group_kernelE"),
     ("profile_group_kernel<2,3,2500>  (nxs = 5000; a second profile of a pass, HMG_NO_TENSOR_GROUP=1)", r"profile_group_kernelILi2ELi3ELi2500E"),
     ("power_batch_kernel<2,3,2,false,593,true>  (Config 3, full grid: the NFW tensor in the series slot)", r"power_batch_kernelILi2ELi3ELi2ELb0ELj593ELb1E"),
