@@ -26,8 +26,12 @@ correlation function of the same discretisation, R_mu C / (2 pi), and project an
 between nodes - cov.cl_cov_1halo's or cov.cl_cov_ssc's output - to real space, R_mu M R_nu^T / (4 pi^2).  The projection
 is linear and takes one matrix at a time; section 17's warning about the two measures of those matrices stays with the
 caller.  The kernels are in hmvec_amd/csrc/kernels/angcov.hpp.
+
+A sky is a Sky record: the names of a probe's third entry (orders here, kinds in curvedsky.py), its checks, its weights
+launch, its bins' geometry and its entry points.  The driver is here, once: the sky_* functions, bound to FLAT or CURVED.
 """
 import ctypes as C_
+from typing import Callable, NamedTuple, Optional
 
 import numpy as np
 
@@ -90,20 +94,34 @@ def check_multipoles(ells_int):
     return np.ascontiguousarray(l)
 
 
-def check_probes(probes, nf):
-    """The probes (f, g, mu) as an (np, 3) int32 array of (f, g, mu / 2)."""
+def sky_check_probes(sky, probes, nf, spins=None):
+    """The probes (f, g, name) as an (np, 3) int32 array of (f, g, index of the name); spins: 0 or 2 per field to hold them to."""
     out = []
     for p in probes:
         if len(p) != 3:
-            raise ValueError(f"a probe is (f, g, order), got {p!r}")
-        f, g, mu = p
-        (mu,), _ = check_orders(mu)
+            raise ValueError(f"a probe is (f, g, {sky.word}), got {p!r}")
+        f, g, name = p
+        (name,), _ = sky.check_names(name)
         if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (f, g)) or not (0 <= f < nf and 0 <= g < nf):
             raise ValueError(f"probe {p!r} names a field outside 0 .. {nf - 1}")
-        out.append((int(f), int(g), mu // 2))
+        if spins is not None and tuple(sorted((int(spins[f]), int(spins[g])))) != sky.spins[name]:
+            raise ValueError(f"probe {p!r}: {sky.word} {name!r} needs fields of spin {sky.spins[name]}, these have spin "
+                             f"{(int(spins[f]), int(spins[g]))}")
+        out.append((int(f), int(g), sky.names.index(name)))
     if not out:
         raise ValueError("at least one probe is needed")
     return np.ascontiguousarray(out, dtype=np.int32)
+
+
+def check_probes(probes, nf):
+    return sky_check_probes(FLAT, probes, nf)
+
+
+def check_spins(spins, nf):
+    s = np.asarray(spins)
+    if s.shape != (nf,) or any(isinstance(v, bool) or v not in (0, 2) for v in s.tolist()):
+        raise ValueError(f"spins must hold 0 or 2 for each of the {nf} fields, got {spins!r}")
+    return np.ascontiguousarray(s, dtype=np.int32)
 
 
 def check_noise(noise, nf):
@@ -139,17 +157,37 @@ def check_spectra(C, nn):
     return np.ascontiguousarray(C), C.shape[0]
 
 
+def _weights_launch(ctx, l0, nl, edges, orders, d_ells=None):
+    d_ells = ctx.upload(np.arange(l0, l0 + nl, dtype=np.float64)) if d_ells is None else d_ells     # (weights_device's)
+    nt, d_edges = edges.size - 1, ctx.upload(edges)
+    K = {o: ctx.empty((nl, nt)) for o in dict.fromkeys(orders)}
+    return ("hmg_angcov_weights", nl, nt, d_ells.ptr, d_edges.ptr, *(nat.ptr(K.get(o)) for o in ORDERS)), K, (d_ells, d_edges)
+
+
 def weights_device(ctx, d_ells, nl, edges, orders):
     """{order: DeviceArray (nl, nt)} of K_order at nl device multipoles: one launch for all the orders."""
-    nt = edges.size - 1
-    d_edges = ctx.upload(edges)
-    K = {o: ctx.empty((nl, nt)) for o in dict.fromkeys(orders)}
-    ctx.call("hmg_angcov_weights", nl, nt, d_ells.ptr, d_edges.ptr, *(nat.ptr(K.get(o)) for o in ORDERS))
+    launch, K, _keepalive = _weights_launch(ctx, None, nl, edges, orders, d_ells)
+    ctx.call(*launch)
     return K
 
 
-def _range_weights(ctx, l0, nl, edges, orders):
-    return weights_device(ctx, ctx.upload(np.arange(l0, l0 + nl, dtype=np.float64)), nl, edges, orders)
+class Sky(NamedTuple):
+    """What the driver needs of a sky, as data and plain functions: FLAT below, CURVED in curvedsky.py."""
+    names: tuple                # what a probe's third entry is drawn from; a name's place here is its index on the device
+    word: str                   # what the messages call a name
+    check_names: Callable       # a name or a sequence of them -> (tuple of names, whether a sequence was given)
+    spins: Optional[dict]       # name -> the sorted spins of its two fields; None where the names do not fix them
+    check_nodes: Callable
+    check_edges: Callable
+    weights_launch: Callable    # (ctx, l0, nl, edges, names) -> (arguments of ctx.call, {name: K (nl, nt)}, keepalive)
+    geometry: Callable          # edges -> the host vector of the bins that the combine kernel takes
+    gaussian: str               # the entry points
+    node_weights: str
+
+
+FLAT = Sky(names=ORDERS, word="order", check_names=check_orders, spins=None, check_nodes=check_nodes, check_edges=check_edges,
+           weights_launch=_weights_launch, geometry=lambda edges: edges, gaussian="hmg_angcov_gaussian",
+           node_weights="hmg_angcov_node_weights")
 
 
 def bin_averaged_bessel_device(ells_int, theta_edges, orders, *, ctx=None):
@@ -175,23 +213,39 @@ def bin_averaged_bessel(ells_int, theta_edges, orders, *, ctx=None):
     return outs if seq else outs[0]
 
 
-def real_cov_gaussian_device(ells, C, noise, theta_edges, probes, fsky, *, ctx=None):
-    """real_cov_gaussian with the result left on the device: a DeviceArray (nprobe, ntheta, nprobe, ntheta).  C may be a
-    DeviceArray (nf, nf, len(ells)): it is taken as it is, and of its entries those with f <= g are read."""
-    nodes, l0, nl = check_nodes(ells)
-    C, nf = check_spectra(C, nodes.size)
-    noise, edges, fsky = check_noise(noise, nf), check_edges(theta_edges), check_fsky(fsky)
-    pr = check_probes(probes, nf)
-    ctx = nat.context_or_default(ctx)
-    nt, np_ = edges.size - 1, pr.shape[0]
-    K = _range_weights(ctx, l0, nl, edges, [ORDERS[o] for o in sorted(set(pr[:, 2].tolist()))])
+def sky_gaussian_launches(sky, ctx, nodes, l0, nl, C, noise, edges, pr, fsky):
+    """(weights, contraction, cov, keepalive) of a Gaussian covariance of checked inputs: the arguments of its two ctx.calls
+    (the K of names that pr lacks stay NULL), the DeviceArray (np, nt, np, nt) they fill and the buffers they point into.
+    The one place where these arguments and the work buffer's size are spelled out: the timing tools launch from it too."""
+    nf, nt, np_ = noise.size, edges.size - 1, pr.shape[0]
+    weights, K, keep = sky.weights_launch(ctx, l0, nl, edges, [sky.names[i] for i in sorted(set(pr[:, 2].tolist()))])
     words = np_ * (np_ + 1) // 2 * ((nl - 1) // chunk() + 1) * nt * nt
     work, cov = ctx.empty((words,)), ctx.empty((np_, nt, np_, nt))
-    d_nodes, d_C, d_noise, d_edges, d_pr = ctx.upload(nodes), nat.as_device(ctx, C), ctx.upload(noise), ctx.upload(edges), ctx.upload_int32(pr)
-    ctx.call("hmg_angcov_gaussian", nf, nodes.size, d_nodes.ptr, d_C.ptr, d_noise.ptr, l0, nl, nt, d_edges.ptr, np_,
-             pr.ctypes.data_as(C_.POINTER(C_.c_int)), d_pr.ptr, 4.0 * np.pi * fsky,
-             *(nat.ptr(K.get(o)) for o in ORDERS), words, work.ptr, cov.ptr)
+    bufs = ctx.upload(nodes), nat.as_device(ctx, C), ctx.upload(noise), ctx.upload(sky.geometry(edges)), ctx.upload_int32(pr)
+    d_nodes, d_C, d_noise, d_geo, d_pr = (b.ptr for b in bufs)
+    contraction = (sky.gaussian, nf, nodes.size, d_nodes, d_C, d_noise, l0, nl, nt, d_geo, np_,
+                   pr.ctypes.data_as(C_.POINTER(C_.c_int)), d_pr, 4.0 * np.pi * fsky,
+                   *(nat.ptr(K.get(n)) for n in sky.names), words, work.ptr, cov.ptr)
+    return weights, contraction, cov, (keep, K, work, bufs, pr)
+
+
+def sky_cov_gaussian_device(sky, ells, C, noise, theta_edges, probes, fsky, *, spins=None, ctx=None):
+    """The Gaussian covariance of a sky as a DeviceArray (nprobe, ntheta, nprobe, ntheta).  C may be a DeviceArray (nf, nf,
+    len(ells)): it is taken as it is, and of its entries those with f <= g are read."""
+    nodes, l0, nl = sky.check_nodes(ells)
+    C, nf = check_spectra(C, nodes.size)
+    noise, edges, fsky = check_noise(noise, nf), sky.check_edges(theta_edges), check_fsky(fsky)
+    pr = sky_check_probes(sky, probes, nf, None if spins is None else check_spins(spins, nf))
+    ctx = nat.context_or_default(ctx)
+    weights, contraction, cov, _keepalive = sky_gaussian_launches(sky, ctx, nodes, l0, nl, C, noise, edges, pr, fsky)
+    ctx.call(*weights)
+    ctx.call(*contraction)
     return cov
+
+
+def real_cov_gaussian_device(ells, C, noise, theta_edges, probes, fsky, *, ctx=None):
+    """real_cov_gaussian with the result left on the device: sky_cov_gaussian_device of the flat sky."""
+    return sky_cov_gaussian_device(FLAT, ells, C, noise, theta_edges, probes, fsky, ctx=ctx)
 
 
 def real_cov_gaussian(ells, C, noise, theta_edges, probes, fsky, *, ctx=None):
@@ -214,13 +268,18 @@ def real_cov_gaussian(ells, C, noise, theta_edges, probes, fsky, *, ctx=None):
     return real_cov_gaussian_device(ells, C, noise, theta_edges, probes, fsky, ctx=ctx).numpy()
 
 
-def node_weights_device(ctx, nodes, l0, nl, edges, order, scale=1.0, by_node=False):
-    """scale * R_order as a DeviceArray (ntheta, nn), or (nn, ntheta) with by_node."""
-    nt = edges.size - 1
-    K = _range_weights(ctx, l0, nl, edges, (order,))[order]
+def sky_node_weights_device(sky, ctx, nodes, l0, nl, edges, name, scale=1.0, by_node=False):
+    """scale * R_name as a DeviceArray (ntheta, nn), or (nn, ntheta) with by_node."""
+    launch, K, _keepalive = sky.weights_launch(ctx, l0, nl, edges, (name,))
+    ctx.call(*launch)
+    nt, K = edges.size - 1, K[name]
     R = ctx.empty((nodes.size, nt) if by_node else (nt, nodes.size))
-    ctx.call("hmg_angcov_node_weights", nodes.size, ctx.upload(nodes).ptr, l0, nl, nt, K.ptr, float(scale), int(by_node), R.ptr)
+    ctx.call(sky.node_weights, nodes.size, ctx.upload(nodes).ptr, l0, nl, nt, K.ptr, float(scale), int(by_node), R.ptr)
     return R
+
+
+def node_weights_device(ctx, nodes, l0, nl, edges, order, scale=1.0, by_node=False):
+    return sky_node_weights_device(FLAT, ctx, nodes, l0, nl, edges, order, scale, by_node)
 
 
 def _matmul(ctx, A, B):
@@ -231,55 +290,75 @@ def _matmul(ctx, A, B):
     return out
 
 
-def binned_angular_from_cl_device(ells, C, theta_edges, order, *, ctx=None):
-    """binned_angular_from_cl with the result left on the device: a DeviceArray (ns, ntheta) for C of shape (ns, nn) (a
-    host array or a DeviceArray)."""
-    (order,), _ = check_orders(order)
-    nodes, l0, nl = check_nodes(ells)
-    edges = check_edges(theta_edges)
-    if not isinstance(C, nat.DeviceArray):
-        C = np.asarray(C, dtype=np.float64)
-        if not np.all(np.isfinite(C)):
-            raise ValueError("C must be finite")
+def _finite(a, what):
+    if not isinstance(a, nat.DeviceArray):              # (a DeviceArray is taken as it is)
+        a = np.asarray(a, dtype=np.float64)
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{what} must be finite")
+    return a
+
+
+def sky_binned_device(sky, ells, C, theta_edges, name, *, ctx=None):
+    """Bin-averaged xi of a sky left on the device: a DeviceArray (ns, ntheta) for C (ns, nn), a host array or a DeviceArray."""
+    (name,), _ = sky.check_names(name)
+    (nodes, l0, nl), edges, C = sky.check_nodes(ells), sky.check_edges(theta_edges), _finite(C, "C")
     if len(C.shape) != 2 or C.shape[1] != nodes.size or C.shape[0] < 1:
         raise ValueError(f"C must have shape (ns, {nodes.size}) with ns >= 1, got {tuple(C.shape)}")
     ctx = nat.context_or_default(ctx)
-    R = node_weights_device(ctx, nodes, l0, nl, edges, order, 0.5 / np.pi, by_node=True)
+    R = sky_node_weights_device(sky, ctx, nodes, l0, nl, edges, name, 0.5 / np.pi, by_node=True)
     return _matmul(ctx, nat.as_device(ctx, C), R)
+
+
+def sky_binned(sky, ells, C, theta_edges, name, *, ctx=None):
+    """sky_binned_device on the host, for C of any leading shape: that shape with ntheta last."""
+    Ch = np.asarray(C, dtype=np.float64)
+    if Ch.ndim < 1:
+        raise ValueError("C must have the nodes as its last axis")
+    flat, nt = Ch.reshape(-1, Ch.shape[-1]), np.size(theta_edges) - 1
+    if flat.shape[0] == 0:
+        sky.check_names(name), sky.check_nodes(ells), sky.check_edges(theta_edges)
+        return np.empty(Ch.shape[:-1] + (nt,))
+    return sky_binned_device(sky, ells, flat, theta_edges, name, ctx=ctx).numpy().reshape(Ch.shape[:-1] + (nt,))
+
+
+def sky_project_device(sky, M, ells, theta_edges, name1, name2, *, ctx=None):
+    """R_name1 M R_name2^T / (4 pi^2) of a sky left on the device, (ntheta, ntheta); M (nn, nn): a host array or a DeviceArray."""
+    (n1,), _ = sky.check_names(name1)
+    (n2,), _ = sky.check_names(name2)
+    (nodes, l0, nl), edges, M = sky.check_nodes(ells), sky.check_edges(theta_edges), _finite(M, "M")
+    if tuple(M.shape) != (nodes.size, nodes.size):
+        raise ValueError(f"M must have shape ({nodes.size}, {nodes.size}), got {tuple(M.shape)}")
+    ctx = nat.context_or_default(ctx)
+    R1 = sky_node_weights_device(sky, ctx, nodes, l0, nl, edges, n1, 0.5 / np.pi)
+    R2 = sky_node_weights_device(sky, ctx, nodes, l0, nl, edges, n2, 0.5 / np.pi, by_node=True)
+    return _matmul(ctx, _matmul(ctx, R1, nat.as_device(ctx, M)), R2)
+
+
+def sky_by_index(sky, probes, labels):
+    """The probes (label, label2, name) of a model-level call as (f, g, name) by the fields' positions in labels."""
+    index, pr = {lab: i for i, lab in enumerate(labels)}, []
+    for p in probes:
+        if len(p) != 3 or p[0] not in index or p[1] not in index:
+            raise ValueError(f"probe {p!r} must be (label, label2, {sky.word}) with labels out of {labels}")
+        pr.append((index[p[0]], index[p[1]], p[2]))
+    return pr
+
+
+def binned_angular_from_cl_device(ells, C, theta_edges, order, *, ctx=None):
+    """binned_angular_from_cl with the result left on the device: sky_binned_device of the flat sky."""
+    return sky_binned_device(FLAT, ells, C, theta_edges, order, ctx=ctx)
 
 
 def binned_angular_from_cl(ells, C, theta_edges, order, *, ctx=None):
     """Bin-averaged correlation function xi_order(bin i) = R_order[i, :] . C / (2 pi) of the spectra C[..., :] at the
     nodes ells (C linear in l between nodes, summed over the integers L): the discretisation real_cov_gaussian is the
     covariance of.  Arguments as for real_cov_gaussian; returns C's leading shape with ntheta last."""
-    Ch = np.asarray(C, dtype=np.float64)
-    if Ch.ndim < 1:
-        raise ValueError("C must have the nodes as its last axis")
-    flat = Ch.reshape(-1, Ch.shape[-1])
-    nt = np.size(theta_edges) - 1
-    if flat.shape[0] == 0:
-        check_orders(order), check_nodes(ells), check_edges(theta_edges)
-        return np.empty(Ch.shape[:-1] + (nt,))
-    return binned_angular_from_cl_device(ells, flat, theta_edges, order, ctx=ctx).numpy().reshape(Ch.shape[:-1] + (nt,))
+    return sky_binned(FLAT, ells, C, theta_edges, order, ctx=ctx)
 
 
 def project_cl_cov_device(M, ells, theta_edges, order1, order2, *, ctx=None):
-    """project_cl_cov with the result left on the device: a DeviceArray (ntheta, ntheta).  M: a host array or a
-    DeviceArray of shape (nn, nn)."""
-    (o1,), _ = check_orders(order1)
-    (o2,), _ = check_orders(order2)
-    nodes, l0, nl = check_nodes(ells)
-    edges = check_edges(theta_edges)
-    if not isinstance(M, nat.DeviceArray):
-        M = np.asarray(M, dtype=np.float64)
-        if not np.all(np.isfinite(M)):
-            raise ValueError("M must be finite")
-    if tuple(M.shape) != (nodes.size, nodes.size):
-        raise ValueError(f"M must have shape ({nodes.size}, {nodes.size}), got {tuple(M.shape)}")
-    ctx = nat.context_or_default(ctx)
-    R1 = node_weights_device(ctx, nodes, l0, nl, edges, o1, 0.5 / np.pi)
-    R2 = node_weights_device(ctx, nodes, l0, nl, edges, o2, 0.5 / np.pi, by_node=True)
-    return _matmul(ctx, _matmul(ctx, R1, nat.as_device(ctx, M)), R2)
+    """project_cl_cov with the result left on the device: sky_project_device of the flat sky."""
+    return sky_project_device(FLAT, M, ells, theta_edges, order1, order2, ctx=ctx)
 
 
 def project_cl_cov(M, ells, theta_edges, order1, order2, *, ctx=None):
@@ -349,10 +428,5 @@ def angular_cov(model, theta_edges, probes, fields, fsky, ells, term="total"):
     model, like cov.cl_cov_1halo and cov.cl_cov_ssc: the attribute surface of HaloModel is pinned
     (tests/test_facade_cpu.py) and stays as it is."""
     labels, Ctab, noise = angular_cov_spectra_device(model, fields, ells, term)
-    index = {lab: i for i, lab in enumerate(labels)}
-    pr = []
-    for p in probes:
-        if len(p) != 3 or p[0] not in index or p[1] not in index:
-            raise ValueError(f"probe {p!r} must be (label, label2, order) with labels out of {labels}")
-        pr.append((index[p[0]], index[p[1]], p[2]))
-    return real_cov_gaussian_device(ells, Ctab, noise, theta_edges, pr, fsky, ctx=model._ctx()).numpy()
+    return real_cov_gaussian_device(ells, Ctab, noise, theta_edges, sky_by_index(FLAT, probes, labels), fsky,
+                                    ctx=model._ctx()).numpy()

@@ -25,6 +25,8 @@ Shear factor: Limber spectra are those of the convergence; a spin-2 leg of a spe
 f(l) = sqrt((l + 2)(l - 1) / (l (l + 1))) (f for g-kappa -> g-E, f^2 for kappa-kappa -> E-E).  The free functions take
 spectra as given - the caller's E-mode spectra; the model-level functions apply f to the fields flagged spin 2 unless
 shear_factor=False.  The kernels are in hmvec_amd/csrc/kernels/curvedsky.hpp and angcov.hpp.
+
+A sky is an angcov.Sky record, CURVED this one; the driver is in angcov.py, and covariance, binned xi and projection bind it.
 """
 import ctypes as C_
 
@@ -32,6 +34,7 @@ import numpy as np
 
 from . import _native as nat
 from . import angcov
+from .angcov import check_spins
 
 __all__ = ["bin_averaged_wigner", "bin_averaged_wigner_device", "curved_cov_gaussian", "curved_cov_gaussian_device",
            "curved_binned_from_cl", "curved_binned_from_cl_device", "curved_project_cl_cov", "curved_project_cl_cov_device",
@@ -78,40 +81,27 @@ def cos_differences(edges):
     return 2.0 * (np.sin(0.5 * (a + b)) * np.sin(0.5 * (b - a)))
 
 
-def check_spins(spins, nf):
-    s = np.asarray(spins)
-    if s.shape != (nf,) or any(isinstance(v, bool) or v not in (0, 2) for v in s.tolist()):
-        raise ValueError(f"spins must hold 0 or 2 for each of the {nf} fields, got {spins!r}")
-    return np.ascontiguousarray(s, dtype=np.int32)
-
-
 def check_probes(probes, nf, spins=None):
-    """The probes (f, g, kind) as an (np, 3) int32 array of (f, g, index of the kind); with spins (0 or 2 per field) a
-    kind whose pair of spins is not its fields' is refused."""
-    out = []
-    for p in probes:
-        if len(p) != 3:
-            raise ValueError(f"a probe is (f, g, kind), got {p!r}")
-        f, g, kind = p
-        (kind,), _ = check_kinds(kind)
-        if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (f, g)) or not (0 <= f < nf and 0 <= g < nf):
-            raise ValueError(f"probe {p!r} names a field outside 0 .. {nf - 1}")
-        if spins is not None and tuple(sorted((int(spins[f]), int(spins[g])))) != KIND_SPINS[kind]:
-            raise ValueError(f"probe {p!r}: kind {kind!r} needs fields of spin {KIND_SPINS[kind]}, these have spin "
-                             f"{(int(spins[f]), int(spins[g]))}")
-        out.append((int(f), int(g), KINDS.index(kind)))
-    if not out:
-        raise ValueError("at least one probe is needed")
-    return np.ascontiguousarray(out, dtype=np.int32)
+    return angcov.sky_check_probes(CURVED, probes, nf, spins)
+
+
+def _weights_launch(ctx, l0, nl, edges, kinds):
+    nt = edges.size - 1
+    K = {k: ctx.empty((nl, nt)) for k in dict.fromkeys(kinds)}
+    d_edges, d_cd = ctx.upload(edges), ctx.upload(cos_differences(edges))
+    return ("hmg_curvedsky_weights", l0, nl, nt, d_edges.ptr, d_cd.ptr, *(nat.ptr(K.get(k)) for k in KINDS)), K, (d_edges, d_cd)
 
 
 def weights_device(ctx, l0, nl, edges, kinds):
     """{kind: DeviceArray (nl, nt)} of K_kind on l0 .. l0 + nl - 1: one launch for all the kinds."""
-    nt = edges.size - 1
-    K = {k: ctx.empty((nl, nt)) for k in dict.fromkeys(kinds)}
-    ctx.call("hmg_curvedsky_weights", l0, nl, nt, ctx.upload(edges).ptr, ctx.upload(cos_differences(edges)).ptr,
-             *(nat.ptr(K.get(k)) for k in KINDS))
+    launch, K, _keepalive = _weights_launch(ctx, l0, nl, edges, kinds)
+    ctx.call(*launch)
     return K
+
+
+CURVED = angcov.Sky(names=KINDS, word="kind", check_names=check_kinds, spins=KIND_SPINS, check_nodes=check_nodes,
+                    check_edges=check_edges, weights_launch=_weights_launch, geometry=cos_differences,
+                    gaussian="hmg_curvedsky_gaussian", node_weights="hmg_curvedsky_node_weights")
 
 
 def bin_averaged_wigner_device(ells_int, theta_edges, kinds, *, ctx=None):
@@ -153,24 +143,8 @@ def bin_averaged_wigner(ells_int, theta_edges, kinds, *, ctx=None):
 
 
 def curved_cov_gaussian_device(ells, C, noise, theta_edges, probes, fsky, *, spins=None, ctx=None):
-    """curved_cov_gaussian with the result left on the device: a DeviceArray (nprobe, ntheta, nprobe, ntheta).  C may be
-    a DeviceArray (nf, nf, len(ells)): it is taken as it is, and of its entries those with f <= g are read."""
-    nodes, l0, nl = check_nodes(ells)
-    C, nf = angcov.check_spectra(C, nodes.size)
-    noise, edges, fsky = angcov.check_noise(noise, nf), check_edges(theta_edges), angcov.check_fsky(fsky)
-    if spins is not None:
-        spins = check_spins(spins, nf)
-    pr = check_probes(probes, nf, spins)
-    ctx = nat.context_or_default(ctx)
-    nt, np_ = edges.size - 1, pr.shape[0]
-    K = weights_device(ctx, l0, nl, edges, [KINDS[k] for k in sorted(set(pr[:, 2].tolist()))])
-    words = np_ * (np_ + 1) // 2 * ((nl - 1) // angcov.chunk() + 1) * nt * nt
-    work, cov = ctx.empty((words,)), ctx.empty((np_, nt, np_, nt))
-    d_nodes, d_C, d_noise, d_pr = ctx.upload(nodes), nat.as_device(ctx, C), ctx.upload(noise), ctx.upload_int32(pr)
-    ctx.call("hmg_curvedsky_gaussian", nf, nodes.size, d_nodes.ptr, d_C.ptr, d_noise.ptr, l0, nl, nt,
-             ctx.upload(cos_differences(edges)).ptr, np_, pr.ctypes.data_as(C_.POINTER(C_.c_int)), d_pr.ptr,
-             4.0 * np.pi * fsky, *(nat.ptr(K.get(k)) for k in KINDS), words, work.ptr, cov.ptr)
-    return cov
+    """curved_cov_gaussian with the result left on the device: angcov.sky_cov_gaussian_device of the curved sky."""
+    return angcov.sky_cov_gaussian_device(CURVED, ells, C, noise, theta_edges, probes, fsky, spins=spins, ctx=ctx)
 
 
 def curved_cov_gaussian(ells, C, noise, theta_edges, probes, fsky, *, spins=None, ctx=None):
@@ -191,63 +165,24 @@ def curved_cov_gaussian(ells, C, noise, theta_edges, probes, fsky, *, spins=None
 
 
 def node_weights_device(ctx, nodes, l0, nl, edges, kind, scale=1.0, by_node=False):
-    """scale * R_kind as a DeviceArray (ntheta, nn), or (nn, ntheta) with by_node."""
-    nt = edges.size - 1
-    K = weights_device(ctx, l0, nl, edges, (kind,))[kind]
-    R = ctx.empty((nodes.size, nt) if by_node else (nt, nodes.size))
-    ctx.call("hmg_curvedsky_node_weights", nodes.size, ctx.upload(nodes).ptr, l0, nl, nt, K.ptr, float(scale), int(by_node),
-             R.ptr)
-    return R
+    return angcov.sky_node_weights_device(CURVED, ctx, nodes, l0, nl, edges, kind, scale, by_node)
 
 
 def curved_binned_from_cl_device(ells, C, theta_edges, kind, *, ctx=None):
-    """curved_binned_from_cl with the result left on the device: a DeviceArray (ns, ntheta) for C of shape (ns, nn) (a
-    host array or a DeviceArray)."""
-    (kind,), _ = check_kinds(kind)
-    nodes, l0, nl = check_nodes(ells)
-    edges = check_edges(theta_edges)
-    if not isinstance(C, nat.DeviceArray):
-        C = np.asarray(C, dtype=np.float64)
-        if not np.all(np.isfinite(C)):
-            raise ValueError("C must be finite")
-    if len(C.shape) != 2 or C.shape[1] != nodes.size or C.shape[0] < 1:
-        raise ValueError(f"C must have shape (ns, {nodes.size}) with ns >= 1, got {tuple(C.shape)}")
-    ctx = nat.context_or_default(ctx)
-    R = node_weights_device(ctx, nodes, l0, nl, edges, kind, 0.5 / np.pi, by_node=True)
-    return angcov._matmul(ctx, nat.as_device(ctx, C), R)
+    """curved_binned_from_cl with the result left on the device: angcov.sky_binned_device of the curved sky."""
+    return angcov.sky_binned_device(CURVED, ells, C, theta_edges, kind, ctx=ctx)
 
 
 def curved_binned_from_cl(ells, C, theta_edges, kind, *, ctx=None):
     """Bin-averaged curved-sky correlation function xi_kind(bin i) = R_kind[i, :] . C / (2 pi)
     = sum_{l in L} (2l + 1)/(4 pi) K_kind(l; i) C(l) of the spectra C[..., :] at the nodes ells: the discretisation
     curved_cov_gaussian is the covariance of.  Returns C's leading shape with ntheta last."""
-    Ch = np.asarray(C, dtype=np.float64)
-    if Ch.ndim < 1:
-        raise ValueError("C must have the nodes as its last axis")
-    flat = Ch.reshape(-1, Ch.shape[-1])
-    nt = np.size(theta_edges) - 1
-    if flat.shape[0] == 0:
-        check_kinds(kind), check_nodes(ells), check_edges(theta_edges)
-        return np.empty(Ch.shape[:-1] + (nt,))
-    return curved_binned_from_cl_device(ells, flat, theta_edges, kind, ctx=ctx).numpy().reshape(Ch.shape[:-1] + (nt,))
+    return angcov.sky_binned(CURVED, ells, C, theta_edges, kind, ctx=ctx)
 
 
 def curved_project_cl_cov_device(M, ells, theta_edges, kind1, kind2, *, ctx=None):
-    """curved_project_cl_cov with the result left on the device: a DeviceArray (ntheta, ntheta)."""
-    (k1,), _ = check_kinds(kind1)
-    (k2,), _ = check_kinds(kind2)
-    nodes, l0, nl = check_nodes(ells)
-    edges = check_edges(theta_edges)
-    if not isinstance(M, nat.DeviceArray):
-        M = np.asarray(M, dtype=np.float64)
-        if not np.all(np.isfinite(M)):
-            raise ValueError("M must be finite")
-    if tuple(M.shape) != (nodes.size, nodes.size):
-        raise ValueError(f"M must have shape ({nodes.size}, {nodes.size}), got {tuple(M.shape)}")
-    ctx = nat.context_or_default(ctx)
-    R1 = node_weights_device(ctx, nodes, l0, nl, edges, k1, 0.5 / np.pi)
-    R2 = node_weights_device(ctx, nodes, l0, nl, edges, k2, 0.5 / np.pi, by_node=True)
-    return angcov._matmul(ctx, angcov._matmul(ctx, R1, nat.as_device(ctx, M)), R2)
+    """curved_project_cl_cov with the result left on the device: angcov.sky_project_device of the curved sky."""
+    return angcov.sky_project_device(CURVED, M, ells, theta_edges, kind1, kind2, ctx=ctx)
 
 
 def curved_project_cl_cov(M, ells, theta_edges, kind1, kind2, *, ctx=None):
@@ -296,21 +231,11 @@ def curved_angular_spectra_device(model, fields, ells, term="total", shear_facto
     return labels, Ctab, noise, spins
 
 
-def _by_index(probes, labels):
-    index = {lab: i for i, lab in enumerate(labels)}
-    pr = []
-    for p in probes:
-        if len(p) != 3 or p[0] not in index or p[1] not in index:
-            raise ValueError(f"probe {p!r} must be (label, label2, kind) with labels out of {labels}")
-        pr.append((index[p[0]], index[p[1]], p[2]))
-    return pr
-
-
 def curved_angular_cov_device(model, theta_edges, probes, fields, fsky, ells, term="total", shear_factor=True):
     """curved_angular_cov with the result left on the device."""
     labels, Ctab, noise, spins = curved_angular_spectra_device(model, fields, ells, term, shear_factor)
-    return curved_cov_gaussian_device(ells, Ctab, noise, theta_edges, _by_index(probes, labels), fsky, spins=spins,
-                                      ctx=model._ctx())
+    return curved_cov_gaussian_device(ells, Ctab, noise, theta_edges, angcov.sky_by_index(CURVED, probes, labels), fsky,
+                                      spins=spins, ctx=model._ctx())
 
 
 def curved_angular_cov(model, theta_edges, probes, fields, fsky, ells, term="total", shear_factor=True):
@@ -326,7 +251,7 @@ def curved_angular_binned_device(model, theta_edges, probes, fields, ells, term=
     """curved_angular_binned with the result left on the device: a list of DeviceArrays (1, ntheta), one per probe."""
     labels, Ctab, _, spins = curved_angular_spectra_device(model, fields, ells, term, shear_factor)
     nf, nn = len(labels), Ctab.shape[2]
-    pr = check_probes(_by_index(probes, labels), nf, spins)
+    pr = check_probes(angcov.sky_by_index(CURVED, probes, labels), nf, spins)
     check_edges(theta_edges)
     out = []
     for f, g, k in pr.tolist():

@@ -9,6 +9,8 @@ and tests/test_gpu_angcov.py share.
 * ``cov_numpy`` / ``cov_mpmath``: the Gaussian covariance as an einsum over L and as a literal evaluation of the
   definition (C^^ C^^ + C^^ C^^ - NN, no term multiplied out) in 40 digits;
 * ``node_weights_numpy``, ``binned_mpmath``: R_mu and the bin-averaged correlation function;
+* these restatements, ``noise_matrix`` and ``binned_gate`` are written once for both skies: their last argument is a Sky
+  record (its weights functions, its measure, its noise denominator), FLAT by default; curvedsky_model binds CURVED;
 * the gates.  u = 2^-53.  A weight's absolute error bound is
       delta = 2 / ((b^2 - a^2) l^2) (dG(l b) + dG(l a)),     dG_mu(x) = C2 u |G_mu(x)| + coef_mu(x) dJ(x),
   dJ(x) = 4 u min(1, x) + [x > 5] 2 u x min(1, sqrt(2/(pi x))) the bound of j0.hpp / j1.hpp / j01.hpp (a few u of the
@@ -23,6 +25,7 @@ and tests/test_gpu_angcov.py share.
   is no headroom; with 16 it is 0.32, a factor of 3.
 """
 import functools
+from typing import Callable, NamedTuple
 
 import numpy as np
 from scipy.special import j0, j1
@@ -182,35 +185,53 @@ def noise_term(N, edges, P, Q, i, j, fsky):
     return (cnt * (np.float64(N[P[0]]) * np.float64(N[P[1]]))) / (area_pi * ((eb - ea) * (eb + ea)))
 
 
-def noise_matrix(N, edges, probes, fsky):
-    nt = len(edges) - 1
+class Sky(NamedTuple):
+    """What the restatements below need of a sky: FLAT here, curvedsky_model.CURVED.  The three weights functions are the
+    module's (those of mpmath as lists of mpf); the rest is how the sky enters the definitions."""
+    weights_numpy: Callable
+    weights_mpmath: Callable    # (ells, edges, name, dps)
+    weights_gate: Callable
+    measure: Callable           # of the float64 multipoles: what K K G is summed with, over 2 pi A
+    measure_mp: Callable        # (mp, l, A): the same in the definition's own words
+    noise_mp: Callable          # (mp, a, b, A): what N_a N_b is divided by on the diagonal of the bin [a, b]
+    noise_term: Callable        # the module's, and what it takes in place of the edges
+    noise_geometry: Callable
+
+
+FLAT = Sky(weights_numpy, lambda ells, edges, order, dps: weights_mpmath(ells, edges, order, dps, as_float=False), weights_gate,
+           measure=lambda L: L, measure_mp=lambda mp, l, A: l / (2 * mp.pi * A),
+           noise_mp=lambda mp, a, b, A: A * mp.pi * (b ** 2 - a ** 2), noise_term=noise_term, noise_geometry=lambda edges: edges)
+
+
+def noise_matrix(N, edges, probes, fsky, sky=FLAT):
+    nt, geometry = len(edges) - 1, sky.noise_geometry(edges)
     out = np.zeros((len(probes), nt, len(probes), nt))
     for p, P in enumerate(probes):
         for q, Q in enumerate(probes):
             for i in range(nt):
-                out[p, i, q, i] = noise_term(N, edges, P, Q, i, i, fsky)
+                out[p, i, q, i] = sky.noise_term(N, geometry, P, Q, i, i, fsky)
     return out
 
 
-def cov_numpy(nodes, C, N, edges, probes, fsky, with_gate=False):
+def cov_numpy(nodes, C, N, edges, probes, fsky, with_gate=False, sky=FLAT):
     """cov[P, i, Q, j] of the definition as an einsum over L; with_gate: (cov, gate), the gate of the docstring with
     the restatement's own K, G and terms as magnitudes (the restatement is pinned against mpmath on the CPU)."""
     L = multipoles(nodes)
     Cl = interp(nodes, C, L)
-    K = {o: weights_numpy(L, edges, o) for o in {p[2] for p in probes}}
-    D = {o: weights_gate(L, edges, o) for o in K} if with_gate else None
+    K = {o: sky.weights_numpy(L, edges, o) for o in {p[2] for p in probes}}
+    D = {o: sky.weights_gate(L, edges, o) for o in K} if with_gate else None
     A = 4.0 * np.pi * fsky
-    nt, npr = len(edges) - 1, len(probes)
-    cov = noise_matrix(N, edges, probes, fsky)
+    cov = noise_matrix(N, edges, probes, fsky, sky)
     gate = 4.0 * U * np.abs(cov)
     gam = L.size * U / (1.0 - L.size * U)
+    W = sky.measure(L)
     for p, P in enumerate(probes):
         for q, Q in enumerate(probes):
             G, _ = g_pq(Cl, N, P, Q)
             Ki, Kj = K[P[2]], K[Q[2]]
-            cov[p, :, q, :] += np.einsum("l,li,lj->ij", L * G, Ki, Kj) / (2.0 * np.pi * A)
+            cov[p, :, q, :] += np.einsum("l,li,lj->ij", W * G, Ki, Kj) / (2.0 * np.pi * A)
             if with_gate:
-                w = L * np.abs(G)
+                w = W * np.abs(G)
                 Di, Dj = D[P[2]], D[Q[2]]
                 aKi, aKj = np.abs(Ki), np.abs(Kj)
                 g = np.einsum("l,li,lj->ij", w, Di, aKj) + np.einsum("l,li,lj->ij", w, aKi, Dj) + \
@@ -219,14 +240,14 @@ def cov_numpy(nodes, C, N, edges, probes, fsky, with_gate=False):
     return (cov, gate) if with_gate else cov
 
 
-def cov_mpmath(nodes, C, N, edges, probes, fsky, dps=40):
-    """The definition, literally, in dps digits: C^^ = C + delta N, C^^ac C^^bd + C^^ad C^^bc - NN, summed over L, plus
-    the closed-form noise term."""
+def cov_mpmath(nodes, C, N, edges, probes, fsky, dps=40, sky=FLAT):
+    """The definition, literally, in dps digits: C^^ = C + delta N, C^^ac C^^bd + C^^ad C^^bc - NN, summed over L with
+    the sky's measure - l / (2 pi A), or (2 l + 1) / (4 pi A) on the curved sky - plus the closed-form noise term."""
     import mpmath as mp
     L = multipoles(nodes)
-    nt, nf = len(edges) - 1, len(N)
+    nt = len(edges) - 1
     with mp.workdps(dps):
-        K = {o: weights_mpmath(L, edges, o, dps, as_float=False) for o in {p[2] for p in probes}}
+        K = {o: sky.weights_mpmath(L, edges, o, dps) for o in {p[2] for p in probes}}
         nd = [mp.mpf(float(v)) for v in nodes]
         Nm = [mp.mpf(float(v)) for v in N]
         e = [mp.mpf(float(v)) for v in edges]
@@ -239,61 +260,61 @@ def cov_mpmath(nodes, C, N, edges, probes, fsky, dps=40):
                 kron = (a == c and b == d) + (a == d and b == c)
                 acc = [[mp.mpf(0)] * nt for _ in range(nt)]
                 for li, l in enumerate(L):
-                    n = int(npan[li])
-                    t = (mp.mpf(float(l)) - nd[n]) / (nd[n + 1] - nd[n])
+                    n, l = int(npan[li]), mp.mpf(float(l))
+                    t = (l - nd[n]) / (nd[n + 1] - nd[n])
 
                     def hat(f, g):
                         v = (1 - t) * mp.mpf(float(C[f][g][n])) + t * mp.mpf(float(C[f][g][n + 1]))
                         return v + (Nm[f] if f == g else 0)
-                    G = hat(a, c) * hat(b, d) + hat(a, d) * hat(b, c) - kron * Nm[a] * Nm[b]
+                    G = (hat(a, c) * hat(b, d) + hat(a, d) * hat(b, c) - kron * Nm[a] * Nm[b]) * sky.measure_mp(mp, l, A)
                     for i in range(nt):
                         for j in range(nt):
-                            acc[i][j] += mp.mpf(float(l)) * K[P[2]][li][i] * K[Q[2]][li][j] * G
+                            acc[i][j] += K[P[2]][li][i] * K[Q[2]][li][j] * G
                 for i in range(nt):
                     for j in range(nt):
-                        v = acc[i][j] / (2 * mp.pi * A)
+                        v = acc[i][j]
                         if i == j and P[2] == Q[2]:
-                            v += kron * Nm[a] * Nm[b] / (A * mp.pi * (e[i + 1] ** 2 - e[i] ** 2))
+                            v += kron * Nm[a] * Nm[b] / sky.noise_mp(mp, e[i], e[i + 1], A)
                         out[p, i, q, j] = float(v)
     return out
 
 
-def node_weights_numpy(nodes, edges, order, with_gate=False):
-    """R_order[i, n] = sum_l l K(l; i) h_n(l); with_gate: (R, gate)."""
+def node_weights_numpy(nodes, edges, order, with_gate=False, sky=FLAT):
+    """R_order[i, n] = sum_l l K(l; i) h_n(l), l the sky's measure (l + 1/2 on the curved sky); with_gate: (R, gate)."""
     L = multipoles(nodes)
     H = hats(nodes, L)
-    K = weights_numpy(L, edges, order)
-    R = (L[:, None] * K).T @ H
+    K = sky.weights_numpy(L, edges, order)
+    W = sky.measure(L)[:, None]
+    R = (W * K).T @ H
     if not with_gate:
         return R
     gam = L.size * U / (1.0 - L.size * U)
-    gate = (L[:, None] * weights_gate(L, edges, order)).T @ H + (6.0 * U + gam) * (L[:, None] * np.abs(K)).T @ H
-    return R, gate
+    return R, (W * sky.weights_gate(L, edges, order)).T @ H + (6.0 * U + gam) * (W * np.abs(K)).T @ H
 
 
-def binned_mpmath(nodes, Cn, edges, order, dps=40):
-    """xi_order(bin i) = 1/(2 pi) sum_{l in L} l K(l; i) C(l) in dps digits."""
+def binned_mpmath(nodes, Cn, edges, order, dps=40, sky=FLAT):
+    """xi_order(bin i) = sum_{l in L} l / (2 pi) K(l; i) C(l), on the curved sky (2 l + 1) / (4 pi) K C, in dps digits."""
     import mpmath as mp
     L = multipoles(nodes)
     npan, _ = panels(nodes, L)
     with mp.workdps(dps):
-        K = weights_mpmath(L, edges, order, dps, as_float=False)
+        K = sky.weights_mpmath(L, edges, order, dps)
         nd = [mp.mpf(float(v)) for v in nodes]
         out = []
         for i in range(len(edges) - 1):
             s = mp.mpf(0)
             for li, l in enumerate(L):
-                n = int(npan[li])
-                t = (mp.mpf(float(l)) - nd[n]) / (nd[n + 1] - nd[n])
-                s += mp.mpf(float(l)) * K[li][i] * ((1 - t) * mp.mpf(float(Cn[n])) + t * mp.mpf(float(Cn[n + 1])))
-            out.append(float(s / (2 * mp.pi)))
+                n, l = int(npan[li]), mp.mpf(float(l))
+                t = (l - nd[n]) / (nd[n + 1] - nd[n])
+                s += sky.measure_mp(mp, l, 1) * K[li][i] * ((1 - t) * mp.mpf(float(Cn[n])) + t * mp.mpf(float(Cn[n + 1])))
+            out.append(float(s))
     return np.array(out)
 
 
-def binned_gate(nodes, Cn, edges, order):
+def binned_gate(nodes, Cn, edges, order, sky=FLAT):
     """The gate of binned_angular_from_cl: the node weights' gate against |C| plus the rounding of the product with C
     (nn terms, the scale 1/(2 pi) and the interpolation weights)."""
-    R, gR = node_weights_numpy(nodes, edges, order, with_gate=True)
+    R, gR = node_weights_numpy(nodes, edges, order, with_gate=True, sky=sky)
     nn = np.size(nodes)
     return (gR @ np.abs(Cn) + (nn + 8.0) * U * (np.abs(R) @ np.abs(Cn))) / (2.0 * np.pi)
 

@@ -11,7 +11,7 @@ s = sin^2(theta/2), t = 2 s, G_kind(l; theta) = int_0^theta sin d_kind^l and K =
   antiderivatives, nothing rewritten) on 90-digit recurrences, rounded to 40 digits' worth and then to float64;
   ``g_quad`` is the quadrature of the definition (Jacobi polynomials) that checks them;
 * ``cov_numpy`` / ``cov_mpmath``, ``node_weights_numpy``, ``binned_mpmath``: section 23's with l -> l + 1/2 and
-  pi (b^2 - a^2) -> 2 pi (cos a - cos b);
+  pi (b^2 - a^2) -> 2 pi (cos a - cos b) - angcov_model's own functions, bound to the record CURVED that says so;
 * the gates.  u = 2^-53.  dG = C2 u |G| + (the closed form's coefficients) x (the bounds of what the recurrences carry),
       dP_l  = CR u (l + 1) eP,                 eP  = min(1, sqrt(2 / (pi (l + 1/2) sin theta)))      (Bernstein)
       dD_l  = CR u (l + 1) min((l + 1) t, 2 sin(theta/2) eP),        D_l = P_{l+1} - P_l
@@ -284,117 +284,17 @@ def noise_term(N, cd, P, Q, i, j, fsky):
     return (cnt * (np.float64(N[P[0]]) * np.float64(N[P[1]]))) / (area_pi * (2.0 * cd[i]))
 
 
-def noise_matrix(N, edges, probes, fsky):
-    edges = np.asarray(edges, dtype=np.float64)
-    nt = len(edges) - 1
-    cd = cosdiff(edges[:-1], edges[1:])
-    out = np.zeros((len(probes), nt, len(probes), nt))
-    for p, P in enumerate(probes):
-        for q, Q in enumerate(probes):
-            for i in range(nt):
-                out[p, i, q, i] = noise_term(N, cd, P, Q, i, i, fsky)
-    return out
-
-
-def cov_numpy(nodes, C, N, edges, probes, fsky, with_gate=False):
-    """cov[P, i, Q, j] of the definition as an einsum over L, measure l + 1/2; with_gate: (cov, gate)."""
-    L = acm.multipoles(nodes)
-    Cl = acm.interp(nodes, C, L)
-    K = {k: weights_numpy(L, edges, k) for k in {p[2] for p in probes}}
-    D = {k: weights_gate(L, edges, k) for k in K} if with_gate else None
-    A = 4.0 * np.pi * fsky
-    cov = noise_matrix(N, edges, probes, fsky)
-    gate = 4.0 * U * np.abs(cov)
-    gam = L.size * U / (1.0 - L.size * U)
-    W = L + 0.5
-    for p, P in enumerate(probes):
-        for q, Q in enumerate(probes):
-            G, _ = acm.g_pq(Cl, N, P, Q)
-            Ki, Kj = K[P[2]], K[Q[2]]
-            cov[p, :, q, :] += np.einsum("l,li,lj->ij", W * G, Ki, Kj) / (2.0 * np.pi * A)
-            if with_gate:
-                w = W * np.abs(G)
-                Di, Dj, aKi, aKj = D[P[2]], D[Q[2]], np.abs(Ki), np.abs(Kj)
-                g = np.einsum("l,li,lj->ij", w, Di, aKj) + np.einsum("l,li,lj->ij", w, aKi, Dj) + \
-                    np.einsum("l,li,lj->ij", w, Di, Dj) + (C1 * U + gam) * np.einsum("l,li,lj->ij", w, aKi, aKj)
-                gate[p, :, q, :] += g / (2.0 * np.pi * A)
-    return (cov, gate) if with_gate else cov
-
-
-def cov_mpmath(nodes, C, N, edges, probes, fsky, dps=40):
-    """The definition, literally: 1/(4 pi A) sum (2 l + 1) K K (C^^ C^^ + C^^ C^^ - NN) plus the closed-form noise term."""
-    import mpmath as mp
-    L = acm.multipoles(nodes)
-    nt = len(edges) - 1
-    with mp.workdps(dps):
-        K = {k: weights_mpmath(L, edges, k, as_float=False) for k in {p[2] for p in probes}}
-        nd = [mp.mpf(float(v)) for v in nodes]
-        Nm = [mp.mpf(float(v)) for v in N]
-        e = [mp.mpf(float(v)) for v in edges]
-        A = 4 * mp.pi * mp.mpf(float(fsky))
-        npan, _ = acm.panels(nodes, L)
-        out = np.zeros((len(probes), nt, len(probes), nt))
-        for p, P in enumerate(probes):
-            for q, Q in enumerate(probes):
-                a, b, c, d = P[0], P[1], Q[0], Q[1]
-                kron = (a == c and b == d) + (a == d and b == c)
-                acc = [[mp.mpf(0)] * nt for _ in range(nt)]
-                for li, l in enumerate(L):
-                    n = int(npan[li])
-                    t = (mp.mpf(float(l)) - nd[n]) / (nd[n + 1] - nd[n])
-
-                    def hat(f, g):
-                        v = (1 - t) * mp.mpf(float(C[f][g][n])) + t * mp.mpf(float(C[f][g][n + 1]))
-                        return v + (Nm[f] if f == g else 0)
-                    G = hat(a, c) * hat(b, d) + hat(a, d) * hat(b, c) - kron * Nm[a] * Nm[b]
-                    for i in range(nt):
-                        for j in range(nt):
-                            acc[i][j] += (2 * mp.mpf(float(l)) + 1) * K[P[2]][li][i] * K[Q[2]][li][j] * G
-                for i in range(nt):
-                    for j in range(nt):
-                        v = acc[i][j] / (4 * mp.pi * A)
-                        if i == j and P[2] == Q[2]:
-                            v += kron * Nm[a] * Nm[b] / (A * 2 * mp.pi * (mp.cos(e[i]) - mp.cos(e[i + 1])))
-                        out[p, i, q, j] = float(v)
-    return out
-
-
-def node_weights_numpy(nodes, edges, kind, with_gate=False):
-    """R_kind[i, n] = sum_l (l + 1/2) K(l; i) h_n(l); with_gate: (R, gate)."""
-    L = acm.multipoles(nodes)
-    H = acm.hats(nodes, L)
-    K = weights_numpy(L, edges, kind)
-    W = (L + 0.5)[:, None]
-    R = (W * K).T @ H
-    if not with_gate:
-        return R
-    gam = L.size * U / (1.0 - L.size * U)
-    return R, (W * weights_gate(L, edges, kind)).T @ H + (6.0 * U + gam) * (W * np.abs(K)).T @ H
-
-
-def binned_mpmath(nodes, Cn, edges, kind, dps=40):
-    """xi_kind(bin i) = sum_{l in L} (2 l + 1)/(4 pi) K(l; i) C(l) in dps digits."""
-    import mpmath as mp
-    L = acm.multipoles(nodes)
-    npan, _ = acm.panels(nodes, L)
-    with mp.workdps(dps):
-        K = weights_mpmath(L, edges, kind, as_float=False)
-        nd = [mp.mpf(float(v)) for v in nodes]
-        out = []
-        for i in range(len(edges) - 1):
-            sm = mp.mpf(0)
-            for li, l in enumerate(L):
-                n = int(npan[li])
-                t = (mp.mpf(float(l)) - nd[n]) / (nd[n + 1] - nd[n])
-                sm += (2 * mp.mpf(float(l)) + 1) * K[li][i] * ((1 - t) * mp.mpf(float(Cn[n])) + t * mp.mpf(float(Cn[n + 1])))
-            out.append(float(sm / (4 * mp.pi)))
-    return np.array(out)
-
-
-def binned_gate(nodes, Cn, edges, kind):
-    R, gR = node_weights_numpy(nodes, edges, kind, with_gate=True)
-    nn = np.size(nodes)
-    return (gR @ np.abs(Cn) + (nn + 8.0) * U * (np.abs(R) @ np.abs(Cn))) / (2.0 * np.pi)
+CURVED = acm.Sky(weights_numpy, lambda ells, edges, kind, dps: weights_mpmath(ells, edges, kind, as_float=False), weights_gate,
+                 measure=lambda L: L + 0.5, measure_mp=lambda mp, l, A: (2 * l + 1) / (4 * mp.pi * A),
+                 noise_mp=lambda mp, a, b, A: A * 2 * mp.pi * (mp.cos(a) - mp.cos(b)), noise_term=noise_term,
+                 noise_geometry=lambda edges: cosdiff(edges[:-1], edges[1:]))
+# angcov_model's restatements on this sky, with its signatures
+noise_matrix = functools.partial(acm.noise_matrix, sky=CURVED)
+cov_numpy = functools.partial(acm.cov_numpy, sky=CURVED)
+cov_mpmath = functools.partial(acm.cov_mpmath, sky=CURVED)
+node_weights_numpy = functools.partial(acm.node_weights_numpy, sky=CURVED)
+binned_mpmath = functools.partial(acm.binned_mpmath, sky=CURVED)
+binned_gate = functools.partial(acm.binned_gate, sky=CURVED)
 
 
 # ---------------------------------------------------------------- the shapes of the covariance checks

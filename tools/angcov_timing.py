@@ -2,14 +2,13 @@
 """Device time of the Gaussian covariance of angular correlation functions on GPU 0 for a
 3x2pt-like data vector: 8 fields (3 lens bins, 5 source bins), 41 probes (w of the lens bins, gamma_t of every lens
 about every source bin, xi+ of 12 and xi- of 11 of the 15 source pairs), 20 bins in theta and 17 log-spaced nodes to
-l_max = 2e4.  Timed separately between event records on the context's stream: the weights launch
-(hmg_angcov_weights, three orders) and the contraction with its ordered combine (hmg_angcov_gaussian).  Inputs are
+l_max = 2e4.  Timed separately between event records on the context's stream: the weights launch (three orders) and
+the contraction with its ordered combine, both as angcov.sky_gaussian_launches builds them for the library.  Inputs are
 uploaded once; each timed window holds --batch launches.  Next to it, the wall time of the numpy einsum restatement
 (tests/helpers/angcov_model.cov_numpy) on the same host, once.  Prints one JSON line.
 
 Usage:  python tools/angcov_timing.py [--reps 10] [--warmup 2] [--batch 3]"""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -55,18 +54,11 @@ def main():
     Cn, noise = spectra(nodes)
     _, l0, nl = angcov.check_nodes(nodes)
     nt, np_, nf = edges.size - 1, len(probes), noise.size
-    d_ells, d_edges = ctx.upload(np.arange(l0, l0 + nl, dtype=np.float64)), ctx.upload(edges)
-    K = [ctx.empty((nl, nt)) for _ in range(3)]
     res = dict(fields=nf, probes=np_, bins=nt, multipoles=nl, nodes=int(nodes.size))
-    res["weights"] = timed(ctx, a.reps, a.warmup, a.batch, "hmg_angcov_weights", nl, nt, d_ells.ptr, d_edges.ptr,
-                           *(k.ptr for k in K))
-    pr = angcov.check_probes(probes, nf)
-    words = np_ * (np_ + 1) // 2 * ((nl - 1) // angcov.chunk() + 1) * nt * nt
-    work, cov = ctx.empty((words,)), ctx.empty((np_, nt, np_, nt))
-    d_nodes, d_C, d_noise, d_pr = ctx.upload(nodes), ctx.upload(Cn), ctx.upload(noise), ctx.upload_int32(pr)
-    res["gaussian"] = timed(ctx, a.reps, a.warmup, a.batch, "hmg_angcov_gaussian", nf, nodes.size, d_nodes.ptr, d_C.ptr,
-                            d_noise.ptr, l0, nl, nt, d_edges.ptr, np_, pr.ctypes.data_as(C.POINTER(C.c_int)), d_pr.ptr,
-                            4.0 * np.pi * fsky, *(k.ptr for k in K), words, work.ptr, cov.ptr)
+    weights, gaussian, cov, _keepalive = angcov.sky_gaussian_launches(
+        angcov.FLAT, ctx, nodes, l0, nl, Cn, noise, edges, angcov.check_probes(probes, nf), fsky)
+    res["weights"] = timed(ctx, a.reps, a.warmup, a.batch, *weights)
+    res["gaussian"] = timed(ctx, a.reps, a.warmup, a.batch, *gaussian)
     res["gaussian"]["fma"] = np_ * (np_ + 1) // 2 * nl * nt * nt
     got = cov.numpy()
     assert np.all(np.isfinite(got)) and np.array_equal(got, got.transpose(2, 3, 0, 1))

@@ -3,13 +3,12 @@
 tools/angcov_timing.py: 8 fields (3 lens bins of spin 0, 5 source bins of spin 2), 41 probes (w of the lens bins, gamma_t
 of every lens about every source bin, xi+ of 12 and xi- of 11 of the 15 source pairs), 20 bins in theta from 5e-4 to 0.1
 and 17 log-spaced nodes to l_max = 2e4.  Timed separately between event records on the context's stream: the weights
-launch (hmg_curvedsky_weights, four kinds: the recurrence from l = 0 at 21 edges), the contraction with its ordered
-combine (hmg_curvedsky_gaussian), and next to them the flat path's two launches on the same shape (hmg_angcov_weights,
-hmg_angcov_gaussian).  Inputs are uploaded once; each timed window holds --batch launches.  Prints one JSON line.
+launch (four kinds: the recurrence from l = 0 at 21 edges), the contraction with its ordered combine, and next to them
+the flat path's two launches on the same shape, all four as angcov.sky_gaussian_launches builds them for the library.
+Inputs are uploaded once; each timed window holds --batch launches.  Prints one JSON line.
 
 Usage:  python tools/curvedsky_timing.py [--reps 10] [--warmup 2] [--batch 3]"""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -47,31 +46,21 @@ def main():
     probes = curved_probes()
     pr = curvedsky.check_probes(probes, noise.size, spins)
     nt, np_, nf = edges.size - 1, len(probes), noise.size
-    d_edges, d_cd = ctx.upload(edges), ctx.upload(curvedsky.cos_differences(edges))
-    K = [ctx.empty((nl, nt)) for _ in range(4)]
     res = dict(fields=nf, probes=np_, bins=nt, multipoles=nl, nodes=int(nodes.size))
-    res["weights"] = timed(ctx, a.reps, a.warmup, a.batch, "hmg_curvedsky_weights", l0, nl, nt, d_edges.ptr, d_cd.ptr,
-                           *(k.ptr for k in K))
-    words = np_ * (np_ + 1) // 2 * ((nl - 1) // angcov.chunk() + 1) * nt * nt
-    work, cov = ctx.empty((words,)), ctx.empty((np_, nt, np_, nt))
-    d_nodes, d_C, d_noise, d_pr = ctx.upload(nodes), ctx.upload(Cn), ctx.upload(noise), ctx.upload_int32(pr)
-    res["gaussian"] = timed(ctx, a.reps, a.warmup, a.batch, "hmg_curvedsky_gaussian", nf, nodes.size, d_nodes.ptr, d_C.ptr,
-                            d_noise.ptr, l0, nl, nt, d_cd.ptr, np_, pr.ctypes.data_as(C.POINTER(C.c_int)), d_pr.ptr,
-                            4.0 * np.pi * fsky, *(k.ptr for k in K), words, work.ptr, cov.ptr)
+    weights, gaussian, cov, _keepalive = angcov.sky_gaussian_launches(curvedsky.CURVED, ctx, nodes, l0, nl, Cn, noise, edges, pr, fsky)
+    res["weights"] = timed(ctx, a.reps, a.warmup, a.batch, *weights)
+    res["gaussian"] = timed(ctx, a.reps, a.warmup, a.batch, *gaussian)
     res["total_median_ms"] = res["weights"]["median_ms"] + res["gaussian"]["median_ms"]
     got = cov.numpy()
     assert np.all(np.isfinite(got)) and np.array_equal(got, got.transpose(2, 3, 0, 1))
     assert np.array_equal(got, curvedsky.curved_cov_gaussian(nodes, Cn, noise, edges, probes, fsky, spins=spins, ctx=ctx))
     # the flat path on the same shape
-    fpr = angcov.check_probes(data_vector(), nf)
-    d_ells, d_fpr = ctx.upload(np.arange(l0, l0 + nl, dtype=np.float64)), ctx.upload_int32(fpr)
-    res["flat_weights"] = timed(ctx, a.reps, a.warmup, a.batch, "hmg_angcov_weights", nl, nt, d_ells.ptr, d_edges.ptr,
-                                *(k.ptr for k in K[:3]))
-    res["flat_gaussian"] = timed(ctx, a.reps, a.warmup, a.batch, "hmg_angcov_gaussian", nf, nodes.size, d_nodes.ptr,
-                                 d_C.ptr, d_noise.ptr, l0, nl, nt, d_edges.ptr, np_, fpr.ctypes.data_as(C.POINTER(C.c_int)),
-                                 d_fpr.ptr, 4.0 * np.pi * fsky, *(k.ptr for k in K[:3]), words, work.ptr, cov.ptr)
+    weights, gaussian, fcov, _fkeepalive = angcov.sky_gaussian_launches(
+        angcov.FLAT, ctx, nodes, l0, nl, Cn, noise, edges, angcov.check_probes(data_vector(), nf), fsky)
+    res["flat_weights"] = timed(ctx, a.reps, a.warmup, a.batch, *weights)
+    res["flat_gaussian"] = timed(ctx, a.reps, a.warmup, a.batch, *gaussian)
     res["flat_total_median_ms"] = res["flat_weights"]["median_ms"] + res["flat_gaussian"]["median_ms"]
-    flat = cov.numpy()
+    flat = fcov.numpy()
     res["max_rel_diff_curved_to_flat"] = float(np.max(np.abs(got - flat)) / np.max(np.abs(flat)))
     res["kernel_source_sha16"] = nat.kernel_source_sha16()
     print(json.dumps(res))
