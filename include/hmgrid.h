@@ -248,7 +248,10 @@ int hmg_profile_rows_from_mvir(hmg_ctx* ctx, int kind, int nz, int nm, const dou
  * wavenumbers by division with the mode spacing.
  * out[z,m,k] *= d_post[z,m] if d_post != NULL (pressure prefactor, hmvec.py:316).
  *
- * Routes (chosen by the library from the radial grid and the rows' support; same results to <= 1e-12 in u):
+ * Routes (chosen by the library from the radial grid and the rows' support; same results to <= 1e-12 in u, and each
+ * within K 2^-52 S(k) |post| of the 40-digit discrete transform of the same float64 inputs, S the l1 scale of the row's
+ * sum and K between 0.2 and 1.1 per route (3.9 for hmg_profile_fft_table, whose scale carries no integrand weights):
+ * DESIGN.md section 30, tests/test_gpu_profile_rows.py):
  *   nxs = 1000, 2000, 4000, 5000      one (z,m) row per workgroup, packed-real FFT in LDS, compile-time plan;
  *   other even nxs <= 12288 (M = nxs/2 <= HMG_FUSED_MAX_M = 6144) whose half factors into 2, 3, 4, 5 with at most four
  *     butterflies per thread in every pass: the same with a run-time plan - for M > 2500 (HMG_FUSED_PREFER_M) only

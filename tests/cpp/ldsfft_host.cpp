@@ -342,3 +342,13 @@ extern "C" int ldsfft_unpack_table_check(int nxs) {
     if (t.size() != twN.size()) return 1;
     return memcmp(t.data(), twN.data(), twN.size() * sizeof(UnpackTw)) ? 2 : 0;
 }
+
+// The plan fft_plan_fill makes for a length-M transform, for tests that restate the row kernels' predicates (the first
+// radix decides the pruned first pass, the last one the butterfly count of the pass that `keep` cuts down): the number
+// of passes, their radices in radix[0..npass), or 0 when M has no radix-2/3/4/5 plan.
+extern "C" int ldsfft_plan(int M, int* radix /* FFT_MAX_PASSES */) {
+    FftPlanDev plan;
+    if (M < 2 || !fft_make_plan(M, &plan)) return 0;
+    for (int p = 0; p < plan.npass; ++p) radix[p] = plan.radix[p];
+    return plan.npass;
+}
