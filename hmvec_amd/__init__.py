@@ -29,6 +29,8 @@ from .nonlimber import (nonlimber_cl, nonlimber_cl_device, nonlimber_k_rule, non
 from .cov import (GaussianCov, bin_annuli, cl_cov_1halo, cl_cov_ssc, lensing_shape_noise, limber_samples,  # noqa: F401
                   shot_noise, sigma_b_disc)  # (covariances)
 from .bispectrum import F2, cl_bispectrum, tree_bispectrum  # noqa: F401  (bispectrum of three tracers)
+from .connected import (AngleRule, F3s, angle_rule, cl_cov_connected, connected_trispectrum_device, get_trispectrum, plin_at,  # noqa: F401
+                        pt_averages, pt_averages_device, tree_trispectrum)  # (the 2-, 3- and 4-halo terms of the trispectrum and the connected covariance: functions of a model)
 from .rsd import legendre_weights, mu_rule, virial_dispersion  # noqa: F401  (redshift-space wedges and multipoles)
 from .xipoles import get_xi_multipoles, xi_multipoles_device, xi_multipoles_from_power  # noqa: F401  (redshift-space correlation multipoles xi_0, xi_2, xi_4(s): the j_0 / j_2 / j_4 transforms of P_0, P_2, P_4, of plain arrays and of a model)
 from .onepoint import char_exponent, cumulants, lambda_grid, pdf_from_exponent, ring_rule  # noqa: F401  (one-point PDF of a sum of halo profiles)
@@ -38,7 +40,7 @@ from .clusters import (cluster_abundance_device, cluster_cl_cov, cluster_counts_
                        get_cluster_counts, powerlaw_lnobs, scatter_rule, sz_lnobs)  # (cluster number counts N(z, q) and their covariance: functions of a model)
 from .cib import (cib_defaults, cib_luminosities, cib_sed, cl_cib, emission_power_device, emission_tables, get_power_cib,  # noqa: F401
                   register_emission, sed_break, sub_rule)  # (the CIB halo model: multi-frequency spectra, crosses and C_ell: functions of a model)
-from . import angcov, angular, bispectrum, cib, clusters, cosmology, cov, curvedsky, fft, functions, gasprofiles, ksz, lensing, nonlimber, onepoint, params, quadrature, realspace, rsd, tinker, utils, xipoles  # noqa: F401
+from . import angcov, angular, bispectrum, cib, clusters, connected, cosmology, cov, curvedsky, fft, functions, gasprofiles, ksz, lensing, nonlimber, onepoint, params, quadrature, realspace, rsd, tinker, utils, xipoles  # noqa: F401
 from .functions import __all__ as _fn_all
 
 __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "generic_profile_fft", "sigma_nfw",
@@ -55,6 +57,8 @@ __all__ = ["HaloModel", "Cosmology", "default_params", "battaglia_defaults", "ge
            "GaussianCov", "bin_annuli", "shot_noise", "lensing_shape_noise", "cl_cov_1halo", "limber_samples", "cov",
            "cl_cov_ssc", "sigma_b_disc",
            "F2", "tree_bispectrum", "cl_bispectrum", "bispectrum",
+           "AngleRule", "angle_rule", "plin_at", "F3s", "tree_trispectrum", "pt_averages", "pt_averages_device",
+           "connected_trispectrum_device", "get_trispectrum", "cl_cov_connected", "connected",
            "projected_gnfw", "gasprofiles",
            "virial_dispersion", "mu_rule", "legendre_weights", "rsd", "xi_multipoles_from_power", "xi_multipoles_device", "get_xi_multipoles", "xipoles",
            "char_exponent", "cumulants", "pdf_from_exponent", "lambda_grid", "ring_rule", "onepoint",

@@ -889,6 +889,48 @@ int hmg_response(hmg_ctx* ctx, int nz, int nm, int nk, int n, int np, const hmg_
 int hmg_ssc(hmg_ctx* ctx, int nz, int n, int np, const double* d_R /*[np][nz][n]*/,
             const double* d_zscale /*[np][nz] or NULL*/, const double* d_g /*[nz]*/, double* d_cov /*[np n][np n]*/);
 
+/* ---- the 2-, 3- and 4-halo terms of the trispectrum of two spectra ----------------------------
+ * The trispectrum T(k_i, -k_i, k_j, -k_j) of the spectra (a, b) at +-k_i and (c, d) at +-k_j, averaged over the angle
+ * between k_i and k_j with a rule of nr <= 256 nodes: d_mu, d_omm = 1 - mu, d_opm = 1 + mu (arrays of their own, formed
+ * without cancellation) and weights d_w that sum to 1.  Tables and sampled quantities (w_x, k_s, P_s, J_x, D_s) as for
+ * hmg_bispectrum, S_xy as for hmg_trispectrum_1h; n <= 256.
+ * hmg_pt_averages: three (nz, n, n) matrices of plain arrays d_ks (nk), d_Pzk (nz, nk), 2 <= nk <= 8192 (the row's ln k and ln P sit in LDS).  Per node,
+ *   q-+^2 = (k_i - k_j)^2 + 2 k_i k_j (1 -+ mu)  (never a difference of squares),  P(q) = exp of the linear interpolant of
+ *   ln Pzk in ln ks, continued beyond either end with the end panel's slope,  F2 of hmg_bispectrum:
+ *   Pbar = sum_t w_t P(q+)
+ *   Bbar = sum_t w_t 2 [F2(q+,k_i;k_j) P(q+) P_i + F2(q+,k_j;k_i) P(q+) P_j + F2(k_i,k_j;q+) P_i P_j]
+ *   Tbar = sum_t w_t {12 F3s(k_i,-k_i,k_j) P_i^2 P_j + 12 F3s(k_j,-k_j,k_i) P_j^2 P_i
+ *                     + sum_{q = q-, q+} 4 P(q) [F2(q,k_j;k_i) P_j + F2(q,k_i;k_j) P_i]^2}
+ *   F3s from the recursion for F_n, G_n, symmetrised, orderings with a vanishing partial sum dropped.  Each unordered
+ *   pair is evaluated once, its sides ordered by (k, P), and mirrored: the matrices are bit-symmetric.
+ * hmg_trispectrum_connected: d_T (5, nz, n, n) = (T1h, T2h13, T2h22, T3h, T4h), with w = wm nzm bh,
+ *   I_{x,cd}(i;j) = sum_m w w_x(i) S_cd(j),  I_xy(i,j) = sum_m w s_xy(i,j),  s_xy = w_x(i) w_y(j), or, of twice the same
+ *   HOD, [(u_c(i) u_s(j) + u_s(i) u_c(j)) <NcNs> + <Ns(Ns-1)> u_s(i) u_s(j)] / ngal^2 (u at the samples; u_c = 1 without d_cprof):
+ *   T1h   = hmg_trispectrum_1h's with d_scale1h (its caller's scale: damping folded in), the same bits
+ *   T2h13 = sig D_i D_j {P_i [J_a(i) I_{b,cd} + J_b(i) I_{a,cd}] + P_j [J_c(j) I_{d,ab} + J_d(j) I_{c,ab}]}
+ *   T2h22 = sig (D_i D_j)^2 Pbar [I_ac I_bd + I_ad I_bc]
+ *   T3h   = sig D_i D_j Bbar [I_ac J_b(i) J_d(j) + I_bd J_a(i) J_c(j) + I_ad J_b(i) J_c(j) + I_bc J_a(i) J_d(j)]
+ *   T4h   = sig Tbar J_a(i) J_b(i) J_c(j) J_d(j),       sig = scale_i scale_j
+ * Linear halo bias only; three or four galaxies in one halo are formed as w_g S_gg and S_gg S_gg (no third factorial
+ * moment).  d_Tz (5, n, n) = sum_z zweights[z] T[:, z], z in order, needs d_zweights; either output may be NULL, not both.
+ * All HOD tracers of a call must be the same one.  The tables are checked on the device before any tensor is read
+ * through them and the host waits for that answer: neither call can be part of a captured step.  fp64 on the vector
+ * units, every workgroup walks the whole mass axis in order, no atomics: bit-identical on repeat, an element depends only
+ * on its own (z, i, j) entries.                                                                                        */
+int hmg_pt_averages(hmg_ctx* ctx, int nz, int nk, int n, int nr, const double* d_ks, const double* d_Pzk,
+                    const int* d_idx /*[nz][n]*/, const double* d_frac,
+                    const double* d_mu /*[nr]*/, const double* d_omm, const double* d_opm, const double* d_w,
+                    double* d_Pbar /*[nz][n][n]*/, double* d_Bbar, double* d_Tbar);
+int hmg_trispectrum_connected(hmg_ctx* ctx, int nz, int nm, int nk, int n, int nr,
+                              const hmg_tracer* h_a, const hmg_tracer* h_b, const hmg_tracer* h_c, const hmg_tracer* h_d,
+                              const double* d_nzm, const double* d_bh, const double* d_ms, const double* d_wm,
+                              const double* d_ks, const double* d_Pzk, double rho_m0, double kstar /*<= 0: no damping*/,
+                              const int* d_idx /*[nz][n]*/, const double* d_frac, const double* d_scale,
+                              const double* d_scale1h,
+                              const double* d_mu /*[nr]*/, const double* d_omm, const double* d_opm, const double* d_w,
+                              const double* d_zweights /*[nz] or NULL*/,
+                              double* d_T /*[5][nz][n][n] or NULL*/, double* d_Tz /*[5][n][n] or NULL*/);
+
 /* ---- projected generalised-NFW profiles: gas surface density, optical depth, Compton y --------
  * Row h is one profile f(x) = x^gamma (1 + x^alpha[h])^(-eta[h]), zero beyond x = xcut[h]; gamma > -1 is one number for
  * the call.  d_x holds the projected radii in the rows' scaled units: (n, nr) when per_row_x != 0, else one row of nr shared

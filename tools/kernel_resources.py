@@ -1,6 +1,6 @@
 """Resource table of the kernels a pass launches: registers, scratch reservation, occupancy and
 - the part the compiler's summary does not tell - how many scratch INSTRUCTIONS and SGPR-spill lane moves the ISA
-holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, hankel.hip, angcov.hip, curvedsky.hip, nonlimber.hip, trispectrum.hip, bispectrum.hip, response.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip, cib.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
+holds and where.  Reads the .resources.txt and .s files of hmgrid.hip, longgrid.hip, lensing.hip, ksz.hip, realspace.hip, hankel.hip, angcov.hip, curvedsky.hip, nonlimber.hip, trispectrum.hip, bispectrum.hip, response.hip, connected.hip, gasproj.hip, rsd.hip, onepoint.hip, hodens.hip, clusters.hip, cib.hip and sampled.hip (`make -C hmvec_amd/csrc asm`).
 Usage: python tools/kernel_resources.py > profiles/rNN/kernel_resources.txt"""
 import os
 import re
@@ -82,6 +82,8 @@ KERNELS = [   # (label, regex on the mangled name)
     ("bispectrum_check_kernel  (its table and triangle check, bispectrum.hip)", r"23bispectrum_check_kernelE"),
     ("response_pairs_kernel  (response of halo-model spectra to a long mode: A1, I1 and the epilogue, response.hip)", r"21response_pairs_kernelE"),
     ("ssc_kernel  (super-sample contraction, 64 x 64 tile, response.hip)", r"10ssc_kernelE"),
+    ("pt_average_kernel  (angle-averaged PT matrices Pbar, Bbar, Tbar, one thread per (z, i <= j), dynamic LDS 8 (2 nk + 4 nr) B, connected.hip)", r"17pt_average_kernelE"),
+    ("connected_kernel  (2-, 3- and 4-halo terms of the trispectrum, 32 x 32 tile, 2 x 2 register block, connected.hip)", r"16connected_kernelE"),
     ("gnfw_projected_kernel  (projected gas / pressure profile: Sigma, mean, excess; gasproj.hip)", r"21gnfw_projected_kernelE"),
     ("gnfw_smooth_kernel<4>  (the projection through a Gaussian beam, gasproj.hip)", r"18gnfw_smooth_kernelILi4EE"),
     ("rsd_wedge_kernel<true>  (redshift-space wedges P1h, P2h, 8 nodes of mu per thread, rsd.hip)", r"16rsd_wedge_kernelILb1EE"),
@@ -118,7 +120,7 @@ KERNELS = [   # (label, regex on the mangled name)
 def main():
     if "--no-build" not in sys.argv:
         subprocess.run(["make", "-j2", "-B", "-C", CSRC, "asm"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "hankel", "angcov", "curvedsky", "nonlimber", "trispectrum", "bispectrum", "response", "gasproj", "rsd", "onepoint", "hodens", "clusters", "cib", "sampled")
+    units = ("hmgrid", "longgrid", "lensing", "ksz", "realspace", "hankel", "angcov", "curvedsky", "nonlimber", "trispectrum", "bispectrum", "response", "connected", "gasproj", "rsd", "onepoint", "hodens", "clusters", "cib", "sampled")
     res = "".join(open(os.path.join(CSRC, u + ".resources.txt")).read() for u in units)
     asm = "".join(open(os.path.join(CSRC, u + ".s")).read() for u in units)
     from hmvec_amd._native import kernel_source_sha16
